@@ -11,7 +11,9 @@ Multi-GPU is independent-batch (weak scaling, no collective on the data path): e
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 under torch.distributed.run)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline fields; --full adds every
+other leg (long run, per-kernel events and roofline, host-boundary loops, CPU baseline and parity, device, front end, single window).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -64,6 +66,50 @@ def make_chain(h, ba, seqs, packed, flags):
         assert all(s['status'] == 0 for s in sm), "chain solve failed"
         chain.append(ba.PackedBatch([q.next_window(st[i], 'resident', k + 1) for i, q in enumerate(seqs)]))
     return chain
+
+
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: cap of all files together
+
+
+def write_outputs(path, st, sm, pr):
+    """--dump-outputs: what vg_ba_batch_download handed back after the last timed step -- per window the states, the solver summary and
+    the marginalization prior -- as float64 arrays, one DIR/<name>.npy each.  Ragged parts (landmark depths, prior blocks) are
+    concatenated or zero-padded, with their sizes in arrays of their own.  Above DUMP_MAX_BYTES a fixed sample of the windows is
+    written (seed 0; their indices in windows.npy)."""
+    n = len(st)
+
+    def arrays(idx):
+        s = [st[i] for i in idx]
+        q = [pr[i] for i in idx]
+        dims = np.array([[p['n'], p['m']] if p else [0, 0] for p in q], np.float64)
+        pn = int(dims[:, 0].max()) if len(q) else 0
+        J0, r0 = np.zeros((len(q), pn, pn)), np.zeros((len(q), pn))
+        for j, p in enumerate(q):
+            if p:
+                J0[j, :p['n'], :p['n']], r0[j, :p['n']] = p['J0'], p['r0']
+        out = {"windows": np.asarray(idx, np.float64),
+               "pose": np.stack([x['pose'] for x in s]), "speed_bias": np.stack([x['sb'] for x in s]),
+               "extrinsic": np.stack([x['ex'] for x in s]), "td": np.array([x['td'] for x in s], np.float64),
+               "n_landmarks": np.array([len(x['inv_depth']) for x in s], np.float64),
+               "inv_depth": np.concatenate([x['inv_depth'] for x in s]),
+               "summary": np.array([[sm[i][k] for k in ("status", "termination", "num_iterations", "num_accepted", "initial_cost",
+                                                         "final_cost", "final_radius")] for i in idx], np.float64),
+               "prior_dims": dims, "prior_J0": J0, "prior_r0": r0,
+               "prior_x0": np.concatenate([np.concatenate(p['x0']) if p else np.zeros(0) for p in q])}
+        if all('relo_pose' in x for x in s) and s:
+            out["relo_pose"] = np.stack([x['relo_pose'] for x in s])
+        return out
+    idx = list(range(n))
+    out = arrays(idx)
+    size = sum(a.nbytes for a in out.values())
+    while size > DUMP_MAX_BYTES and len(idx) > 1:
+        k = max(1, int(len(idx) * DUMP_MAX_BYTES / size * 0.9))
+        idx = sorted(np.random.default_rng(0).choice(n, k, replace=False).tolist())
+        out = arrays(idx)
+        size = sum(a.nbytes for a in out.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def bench_resident(ba, synth, seqs, nthr=4, rounds=3):
@@ -378,6 +424,8 @@ def bench_sharded(args, ba, synth, D, rank, world):
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = D.max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, *h.ba_download())        # (rank 0's landmark shard)
     # per-launch HIP events (outside the timed region; every rank runs the pass: the collectives need all of them)
     prof = {}
     runs = 5
@@ -688,7 +736,16 @@ def main():
     ap.add_argument("--emulated", action="store_true",
                     help="contract self-test WITHOUT a GPU (tests/test_bench_contract.py): the kernel sources under the CPU fiber emulator of "
                          "tests/simt, tiny loop counts; every number it prints is meaningless except that the line has the right shape")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure (--config batch): the long run, per-kernel event passes and roofline, the "
+                         "host-boundary loops, resident sequences, CPU baseline and parity, device information, the front-end leg and the "
+                         "single-window latency.  Without it the run sets up, warms up, times the K steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (states, summaries, marginalization priors of "
+                         "rank 0's windows) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     # N > 1: one process per GPU.  The driver starts the ranks itself (python -m torch.distributed.run ... bench.py --gpus N); a plain
     # `python bench.py --gpus N` starts them here, so that the command can never silently time ONE GPU and print n_gpus: 1.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -760,7 +817,6 @@ def main():
     flags = [ba.VG_MARGIN_OLD] * nwin
     for hh in handles:
         hh.ba_upload(packed, flags)                  # inputs now resident in HBM (every stream owns its copy of the batch)
-    info = h.ba_info()
 
     def barrier():
         cuda_sync()
@@ -788,6 +844,8 @@ def main():
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = D.max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, *handles[(args.steps - 1) % nfl].ba_download())     # the handle of the last timed step
     if args.profile_loop:
         if rank == 0:
             print(json.dumps({"metric": "sliding-window BA solves/sec (profile loop: timed region only)", "value": world * nwin * args.steps / elapsed,
@@ -797,6 +855,34 @@ def main():
             hh.close()
         D.finish()
         return
+    line = {
+        "metric": "sliding-window BA solves/sec (Estimator::optimization: 8-iteration dogleg solve + marginalization)",
+        "value": world * nwin * args.steps / elapsed,
+        "unit": "solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"batch of {nwin} independent EuRoC-shape windows per step and GPU (K=11 frames, ~150 landmarks, "
+                               f"10 IMU factors, ~600 projection factors, 75-dim marginalization prior, max 8 iterations, "
+                               f"MARGIN_OLD marginalization); windows resident in HBM; consecutive steps are issued to "
+                               f"{nfl} HIP streams (independent batches in flight)",
+                   "windows_per_gpu": nwin, "batches_in_flight": nfl, "launch": h.ba_launch_stats(),
+                   "parallelism": f"independent batches x{world} (no collectives)"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        for hh in handles:
+            hh.close()
+        D.finish()
+        return
+    info = h.ba_info()                               # (h still holds the timed batch)
 
     # the same loop ten times as long (>= 200 steps): the timed region above is ~50 ms, too short for round-to-round deltas of a
     # few per cent to mean much; reported next to `value`, never instead of it
@@ -1094,28 +1180,12 @@ def main():
                     cpu["reference_sources_on_stand_in_headers_ms"] = float(np.median(t_ref[1:])) * 1e3
             except Exception as ex:                       # noqa: BLE001  (informational: never fails the bench)
                 cpu["reference_sources_on_stand_in_headers_ms"] = f"unavailable: {ex!r}"
-        out = {
-            "metric": "sliding-window BA solves/sec (Estimator::optimization: 8-iteration dogleg solve + marginalization)",
-            "value": value,
-            "unit": "solves/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+        out = dict(line)
+        out["config"] = dict(line["config"], launch=launch_stats, valid_solves=n_ok)
+        out.update({
             "value_long_run": world * nwin * n_long / long_elapsed,      # the regression signal: the same loop over >= 200 steps (long_run)
             "long_run": {"steps": n_long, "value": world * nwin * n_long / long_elapsed, "ms_per_step": long_elapsed / n_long * 1e3,
                          "what": "the same timed loop over ten times as many steps (run right after the timed region)"},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"batch of {nwin} independent EuRoC-shape windows per step and GPU (K=11 frames, ~150 landmarks, "
-                                   f"10 IMU factors, ~600 projection factors, 75-dim marginalization prior, max 8 iterations, "
-                                   f"MARGIN_OLD marginalization); windows resident in HBM; consecutive steps are issued to "
-                                   f"{nfl} HIP streams (independent batches in flight)",
-                       "windows_per_gpu": nwin, "batches_in_flight": nfl, "launch": launch_stats,
-                       "parallelism": f"independent batches x{world} (no collectives)", "valid_solves": n_ok},
             "roofline": roofline,
             "cpu_baseline": cpu,
             "parity": parity,
@@ -1152,7 +1222,7 @@ def main():
                                                 "new observations / state guess / pre-integration go in and the states come back, the track "
                                                 "bookkeeping (addFeatureCheckParallax, triangulate, problem tables, slideWindow) runs on the device; "
                                                 "NOT the metric (bench contract: `value` is device-resident)"},
-        }
+        })
     fe_out = bench_fe(h, synth, 2 if QUICK else max(args.steps, 10), args.warmup, rank, rank == 0 and world == 1 and not args.no_cpu_baseline)
     fe_out["value_all_gpus"] = D.sum_over_ranks(fe_out["value"])
     # single-window latency (configs[2]) on rank 0

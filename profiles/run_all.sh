@@ -5,7 +5,7 @@
 set -u
 TAG=$1
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-bash "$ROOT/profiles/run_profile.sh" "$TAG" --steps 20 --warmup 5 > /dev/null
+bash "$ROOT/profiles/run_profile.sh" "$TAG" --full --steps 20 --warmup 5 > /dev/null
 bash "$ROOT/profiles/run_profile.sh" "${TAG}_sharded" --config sharded --steps 10 --warmup 2 > /dev/null
 bash "$ROOT/profiles/run_pmc.sh" "$TAG" > /dev/null
 ls -la "$ROOT"/gpurun_out/${TAG}*

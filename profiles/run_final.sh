@@ -12,7 +12,7 @@ mkdir -p gpurun_out
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --no-cpu-baseline --steps 5 --warmup 1 --in-flight 1"
+CMD="python $ROOT/bench.py --full --no-cpu-baseline --steps 5 --warmup 1 --in-flight 1"
 timeout 110 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/fetch" -o fetch -- $CMD > "$OUT/fetch.log" 2>&1
 timeout 110 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/write" -o write -- $CMD > "$OUT/write.log" 2>&1
 cd "$ROOT"

@@ -249,7 +249,7 @@ def write_seq_file(path, sources, K, n_frames, min_parallax=10.0 / 460.0, init_d
 def drive_sequence(h_seq, sources, wins, K, n_frames, min_parallax=10.0 / 460.0, init_depth=5.0):
     """The same frames through the Python binding: what ResidentEstimators does on the host (processIMU's propagation, the
     pre-integration of the running and of merged intervals), restated here.  Returns [frame][source] = (P, q_wxyz, V, flag, n)."""
-    from oracle import ref as R
+    from oracle import ba_numpy as B
     n = len(sources)
     probs, trks = zip(*[synth.sequence_inputs(w) for w in wins])
     h_seq.seq_begin(list(probs), list(trks), max_features=512, max_new_obs=512, init_depth=init_depth, min_parallax=min_parallax)
@@ -280,7 +280,8 @@ def drive_sequence(h_seq, sources, wins, K, n_frames, min_parallax=10.0 / 460.0,
             else:
                 prev[i], merged[i] = cur[i], None
             q = st['pose'][K - 1][3:]
-            qm = R.quat_from_R(q2R(q))                              # (the C++ side prints Quaterniond(Rs[WINDOW_SIZE]))
+            qm = B.R2q(q2R(q))          # (the C++ side prints Quaterniond(Rs[WINDOW_SIZE]); B.R2q is pinned to that conversion in
+                                        #  tests/test_ref_parity.py, so the comparison needs no library built from the reference)
             row.append((st['pose'][K - 1][:3].copy(), np.array([qm[3], qm[0], qm[1], qm[2]]), st['sb'][K - 1][:3].copy(), info[i]['flag'], info[i]['n_after']))
         out.append(row)
     h_seq.seq_end()

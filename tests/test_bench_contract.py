@@ -1,4 +1,4 @@
-"""bench.py's output contract, checked WITHOUT a GPU: `python bench.py --emulated` runs every leg of the default bench (timed loop,
+"""bench.py's output contract, checked WITHOUT a GPU: `python bench.py --emulated --full` runs every leg of the bench (timed loop,
 per-kernel events, boundary loops, resident sequences, CPU baseline + parity, front end, single window) against the kernel sources
 under the CPU fiber emulator with tiny loop counts.  The numbers are meaningless; what is checked is that the file still runs end to
 end and that the ONE JSON line has the fields and types the driver reads (a bench that crashes at round end is unmeasured work)."""
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_has_the_contract_shape():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emulated", "--windows", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emulated", "--full", "--windows", "2", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -49,6 +49,36 @@ def test_bench_line_has_the_contract_shape():
     assert fe["unit"] == "features/s" and fe["tracked_last_step"] > 0
     assert (rf_fe["bound"] == "hbm" and rf_fe["unit"] == "GB/s") or (rf_fe["bound"] == "valu" and rf_fe["hbm"]["unit"] == "GB/s" and 0 < rf_fe["frac"])
     assert d["single_window"]["solve_pipeline_ms"] > 0 and d["single_window_latency_ms"] > 0
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the run sets up, warms up, times the K steps and prints the headline fields only; --dump-outputs writes what the
+    last timed step computed as float64 arrays (<= 64 MB), and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emulated", "--windows", "2", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)):
+            assert k in line and isinstance(line[k], t), (k, type(line.get(k)))
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "solves/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+        assert abs(line["value"] - 2 * line["steps"] / (line["ms_per_step"] * 1e-3 * line["steps"])) < 1e-6 * line["value"]
+        assert not {"long_run", "roofline", "cpu_baseline", "parity", "device", "fe", "single_window", "host_boundary_inclusive"} & set(line)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {"pose.npy", "speed_bias.npy", "inv_depth.npy", "summary.npy", "prior_J0.npy", "prior_r0.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    pose, summary = np.load(dirs[0] / "pose.npy"), np.load(dirs[0] / "summary.npy")
+    assert pose.shape == (2, 11, 7) and np.isfinite(pose).all() and (summary[:, 0] == 0).all()       # (column 0: status)
 
 
 def test_sharded_bench_line_runs_end_to_end():
