@@ -9,6 +9,7 @@ from oracle import ba_numpy as B
 from vins_mono_amd import ba, synth
 
 import ba_fixtures as FX
+from ba_step_ref import relocalisation_problem       # (moved there with the other window builders; re-exported for its importers)
 
 pytestmark = pytest.mark.gpu
 
@@ -470,28 +471,6 @@ def test_marginalize_second_new_keeps_old_prior_when_pose_absent(handle):
 
 
 # ---------------------------------------------------------------------------------------- edge cases / full size
-def relocalisation_problem(seed=51, loop_frame=3):
-    """A window with relocalisation factors: loop frame = a perturbed copy of frame `loop_frame`, matches for landmarks whose
-    track starts at or before it (estimator.cpp:781)."""
-    seq = synth.SyntheticSequence(seed, L=40)
-    prob = seq.window(0)
-    relo_pose = prob['pose'][loop_frame].copy()
-    relo_pose[:3] += [0.05, -0.03, 0.02]
-    match = []
-    c = seq.cfg
-    Rr, Pr = B.q2R(relo_pose[3:]), relo_pose[:3]
-    for l in range(len(prob['inv_depth'])):
-        if prob['lm_start'][l] <= loop_frame and len(match) < 15:
-            s = int(prob['lm_start'][l])
-            o = prob['obs'][int(prob['obs_off'][l])]
-            pc = np.array([o[0], o[1], 1.0]) / prob['inv_depth'][l]
-            Xw = B.q2R(prob['pose'][s][3:]) @ (c['ric'] @ pc + c['tic']) + prob['pose'][s][:3]
-            p = c['ric'].T @ (Rr.T @ (Xw - Pr) - c['tic'])
-            match.append((l, p[0] / p[2], p[1] / p[2]))
-    prob['relo'] = dict(pose=relo_pose, match=match)
-    return prob
-
-
 def test_relocalisation_factors(handle):
     """estimator.cpp:769-801: extra ProjectionFactors to a relocalisation pose (an extra pose block)."""
     prob = relocalisation_problem()

@@ -87,12 +87,13 @@ def test_phase_function_keeps_its_address_spaces(funcs, frag):
 
 
 def test_kernels_do_not_fall_back_to_flat_memory(funcs):
-    for k in ("ba_accumulate_kernel", "ba_linacc_proj_kernel", "ba_linearize_imu_kernel", "ba_linearize_proj_kernel", "ba_solve_kernel", "fe_lk_kernel"):
+    for k in ("ba_accumulate_kernel", "ba_linacc_proj_kernel", "ba_linearize_imu_kernel", "ba_linearize_proj_kernel", "ba_solve_kernel", "ba_solve_w8_kernel",
+              "fe_lk_kernel"):
         for name in _find(funcs, k):
             ops = funcs[name]
             # the top level of the solve kernel re-reads its context struct from the private stack after the phase calls (its
             # address is handed to them on purpose): a few dozen flat accesses per launch, none in a loop
-            limit = 40 if name == "ba_solve_kernel" else 4
+            limit = 40 if name in ("ba_solve_kernel", "ba_solve_w8_kernel") else 4
             assert _count(ops, "flat_load") + _count(ops, "flat_store") <= limit, name
 
 
@@ -149,6 +150,12 @@ def test_solve_kernel_keeps_its_uniform_state_out_of_scratch():
     assert int(k["vgpr_spill_count"]) <= 80, k
     assert int(k["private_segment_fixed_size"]) <= 640, k
     assert int(k["group_segment_fixed_size"]) == 0, k
+    # the 8-wavefront build of the same source (csrc/ba_solve_w8.hip), the kernel of every call with fewer than 32 windows -- the
+    # drop-in's single window among them: the same arrangement, the same bounds
+    k = md["ba_solve_w8_kernel"]
+    assert int(k["vgpr_spill_count"]) <= 80, k
+    assert int(k["private_segment_fixed_size"]) <= 640, k
+    assert int(k["group_segment_fixed_size"]) == 0, k
 
 
 def test_chain_elimination_loop_stays_out_of_scratch(funcs):
@@ -165,8 +172,37 @@ def test_solve_kernel_fits_two_windows_per_cu():
     file of a CU; the LDS half of the bargain (<= 80 KB for the reference shape) is checked on the layout in tests/test_abi_and_host.py."""
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump of the ROCm toolchain not found")
-    k = _kernel_metadata()["ba_solve_kernel"]
+    md = _kernel_metadata()
+    k = md["ba_solve_kernel"]
     assert int(k["max_flat_workgroup_size"]) == 256 and int(k["vgpr_count"]) <= 256, k
+    # the 8-wavefront build: 512 threads = two wavefronts per SIMD, each within 256 of the 512 registers of a SIMD lane, ONE workgroup per CU
+    k = md["ba_solve_w8_kernel"]
+    assert int(k["max_flat_workgroup_size"]) == 512 and int(k["vgpr_count"]) <= 256, k
+
+
+def test_widest_single_workgroup_window_fits_the_lds_of_a_cu(simt_handle):
+    """build_layout holds the DYNAMIC carve of the solve kernel against 160 KB; a launch must fit together with the kernel's static
+    group segment, and a launch that does not fit fails only on the hardware (the emulator has no LDS limit).  The widest window
+    of the single-workgroup path -- 12 frames + relocalisation pose + extrinsic + td, Rc = 85, RcPad = 96 -- at the largest
+    landmark count of tests/test_ba_step.py: carve + the staged landmark tile of the 8-wavefront build, [RcPad][32 + 1] doubles, +
+    the static segment of the compiled kernel <= 160 KB, and likewise for the 4-wavefront build."""
+    if not os.path.exists(OBJDUMP):
+        pytest.skip("llvm-objdump of the ROCm toolchain not found")
+    from oracle import ba_numpy as B
+    import ba_step_ref as R
+    seq = R.ruled_sequence(3, 12, 218, estimate_extrinsic=1, estimate_td=1)
+    prob = R.add_relocalisation(seq.window(0), seq.cfg)
+    lay = B.Layout(prob)
+    Rc = lay.R - 9 * lay.K
+    RcPad = (Rc + 1 + 15) // 16 * 16
+    assert (Rc, RcPad) == (85, 96)
+    simt_handle.ba_upload([prob])
+    info = simt_handle.ba_info()
+    assert all(info['flops_by_kernel'][k] == 0 for k in ("ba_big_schur_kernel", "ba_solve_big_kernel", "ba_big_step_kernel"))     # not the large path
+    md = _kernel_metadata()
+    carve = info['lds_bytes']
+    assert carve + 8 * RcPad * 33 + int(md["ba_solve_w8_kernel"]["group_segment_fixed_size"]) <= 160 * 1024, carve
+    assert carve + int(md["ba_solve_kernel"]["group_segment_fixed_size"]) <= 160 * 1024, carve
 
 
 def test_factor_and_marginalization_kernels_stay_within_their_register_budgets():
