@@ -592,6 +592,29 @@ typedef struct vg_fe_frame_in {
 } vg_fe_frame_in;
 int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* out);
 
+/* ---- The same for EVERY stream of a handle in one call (added within ABI 12): readImage of in[c] for stream c of a handle configured
+ * with n_cams == n_streams (any other n_streams: VG_ERR_BAD_ARG; the batched streams advance together), out[c] with exactly the
+ * meaning, the values and the lifetime of the single call's result for that stream.  One upload, one launch per step over all streams
+ * (tracking, image build, stamping and detection are indexed by stream; the steps between them run one workgroup per stream; the
+ * RANSAC of all streams runs in two parts around the iteration bookkeeping instead of 1000 iterations per stream), one download after
+ * rejectWithF, one after the detection.  When to use which: one camera -> vg_fe_read_image (lowest latency); many cameras or many
+ * sequences replayed together -> one handle with n_cams streams and this call.
+ *   per stream  (from in[c]):  img / stride, cur_xy / n, publish, max_cnt, intr, focal_length, f_threshold, base_mask, order / user.
+ *               Streams that publish and streams that do not may be mixed; one that does not costs the detection an early exit.
+ *   uniform     equalize over all streams; quality and min_dist over the streams that publish (the batched image build and the
+ *               detection take ONE value each): a call that mixes them is VG_ERR_BAD_ARG.
+ *   frames      every in[c].img NULL: the frames are the ones the last vg_fe_upload_frames put into the selected slot (nothing is
+ *               uploaded; benchmarks time the device work this way).  Some NULL, some not: VG_ERR_BAD_ARG.
+ *   walk order  after rejectWithF of all streams ONE download, then the `order` callbacks on the calling thread in ascending stream
+ *               order (streams that publish, have n2 > 0 and a callback), then ONE upload of all orders.
+ *   host cases  8 <= survivors < 15 (LMedS) and a sample OpenCV would have redrawn go back to the host per stream, as in the single call.
+ * Failure semantics as for the single call: everything that follows from the arguments alone (sizes, a point list on a handle without
+ * a previous frame, mixed uniform fields, n_streams, frames for some streams only) is refused BEFORE any frame is uploaded and no stream
+ * has moved; an error after that (a callback's, a detection overflow, a HIP error) leaves ALL streams one frame ahead of the caller,
+ * who re-starts them with vg_fe_configure.  Limits: max_points <= 2048, rejectWithF on at most 1024 tracking survivors per stream;
+ * the first call allocates the per-stream tables (about 0.45 MB of device memory per stream). */
+int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_frame_in* in /* [n_streams] */, vg_fe_frame_out* out /* [n_streams] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,10 @@
 //   :71-79, :258-268  addPoints + undistortedPoints (liftProjective of the final list) -> fe_ri_finish_kernel
 // All of them are single-workgroup kernels on <= a few hundred points: what matters is that they need no round trip, not their
 // arithmetic.  Compiled with -ffp-contract=off: the lifting evaluates the reference's double expressions as written.
+//
+// vg_fe_read_image_batch runs the same frame for every stream of a handle: the fe_rb_* kernels at the end of this file have one
+// workgroup (the walk: one wavefront) PER STREAM, rebuild the stream's RiDev from the device tables of RbDev and run the very bodies
+// (ri_*_body) the single-stream kernels run.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vg_target.h"
@@ -51,8 +55,7 @@ FDEV int ri_compact(const uint8_t* flag, int n, const int* src, int* dst, int* w
 }
 
 // After the tracking kernel.  One workgroup.
-extern "C" __global__ __launch_bounds__(256) void fe_ri_after_lk_kernel(FeDev d, RiDev r) {
-    __shared__ int wsum[4];
+FDEV void ri_after_lk_body(const FeDev& d, const RiDev& r, int* wsum) {
     const int tid = threadIdx.x;
     const int n = r.ctl[RI_N], publish = r.ctl[RI_PUBLISH];
     // :115-117  status[i] && inBorder(forw_pts[i])  (BORDER_SIZE 1, cvRound = round half to even)
@@ -101,15 +104,19 @@ extern "C" __global__ __launch_bounds__(256) void fe_ri_after_lk_kernel(FeDev d,
         }
     }
 }
+extern "C" __global__ __launch_bounds__(256) void fe_ri_after_lk_kernel(FeDev d, RiDev r) {
+    __shared__ int wsum[4];
+    ri_after_lk_body(d, r, wsum);
+}
 
 // After fe_ransac7_kernel / fe_ransac_count_kernel: the registrator's loop over the iterations (ptsetreg.cpp RANSACPointSetRegistrator::run
 // as restated in fe_ransac.hip: a model replaces the best one if it has more inliers than max(best, 6); after every improvement the
 // iteration bound shrinks to RANSACUpdateNumIters(...), read from the host-made table; iterations at or beyond the bound do not
 // count), then the mask of the winning model and reduceVector by it.  One workgroup; the loop itself runs on one wavefront with the
 // counts of 64 iterations in a register each (v_readlane in sequence: the bound usually ends the loop inside the first chunk).
-extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
-    __shared__ int wsum[4];
-    __shared__ int sbest;
+// The batched call runs the loop in two parts with RANSAC work between them: iterations [it0, stop) per part, the state (bound, best
+// count, best iteration) carried in ctl; `final`: the last part, which also makes the mask.  The single call: (0, FE_RANSAC_MAXIT, true).
+FDEV void ri_pick_body(const RiDev& r, const int it0, const int stop, const bool final, int* wsum, int& sbest) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int n1 = r.ctl[RI_N1];
     if (r.ctl[RI_PUBLISH] == 0 || r.ctl[RI_RANSAC] == 0) return;
@@ -117,10 +124,11 @@ extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
     if (fb & (RI_FB_LMEDS | RI_FB_RANGE)) return;                   // (header already written by fe_ri_after_lk_kernel)
     if (tid < 64) {
         int niters = FE_RANSAC_MAXIT, max_good = 0, best = -1;
+        if (it0 > 0) { niters = r.ctl[RI_NITERS]; max_good = r.ctl[RI_MAXGOOD]; best = r.ctl[RI_BEST]; }
         const int* tab = r.niters_tab + (size_t)n1 * r.tab_stride;
-        for (int base = 0; base < FE_RANSAC_MAXIT && base < niters; base += 64) {
-            const int mine = base + lane < FE_RANSAC_MAXIT ? r.count[base + lane] : -1;
-            for (int j = 0; j < 64 && base + j < niters && base + j < FE_RANSAC_MAXIT; ++j) {
+        for (int base = it0; base < stop && base < niters; base += 64) {
+            const int mine = base + lane < stop ? r.count[base + lane] : -1;
+            for (int j = 0; j < 64 && base + j < niters && base + j < stop; ++j) {
                 const int c = __shfl(mine, j);
                 if (c > (max_good > 6 ? max_good : 6)) {
                     best = base + j; max_good = c;
@@ -129,8 +137,9 @@ extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
                 }
             }
         }
-        if (lane == 0) { sbest = best; r.ctl[RI_BEST] = best; r.ctl[RI_NITERS] = niters; }
+        if (lane == 0) { sbest = best; r.ctl[RI_BEST] = best; r.ctl[RI_NITERS] = niters; if (!final) r.ctl[RI_MAXGOOD] = max_good; }
     }
+    if (!final) return;
     __syncthreads();
     const int best = sbest;
     const int nw = (n1 + 63) >> 6;
@@ -147,6 +156,11 @@ extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
         r.a_hdr[RI_RANSAC] = 1; r.a_hdr[RI_BEST] = best; r.a_hdr[RI_NITERS] = r.ctl[RI_NITERS];
     }
 }
+extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
+    __shared__ int wsum[4];
+    __shared__ int sbest;
+    ri_pick_body(r, 0, FE_RANSAC_MAXIT, true, wsum, sbest);
+}
 
 // setMask (:36-69) in a given order: position q of the walk is survivor order[q] (order == nullptr: the list as it stands).  A point is
 // kept iff its rounded position is inside the image, the base mask there is 255 and no previously kept point's filled disc covers it
@@ -158,8 +172,7 @@ extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
 //   3. the kept lanes store their results side by side (prefix popcount).
 // Also: n_max_cnt = MAX_CNT - kept (:144) for the detection.
 #define RI_SETMASK_MAX 2048
-extern "C" __global__ __launch_bounds__(64) void fe_ri_setmask_kernel(FeDev d, RiDev r) {
-    __shared__ short kx[RI_SETMASK_MAX], ky[RI_SETMASK_MAX];
+FDEV void ri_setmask_body(const FeDev& d, const RiDev& r, short* kx, short* ky) {
     const int lane = threadIdx.x, W = d.W, H = d.H;
     const int n2 = r.ctl[RI_N2];
     const int r2 = r.radius * r.radius;
@@ -203,10 +216,14 @@ extern "C" __global__ __launch_bounds__(64) void fe_ri_setmask_kernel(FeDev d, R
         const_cast<int*>(d.max_corners)[0] = room > 0 ? (room < d.max_pts ? room : d.max_pts) : 0;
     }
 }
+extern "C" __global__ __launch_bounds__(64) void fe_ri_setmask_kernel(FeDev d, RiDev r) {
+    __shared__ short kx[RI_SETMASK_MAX], ky[RI_SETMASK_MAX];
+    ri_setmask_body(d, r, kx, ky);
+}
 
 // addPoints (:71-79) + undistortedPoints (:262-267): the list the frame ends with = the kept points in the walk's order, then the new
 // corners; every point lifted.
-extern "C" __global__ __launch_bounds__(256) void fe_ri_finish_kernel(FeDev d, RiDev r) {
+FDEV void ri_finish_body(const FeDev& d, const RiDev& r) {
     const int tid = threadIdx.x;
     const int nk = r.ctl[RI_NK];
     const int nc = d.ncorners[0];
@@ -229,4 +246,68 @@ extern "C" __global__ __launch_bounds__(256) void fe_ri_finish_kernel(FeDev d, R
         r.ctl[RI_NNEW] = nc;
         r.b_hdr[RI_NK] = nk; r.b_hdr[RI_NNEW] = nc; r.b_hdr[RI_N2] = r.ctl[RI_N2];
     }
+}
+extern "C" __global__ __launch_bounds__(256) void fe_ri_finish_kernel(FeDev d, RiDev r) {
+    ri_finish_body(d, r);
+}
+
+// ================================================================================================ vg_fe_read_image_batch
+// Stream c of the batch as the single call sees a stream: its slices of the per-stream arrays of FeDev (next_xy, status, corners, the
+// detection's counters) and an RiDev made from the tables.  Everything here is uniform over the workgroup.
+FDEV void rb_stream(const RbDev& b, const int c, FeDev& d, RiDev& r) {
+    const size_t cap = (size_t)b.cap, mp = (size_t)d.max_pts;
+    d.next_xy += c * mp * 2; d.status += c * mp; d.corners += c * mp * 2; d.max_corners += c; d.ncorners += c;
+    const RiCam& k = b.cam[c];
+    r.ctl = b.ctl + (size_t)c * RI_CTL_INTS; r.xy_in = b.xy_in + c * cap * 2; r.cap = b.cap;
+    r.idx1 = b.idx1 + c * cap; r.idx2 = b.idx2 + c * cap; r.p1 = b.p1 + c * cap * 2; r.p2 = b.p2 + c * cap * 2;
+    r.order = b.ord_flag[c] ? b.order + c * cap : nullptr;
+    char* a = b.a + c * b.a_stride;
+    r.a_hdr = (int*)a; r.a_status_lk = (uint8_t*)(a + b.a_st); r.a_status_f = (uint8_t*)(a + b.a_sf); r.a_forw_xy = (float*)(a + b.a_fw);
+    r.a_un_xy = b.a_un + c * cap * 2;
+    char* q = b.b + c * b.b_stride;
+    r.b_hdr = (int*)q; r.b_kept = (int*)(q + b.b_k); r.b_new_xy = (float*)(q + b.b_nw); r.b_un_xy = (float*)(q + b.b_un);
+    r.niters_tab = b.niters_tab; r.tab_stride = b.tab_stride;
+    r.count = b.count + (size_t)c * FE_RANSAC_MAXIT; r.words = b.words + (size_t)c * FE_RANSAC_MAXIT * b.words_n;
+    r.focal = k.focal; r.half_w = k.half_w; r.half_h = k.half_h;
+    r.fx = k.fx; r.fy = k.fy; r.cx = k.cx; r.cy = k.cy; r.k1 = k.k1; r.k2 = k.k2; r.pp1 = k.pp1; r.pp2 = k.pp2;
+    r.max_cnt = k.max_cnt; r.radius = k.radius;
+    r.kept_xy = b.kept_xy + c * cap * 2;
+    r.base_mask = (b.base && k.has_base) ? b.base + (size_t)c * d.W * d.H : nullptr;
+}
+
+// grid (S), 256 threads.  Besides the single call's work: every stream starts the frame with no kept point and NO detection (a
+// negative corner budget: fe_mineig_kernel / fe_select_kernel leave at once); fe_rb_setmask_kernel sets both for the streams that publish.
+extern "C" __global__ __launch_bounds__(256) void fe_rb_after_lk_kernel(FeDev d, RbDev b) {
+    __shared__ int wsum[4];
+    const int c = blockIdx.x;
+    RiDev r;
+    rb_stream(b, c, d, r);
+    if (threadIdx.x == 0) { b.nk[c] = 0; const_cast<int*>(d.max_corners)[0] = -1; }
+    ri_after_lk_body(d, r, wsum);
+}
+// grid (S), 256 threads; part 0: iterations [0, RB_CHUNK0), part 1: the rest and the mask
+extern "C" __global__ __launch_bounds__(256) void fe_rb_pick_kernel(FeDev d, RbDev b, int part) {
+    __shared__ int wsum[4];
+    __shared__ int sbest;
+    RiDev r;
+    rb_stream(b, blockIdx.x, d, r);
+    if (part == 0) ri_pick_body(r, 0, RB_CHUNK0, false, wsum, sbest);
+    else ri_pick_body(r, RB_CHUNK0, FE_RANSAC_MAXIT, true, wsum, sbest);
+}
+// grid (S), one wavefront
+extern "C" __global__ __launch_bounds__(64) void fe_rb_setmask_kernel(FeDev d, RbDev b) {
+    __shared__ short kx[RI_SETMASK_MAX], ky[RI_SETMASK_MAX];
+    const int c = blockIdx.x;
+    RiDev r;
+    rb_stream(b, c, d, r);
+    if (r.ctl[RI_PUBLISH] == 0) return;
+    ri_setmask_body(d, r, kx, ky);
+    if (threadIdx.x == 0) b.nk[c] = r.ctl[RI_NK];          // (lane 0 wrote it)
+}
+// grid (S), 256 threads
+extern "C" __global__ __launch_bounds__(256) void fe_rb_finish_kernel(FeDev d, RbDev b) {
+    RiDev r;
+    rb_stream(b, blockIdx.x, d, r);
+    if (r.ctl[RI_PUBLISH] == 0) return;
+    ri_finish_body(d, r);
 }

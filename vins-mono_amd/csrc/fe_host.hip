@@ -43,6 +43,13 @@ __global__ void fe_ri_finish_kernel(FeDev d, RiDev r);
 __global__ void fe_ransac7_kernel(const float* p1, const float* p2, int n, const int* sched, int nsched, double* models, int* ctl);
 __global__ void fe_ransac_count_kernel(const float* p1, const float* p2, int n, float thresh2, int lmeds, const double* models, int nsched,
                                        double* Fout, int* count, double* median, unsigned long long* inl_words, const int* ctl);
+// vg_fe_read_image_batch (fe_frame.hip, fe_ransac.hip)
+__global__ void fe_rb_after_lk_kernel(FeDev d, RbDev b);
+__global__ void fe_rb_pick_kernel(FeDev d, RbDev b, int part);
+__global__ void fe_rb_setmask_kernel(FeDev d, RbDev b);
+__global__ void fe_rb_finish_kernel(FeDev d, RbDev b);
+__global__ void fe_rb_ransac7_kernel(RbDev b, const int* sched, int part);
+__global__ void fe_rb_count_kernel(RbDev b, int part);
 }
 hipError_t fe_ransac_buffers(vg_handle* h, FeRansacBufs* b);
 void fe_ransac_tables(int nmax, std::vector<int>& sched, std::vector<int>& niters, int stride);
@@ -60,6 +67,26 @@ struct RiState {
     RiDev r;
 };
 static void ri_free(RiState* q) {
+    if (!q) return;
+    (void)hipFree(q->dev); (void)hipFree(q->d_sched); (void)hipFree(q->d_tab); (void)hipFree(q->d_base);
+    (void)hipHostFree(q->host);
+    delete q;
+}
+
+// resident state of vg_fe_read_image_batch: the tables of RbDev for every stream of the handle (one device allocation), the pinned
+// mirrors of what travels ([input | block A | lifted survivors | block B | orders]), the RANSAC tables
+struct RbState {
+    char* dev = nullptr;
+    char* host = nullptr;
+    size_t in_bytes = 0, a_bytes = 0, un_bytes = 0, b_bytes = 0, ord_bytes = 0, ord_flags_bytes = 0;
+    size_t o_ctl = 0, o_cam = 0, o_xy = 0;            // inside the input block
+    char *d_in = nullptr, *d_a = nullptr, *d_b = nullptr, *d_ord = nullptr;
+    int *d_sched = nullptr, *d_tab = nullptr;
+    uint8_t* d_base = nullptr;                        // [S][H][W] copies of the callers' fisheye masks
+    std::vector<const uint8_t*> base_src;
+    RbDev b;
+};
+static void rb_free(RbState* q) {
     if (!q) return;
     (void)hipFree(q->dev); (void)hipFree(q->d_sched); (void)hipFree(q->d_tab); (void)hipFree(q->d_base);
     (void)hipHostFree(q->host);
@@ -101,6 +128,7 @@ struct FeState {
     bool prev_clobbered = false;     // an upload has overwritten the frame slot the PREVIOUS pyramid uses as its level 0: no tracking until the next build
     std::vector<char> pushed_once;
     RiState* ri = nullptr;
+    RbState* rb = nullptr;
 };
 
 extern "C" void fe_state_destroy(FeState* s) {
@@ -113,6 +141,7 @@ extern "C" void fe_state_destroy(FeState* s) {
     (void)hipFree(s->sm_pts); (void)hipFree(s->sm_cnt); (void)hipFree(s->sm_n); (void)hipFree(s->sm_kidx); (void)hipFree(s->sm_nk);
     (void)hipFree(s->sm_kxy); (void)hipFree(s->sm_base); (void)hipFree((void*)s->sm_base_ptrs); (void)hipFree(s->lift_in); (void)hipFree(s->lift_out);
     ri_free(s->ri);
+    rb_free(s->rb);
     delete s;
 }
 
@@ -755,5 +784,284 @@ extern "C" int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_fr
     out->kept = (const int*)(hB + ((const char*)r.b_kept - q->d_b));
     out->new_xy = (const float*)(hB + ((const char*)r.b_new_xy - q->d_b));
     out->un_xy = (const float*)(hB + ((const char*)r.b_un_xy - q->d_b));
+    return VG_OK;
+}
+
+// ================================================================================================ one call per frame, every stream
+static int rb_build(vg_handle* h, FeState* s, RbState* q) {
+    const size_t cap = (size_t)s->max_pts, S = (size_t)s->cams;
+    RbDev& b = q->b;
+    memset(&b, 0, sizeof(b));
+    b.S = (int)S; b.cap = (int)cap;
+    // input block: npts | control ints | cameras | cur_pts
+    q->o_ctl = ri_up(sizeof(int) * S, 256);
+    q->o_cam = q->o_ctl + ri_up(sizeof(int) * RI_CTL_INTS * S, 256);
+    q->o_xy = q->o_cam + ri_up(sizeof(RiCam) * S, 256);
+    q->in_bytes = q->o_xy + ri_up(sizeof(float) * 2 * cap * S, 256);
+    b.a_st = 64; b.a_sf = b.a_st + ri_up(cap, 16); b.a_fw = b.a_sf + ri_up(cap, 16);
+    b.a_stride = ri_up(b.a_fw + sizeof(float) * 2 * cap, 256);
+    q->a_bytes = b.a_stride * S;
+    q->un_bytes = ri_up(sizeof(float) * 2 * cap * S, 256);
+    b.b_k = 64; b.b_nw = b.b_k + sizeof(int) * cap; b.b_un = b.b_nw + sizeof(float) * 2 * cap;
+    b.b_stride = ri_up(b.b_un + sizeof(float) * 2 * cap, 256);
+    q->b_bytes = b.b_stride * S;
+    q->ord_flags_bytes = ri_up(sizeof(int) * S, 256);
+    q->ord_bytes = q->ord_flags_bytes + ri_up(sizeof(int) * cap * S, 256);
+    const size_t mirrored = q->in_bytes + q->a_bytes + q->un_bytes + q->b_bytes + q->ord_bytes;
+    // device only: idx1 | idx2 | p1 | p2 | kept_xy | nk | RANSAC scratch (models, counts, inlier words: about 0.4 MB per stream)
+    b.words_n = (int)((std::min<size_t>(cap, FE_RANSAC_MAXPTS) + 63) / 64);
+    const size_t o_idx1 = mirrored, o_idx2 = o_idx1 + ri_up(sizeof(int) * cap * S, 256), o_p1 = o_idx2 + ri_up(sizeof(int) * cap * S, 256);
+    const size_t o_p2 = o_p1 + ri_up(sizeof(float) * 2 * cap * S, 256), o_kxy = o_p2 + ri_up(sizeof(float) * 2 * cap * S, 256);
+    const size_t o_nk = o_kxy + ri_up(sizeof(int) * 2 * cap * S, 256), o_mod = o_nk + ri_up(sizeof(int) * S, 256);
+    const size_t o_cnt = o_mod + sizeof(double) * 27 * FE_RANSAC_MAXIT * S, o_w = o_cnt + ri_up(sizeof(int) * FE_RANSAC_MAXIT * S, 256);
+    const size_t total = o_w + sizeof(unsigned long long) * (size_t)b.words_n * FE_RANSAC_MAXIT * S;
+    HIPCHK(h, hipMalloc((void**)&q->dev, total));
+    HIPCHK(h, hipMemset(q->dev, 0, total));
+    HIPCHK(h, hipHostMalloc((void**)&q->host, mirrored, 0));
+    memset(q->host, 0, mirrored);
+    q->d_in = q->dev; q->d_a = q->d_in + q->in_bytes; q->d_b = q->d_a + q->a_bytes + q->un_bytes; q->d_ord = q->d_b + q->b_bytes;
+    b.npts = (const int*)q->d_in; b.ctl = (int*)(q->d_in + q->o_ctl); b.cam = (const RiCam*)(q->d_in + q->o_cam);
+    b.xy_in = (const float*)(q->d_in + q->o_xy);
+    b.a = q->d_a; b.a_un = (float*)(q->d_a + q->a_bytes); b.b = q->d_b;
+    b.ord_flag = (const int*)q->d_ord; b.order = (const int*)(q->d_ord + q->ord_flags_bytes);
+    b.idx1 = (int*)(q->dev + o_idx1); b.idx2 = (int*)(q->dev + o_idx2); b.p1 = (float*)(q->dev + o_p1); b.p2 = (float*)(q->dev + o_p2);
+    b.kept_xy = (int*)(q->dev + o_kxy); b.nk = (int*)(q->dev + o_nk);
+    b.models = (double*)(q->dev + o_mod); b.count = (int*)(q->dev + o_cnt); b.words = (unsigned long long*)(q->dev + o_w);
+    const int nmax = (int)std::min<size_t>(cap, FE_RANSAC_MAXPTS);
+    std::vector<int> sched, tab;
+    b.tab_stride = nmax + 1;
+    fe_ransac_tables(nmax, sched, tab, b.tab_stride);
+    HIPCHK(h, hipMalloc((void**)&q->d_sched, sizeof(int) * std::max<size_t>(sched.size(), 1)));
+    HIPCHK(h, hipMalloc((void**)&q->d_tab, sizeof(int) * tab.size()));
+    if (!sched.empty()) HIPCHK(h, hipMemcpy(q->d_sched, sched.data(), sizeof(int) * sched.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(q->d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    b.niters_tab = q->d_tab;
+    q->base_src.assign(S, nullptr);
+    return VG_OK;
+}
+
+static int rb_ensure(vg_handle* h, FeState* s) {
+    if (s->rb) return VG_OK;
+    RbState* q = new RbState();
+    const int rc = rb_build(h, s, q);
+    if (rc != VG_OK) { rb_free(q); return rc; }
+    s->rb = q;
+    return VG_OK;
+}
+
+// the frames of all streams into the slot of the next build; rows may be padded differently per stream
+static int rb_upload_frames(vg_handle* h, FeState* s, const vg_fe_frame_in* in) {
+    std::vector<const uint8_t*> imgs((size_t)s->cams);
+    bool same = true;
+    for (int c = 0; c < s->cams; ++c) { imgs[c] = in[c].img; same = same && in[c].stride == in[0].stride; }
+    if (same) return fe_upload_async(h, imgs.data(), in[0].stride);
+    const size_t npix = (size_t)s->W * s->H;
+    s->raw_sel = s->flip ^ 1;                             // (as fe_upload_async)
+    s->d.raw = s->raw2[s->raw_sel];
+    s->prev_clobbered = s->have_prev && s->alias_on[s->flip ^ 1];
+    for (int c = 0; c < s->cams; ++c)
+        HIPCHK(h, hipMemcpy2DAsync(s->raw2[s->raw_sel] + (size_t)c * npix, s->W, imgs[c], in[c].stride, s->W, s->H, hipMemcpyHostToDevice, h->stream));
+    return VG_OK;
+}
+
+extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
+    VG_RANGE("vg_fe_read_image_batch");
+    if (!h || !h->fe || !in || !out || n_streams < 1) return VG_ERR_BAD_ARG;
+    FeState* s = h->fe;
+    if (n_streams != s->cams) { h->err = "vg_fe_read_image_batch: n_streams differs from n_cams of vg_fe_configure (the batched streams advance together)"; return VG_ERR_BAD_ARG; }
+    if (s->max_pts > 2048) { h->err = "vg_fe_read_image_batch: max_points > 2048"; return VG_ERR_UNSUPPORTED; }
+    // ---- everything that follows from the arguments alone is refused here: no frame has gone up, no stream has moved
+    const int S = s->cams;
+    int n_img = 0, n_pub = 0, first_pub = -1, nmax = 0;
+    bool any_ransac = false, any_base = false;
+    for (int c = 0; c < S; ++c) {
+        const vg_fe_frame_in& f = in[c];
+        if (f.struct_size != (int)sizeof(vg_fe_frame_in) || f.n < 0 || (f.n && !f.cur_xy)) { h->err = "vg_fe_read_image_batch: struct_size / n / cur_xy of a stream"; return VG_ERR_BAD_ARG; }
+        if (f.n > s->max_pts || f.max_cnt < 0 || f.max_cnt > s->max_pts) { h->err = "vg_fe_read_image_batch: n / max_cnt beyond max_points of vg_fe_configure"; return VG_ERR_BAD_ARG; }
+        if (f.publish && (f.min_dist < 0 || !(f.f_threshold > 0) || !(f.quality > 0))) { h->err = "vg_fe_read_image_batch: min_dist / f_threshold / quality"; return VG_ERR_BAD_ARG; }
+        if (f.n > 0 && !s->have_prev) { h->err = "vg_fe_read_image_batch: points to track but no previous frame"; return VG_ERR_BAD_ARG; }
+        if (f.img && f.stride < s->W) { h->err = "vg_fe_read_image_batch: stride smaller than the frame width"; return VG_ERR_BAD_ARG; }
+        if ((f.equalize != 0) != (in[0].equalize != 0)) { h->err = "vg_fe_read_image_batch: equalize differs between the streams (the image build takes one value)"; return VG_ERR_BAD_ARG; }
+        n_img += f.img ? 1 : 0;
+        nmax = std::max(nmax, f.n);
+        if (f.publish) {
+            if (first_pub < 0) first_pub = c;
+            else if (f.quality != in[first_pub].quality || f.min_dist != in[first_pub].min_dist) {
+                h->err = "vg_fe_read_image_batch: quality / min_dist differ between the streams that publish (the detection takes one value)";
+                return VG_ERR_BAD_ARG;
+            }
+            ++n_pub;
+            any_ransac = any_ransac || f.n >= 15;
+            any_base = any_base || f.base_mask;
+        }
+    }
+    if (n_img != 0 && n_img != S) { h->err = "vg_fe_read_image_batch: frames for some streams only (all, or none = the resident frames)"; return VG_ERR_BAD_ARG; }
+    const int equalize = in[0].equalize;
+    if (equalize && (s->d.W % 8 || s->d.H % 8)) { h->err = "CLAHE needs width and height divisible by 8"; return VG_ERR_UNSUPPORTED; }
+    if (equalize && s->d.W / 8 / 4 + 3 > 256) { h->err = "CLAHE: frame wider than the interpolation-cell tiling (W / 32 + 3 > 256)"; return VG_ERR_UNSUPPORTED; }
+    const int radius = n_pub ? in[first_pub].min_dist : 0;
+    const double quality = n_pub ? in[first_pub].quality : 0.01;
+    if (n_pub) {
+        const int cell = radius < 1 ? 1 : radius;
+        if (((s->d.W + cell - 1) / cell) * ((s->d.H + cell - 1) / cell) > FE_MAX_CELLS) { h->err = "min_dist too small for the cell grid"; return VG_ERR_UNSUPPORTED; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = rb_ensure(h, s);
+    if (rc) return rc;
+    RbState* q = s->rb;
+    const RbDev& b = q->b;
+    const size_t npix = (size_t)s->W * s->H, cap = (size_t)b.cap;
+    for (int c = 0; c < S; ++c) memset(&out[c], 0, sizeof(out[c]));
+    // the fisheye masks travel once per stream (the reference loads them at start-up)
+    if (any_base && !q->d_base) HIPCHK(h, hipMalloc((void**)&q->d_base, npix * S));
+    RbDev bd = b;
+    bd.base = q->d_base;
+    for (int c = 0; c < S; ++c)
+        if (in[c].publish && in[c].base_mask && in[c].base_mask != q->base_src[c]) {
+            HIPCHK(h, hipMemcpyAsync(q->d_base + (size_t)c * npix, in[c].base_mask, npix, hipMemcpyHostToDevice, h->stream));
+            q->base_src[c] = in[c].base_mask;
+        }
+    // ---- upload: the frames (unless they are resident), then ONE block with the point counts, control ints, cameras and cur_pts
+    if (n_img) {
+        rc = rb_upload_frames(h, s, in);
+        if (rc) return rc;
+    }
+    {
+        int* hn = (int*)q->host;
+        int* hctl = (int*)(q->host + q->o_ctl);
+        RiCam* hcam = (RiCam*)(q->host + q->o_cam);
+        float* hxy = (float*)(q->host + q->o_xy);
+        memset(hctl, 0, sizeof(int) * RI_CTL_INTS * S);
+        for (int c = 0; c < S; ++c) {
+            const vg_fe_frame_in& f = in[c];
+            hn[c] = f.n;
+            hctl[c * RI_CTL_INTS + RI_N] = f.n; hctl[c * RI_CTL_INTS + RI_PUBLISH] = f.publish ? 1 : 0; hctl[c * RI_CTL_INTS + RI_BEST] = -1;
+            RiCam& k = hcam[c];
+            k.focal = f.focal_length; k.half_w = s->W / 2.0; k.half_h = s->H / 2.0;
+            k.fx = f.intr[0]; k.fy = f.intr[1]; k.cx = f.intr[2]; k.cy = f.intr[3];
+            k.k1 = f.intr[4]; k.k2 = f.intr[5]; k.pp1 = f.intr[6]; k.pp2 = f.intr[7];
+            k.thresh2 = (float)(f.f_threshold * f.f_threshold);
+            k.max_cnt = f.max_cnt; k.radius = f.min_dist; k.has_base = (f.publish && f.base_mask) ? 1 : 0;
+            if (f.n) memcpy(hxy + (size_t)c * cap * 2, f.cur_xy, sizeof(float) * 2 * f.n);
+        }
+        // (cur_pts of the last stream end where its points end)
+        const size_t bytes = q->o_xy + sizeof(float) * 2 * (cap * (S - 1) + in[S - 1].n);
+        HIPCHK(h, hipMemcpyAsync(q->d_in, q->host, bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    rc = vg_fe_build_async(h, equalize);
+    if (rc) return rc;
+    FeDev d = s->d;
+    d.npts = b.npts; d.prev_xy = b.xy_in; d.skip_idle = 1;
+    if (nmax > 0) hipLaunchKernelGGL(fe_lk_kernel, dim3(nmax, S), dim3(64), 0, h->stream, d);
+    hipLaunchKernelGGL(fe_rb_after_lk_kernel, dim3(S), dim3(256), 0, h->stream, d, bd);
+    // ---- rejectWithF (:169-202) of every stream that publishes; the kernels leave at once for a stream with fewer than 15 survivors
+    if (any_ransac) {
+        hipLaunchKernelGGL(fe_rb_ransac7_kernel, dim3((RB_CHUNK0 + 6) / 7, S), dim3(64), 0, h->stream, bd, (const int*)q->d_sched, 0);
+        hipLaunchKernelGGL(fe_rb_count_kernel, dim3(RB_CHUNK0, S), dim3(64), 0, h->stream, bd, 0);
+        hipLaunchKernelGGL(fe_rb_pick_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, 0);
+        hipLaunchKernelGGL(fe_rb_ransac7_kernel, dim3(8, S), dim3(64), 0, h->stream, bd, (const int*)q->d_sched, 1);
+        hipLaunchKernelGGL(fe_rb_count_kernel, dim3(56, S), dim3(64), 0, h->stream, bd, 1);
+        hipLaunchKernelGGL(fe_rb_pick_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, 1);
+    }
+    HIPCHK(h, hipGetLastError());
+    char* hA = q->host + q->in_bytes;
+    char* hUn = hA + q->a_bytes;
+    char* hB = hUn + q->un_bytes;
+    char* hOrd = hB + q->b_bytes;
+    // ONE download: block A of every stream, and the lifted survivors when a stream ends its frame here
+    HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes + (n_pub < S ? q->un_bytes : 0), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int max_n2 = 0;
+    for (int c = 0; c < S; ++c) {
+        vg_fe_frame_out& o = out[c];
+        char* a = hA + (size_t)c * b.a_stride;
+        const int* ahdr = (const int*)a;
+        o.status_lk = (const uint8_t*)(a + b.a_st); o.status_f = (const uint8_t*)(a + b.a_sf); o.forw_xy = (const float*)(a + b.a_fw);
+        if (!in[c].publish) {
+            o.n1 = o.n2 = o.n_final = ahdr[RI_N1];
+            o.un_xy = (const float*)hUn + (size_t)c * cap * 2;
+            o.ransac_best = -1;
+            if (o.n1 < 0 || o.n1 > in[c].n) { h->err = "vg_fe_read_image_batch: inconsistent counts from the device"; return VG_ERR_NUMERIC; }
+            continue;
+        }
+        o.n1 = ahdr[RI_N1]; o.n2 = ahdr[RI_N2]; o.ransac_ran = ahdr[RI_RANSAC]; o.fallback = ahdr[RI_FALLBACK];
+        o.ransac_best = ahdr[RI_BEST]; o.ransac_niters = ahdr[RI_NITERS];
+        if (o.n1 < 0 || o.n1 > in[c].n || o.n2 < 0 || o.n2 > o.n1) { h->err = "vg_fe_read_image_batch: inconsistent counts from the device"; return VG_ERR_NUMERIC; }
+    }
+    if (n_pub == 0) return VG_OK;
+    // ---- the streams whose estimate the device could not finish (LMedS range, a sample OpenCV would have redrawn): as in the single call
+    for (int c = 0; c < S; ++c) {
+        vg_fe_frame_out& o = out[c];
+        if (!in[c].publish || !o.fallback) continue;
+        const int n1 = o.n1;
+        std::vector<float> pp((size_t)4 * n1);
+        HIPCHK(h, hipMemcpyAsync(pp.data(), b.p1 + (size_t)c * cap * 2, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pp.data() + 2 * n1, b.p2 + (size_t)c * cap * 2, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        uint8_t* sf = const_cast<uint8_t*>(o.status_f);
+        rc = vg_fe_reject_with_f(h, pp.data(), pp.data() + 2 * n1, n1, in[c].f_threshold, sf, nullptr, nullptr);
+        if (rc) return rc;
+        std::vector<int> idx2;
+        for (int i = 0, k = 0; i < in[c].n; ++i)
+            if (o.status_lk[i]) { if (sf[k]) idx2.push_back(i); ++k; }
+        o.n2 = (int)idx2.size();
+        if (o.n2) HIPCHK(h, hipMemcpy(b.idx2 + (size_t)c * cap, idx2.data(), sizeof(int) * idx2.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(b.ctl + (size_t)c * RI_CTL_INTS + RI_N2, &o.n2, sizeof(int), hipMemcpyHostToDevice));
+        o.ransac_best = -1; o.ransac_niters = 0;
+    }
+    // ---- setMask (:36-69): the callbacks in ascending stream order on this thread, then ONE upload of all orders
+    int* hflag = (int*)hOrd;
+    int* horder = (int*)(hOrd + q->ord_flags_bytes);
+    bool any_order = false;
+    for (int c = 0; c < S; ++c) {
+        hflag[c] = 0;
+        if (!in[c].publish) continue;
+        const int n2 = out[c].n2;
+        max_n2 = std::max(max_n2, n2);
+        if (!in[c].order || n2 <= 0) continue;
+        int* ord = horder + (size_t)c * cap;
+        for (int k = 0; k < n2; ++k) ord[k] = -1;
+        if (in[c].order(in[c].user, &out[c], ord) != 0) { h->err = "vg_fe_read_image_batch: the order callback of a stream failed"; return VG_ERR_BAD_ARG; }
+        std::vector<char> seen((size_t)n2, 0);
+        for (int k = 0; k < n2; ++k) {
+            if (ord[k] < 0 || ord[k] >= n2 || seen[ord[k]]) { h->err = "vg_fe_read_image_batch: an order callback did not return a permutation"; return VG_ERR_BAD_ARG; }
+            seen[ord[k]] = 1;
+        }
+        hflag[c] = 1;
+        any_order = true;
+    }
+    HIPCHK(h, hipMemcpyAsync(q->d_ord, hOrd, any_order ? q->ord_bytes : sizeof(int) * S, hipMemcpyHostToDevice, h->stream));
+    // the masks of the streams that publish: the fisheye mask or 255 (runs of streams without one: one fill)
+    for (int c = 0; c < S;) {
+        if (!in[c].publish) { ++c; continue; }
+        if (in[c].base_mask) {
+            HIPCHK(h, hipMemcpyAsync(s->mask + (size_t)c * npix, q->d_base + (size_t)c * npix, npix, hipMemcpyDeviceToDevice, h->stream));
+            ++c;
+            continue;
+        }
+        int e = c;
+        while (e < S && in[e].publish && !in[e].base_mask) ++e;
+        HIPCHK(h, hipMemsetAsync(s->mask + (size_t)c * npix, 255, npix * (e - c), h->stream));
+        c = e;
+    }
+    hipLaunchKernelGGL(fe_rb_setmask_kernel, dim3(S), dim3(64), 0, h->stream, d, bd);
+    if (max_n2 > 0) hipLaunchKernelGGL(fe_stamp_kernel, dim3(max_n2, S), dim3(256), 0, h->stream, d, (const int*)b.nk, (const int*)b.kept_xy, radius);
+    // ---- goodFeaturesToTrack (:144-149) of the streams that publish (the others leave the kernels at once) + addPoints + undistortedPoints
+    HIPCHK(h, hipMemsetAsync(s->ncand, 0, sizeof(unsigned) * FE_CNT_STRIDE * S, h->stream));
+    hipLaunchKernelGGL(fe_mineig_kernel, dim3((d.W + 63) / 64, (d.H + 15) / 16, S), dim3(256), 0, h->stream, d, quality);
+    HIPCHK(h, fe_launch_select(d, quality, (float)(double)radius, h->stream));
+    hipLaunchKernelGGL(fe_rb_finish_kernel, dim3(S), dim3(256), 0, h->stream, d, bd);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hB, q->d_b, q->b_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int c = 0; c < S; ++c) {
+        if (!in[c].publish) continue;
+        vg_fe_frame_out& o = out[c];
+        char* q2 = hB + (size_t)c * b.b_stride;
+        const int* bhdr = (const int*)q2;
+        if (bhdr[RI_NNEW] < 0) { h->err = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)"; return VG_ERR_UNSUPPORTED; }
+        o.n_kept = bhdr[RI_NK]; o.n_new = bhdr[RI_NNEW]; o.n_final = o.n_kept + o.n_new;
+        o.kept = (const int*)(q2 + b.b_k); o.new_xy = (const float*)(q2 + b.b_nw); o.un_xy = (const float*)(q2 + b.b_un);
+    }
     return VG_OK;
 }

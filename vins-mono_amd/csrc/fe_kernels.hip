@@ -772,6 +772,7 @@ extern "C" __global__ __launch_bounds__(256) void fe_mineig_kernel(FeDev d, doub
     __shared__ float bmax[4];
     __shared__ unsigned wcount[4], wbase[4], lbound;
     const int cam = blockIdx.z, W = d.W, H = d.H;
+    if (d.skip_idle && d.max_corners[cam] < 0) return;            // (vg_fe_read_image_batch: the stream does not publish this frame)
     const int x0 = blockIdx.x * 64, y0 = blockIdx.y * ME_R;
     const glb_u8* img = (const glb_u8*)d.cur_planes[cam];          // level 0
     const glb_u8* gmask = (const glb_u8*)(d.mask + (size_t)cam * W * H);
@@ -1071,6 +1072,10 @@ extern "C" __global__ __launch_bounds__(1024) void fe_select_kernel(FeDev d, dou
     SelWalk w;
     w.cellxy = cellxy; w.cellcnt = cellcnt; w.W = d.W; w.H = d.H;
     w.maxc = d.max_corners[cam];
+    if (d.skip_idle && w.maxc < 0) {                              // (vg_fe_read_image_batch: the stream does not publish this frame)
+        if (tid == 0) d.ncorners[cam] = 0;
+        return;
+    }
     w.cell = __float2int_rn(min_dist) < 1 ? 1 : __float2int_rn(min_dist);
     w.gw = (d.W + w.cell - 1) / w.cell; w.gh = (d.H + w.cell - 1) / w.cell;
     w.md2 = (double)min_dist * (double)min_dist;

@@ -31,6 +31,8 @@ struct FeDev {
     const int* max_corners;         // [cams]
     float* corners;                 // [cams][max_pts][2]
     int* ncorners;                  // [cams]
+    int skip_idle;                  // vg_fe_read_image_batch: a stream whose max_corners is negative (it does not publish) leaves the
+                                    // detection kernels at once with 0 corners; 0 everywhere else
 };
 
 #define FE_RANSAC_MAXIT 1000        // maxIters of cv::findFundamentalMat's RANSAC
@@ -47,6 +49,7 @@ enum {
     RI_NK,             // points setMask kept
     RI_NNEW,           // corners detected (-1: candidate list overflow)
     RI_NITERS,         // iterations that counted
+    RI_MAXGOOD,        // (batched call) inliers of the best model so far, carried between the two parts of the bookkeeping
     RI_CTL_INTS = 16
 };
 #define RI_FB_COLLINEAR 1           // a sample of the point-independent schedule would have been redrawn by OpenCV
@@ -81,6 +84,41 @@ struct RiDev {
     int max_cnt, radius;
     int* kept_xy;                   // [cap][2] rounded positions of the kept points (fe_stamp_kernel)
     const uint8_t* base_mask;       // fisheye mask or nullptr
+};
+// ---- vg_fe_read_image_batch: the same frame for every stream of the handle.  What the single call passes by value in RiDev comes from
+// device tables indexed by stream; a kernel of the batch rebuilds the stream's RiDev from them (scalar loads) and runs the single
+// call's body on it.
+#define RB_CHUNK0 63                // RANSAC iterations every stream evaluates before the bookkeeping first looks (9 wavefronts of 7 samples)
+struct RiCam {                      // per stream, uploaded with the points
+    double focal, half_w, half_h;
+    double fx, fy, cx, cy, k1, k2, pp1, pp2;
+    float thresh2;                  // (float)(F_THRESHOLD^2)
+    int max_cnt, radius, has_base;
+};
+struct RbDev {
+    int S, cap;
+    const int* npts;                // [S] points handed in (what fe_lk_kernel reads)
+    int* ctl;                       // [S][RI_CTL_INTS]
+    const RiCam* cam;               // [S]
+    const float* xy_in;             // [S][cap][2]
+    int *idx1, *idx2;               // [S][cap]
+    float *p1, *p2;                 // [S][cap][2]
+    const int* ord_flag;            // [S] 1: the stream has a walk order
+    const int* order;               // [S][cap]
+    char* a;                        // [S][a_stride]: hdr | status_lk | status_f | forw_xy
+    size_t a_stride, a_st, a_sf, a_fw;
+    float* a_un;                    // [S][cap][2]
+    char* b;                        // [S][b_stride]: hdr | kept | new_xy | un_xy
+    size_t b_stride, b_k, b_nw, b_un;
+    const int* niters_tab;
+    int tab_stride;
+    int* count;                     // [S][FE_RANSAC_MAXIT]
+    unsigned long long* words;      // [S][FE_RANSAC_MAXIT][words_n]
+    int words_n;
+    double* models;                 // [S][FE_RANSAC_MAXIT][3][9]
+    int* kept_xy;                   // [S][cap][2]
+    int* nk;                        // [S] kept points (what fe_stamp_kernel reads); 0 for a stream that does not publish
+    const uint8_t* base;            // [S][H][W] fisheye masks (streams with has_base) or nullptr
 };
 // device scratch of the fundamental-matrix estimate (fe_ransac.hip), one allocation per handle
 struct FeRansacBufs {

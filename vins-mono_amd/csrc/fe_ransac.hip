@@ -128,130 +128,9 @@ extern "C" __global__ __launch_bounds__(64) void fe_ransac7_kernel(const float* 
         if (n < 15 || n > FE_RANSAC_MAXPTS || ctl[RI_PUBLISH] == 0) return;
         sched += (size_t)(n - 15) * 7 * FE_RANSAC_MAXIT;
     }
-    const int lane = threadIdx.x, g = lane / FR_GROUP, c = lane - FR_GROUP * g;
-    const int k = blockIdx.x * FR_PER_WAVE + g;
-    const bool live = g < FR_PER_WAVE && k < nsched;
-    const int gb = g < FR_PER_WAVE ? FR_GROUP * g : 64 - FR_GROUP;      // first lane of the group (lane 63: any valid lanes; its results are dropped)
-    int idx[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) idx[i] = live ? sched[(size_t)k * 7 + i] : i;
-    if (ctl && live && c == 0 && (fr_last_collinear(p1, idx) || fr_last_collinear(p2, idx))) atomicOr(&ctl[RI_FALLBACK], RI_FB_COLLINEAR);
-    // column c of the design matrix (row i = [x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1]) and of the identity
-    double a[7], v[9];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        const double x0 = p1[2 * idx[i]], y0 = p1[2 * idx[i] + 1], x1 = p2[2 * idx[i]], y1 = p2[2 * idx[i] + 1];
-        const double u = c < 3 ? x1 : (c < 6 ? y1 : 1.0);
-        const int cm = c - 3 * (c / 3);
-        const double w = cm == 0 ? x0 : (cm == 1 ? y0 : 1.0);
-        a[i] = u * w;
-    }
-#pragma unroll
-    for (int e = 0; e < 9; ++e) v[e] = (e == c) ? 1.0 : 0.0;
-    // one-sided Jacobi on the 9 columns: A V = U Sigma; the two columns that end with the smallest norms span the null space.
-    // A has rank 7: two columns shrink to rounding noise, and a pair with such a column never passes the orthogonality test (noise
-    // against noise) -- it is still rotated when its turn comes, but only rotations between two columns that carry signal (norm^2
-    // above 1e-26 |A|_F^2) keep the sweeps going: ~7 sweeps instead of all 40.
-    double scale2 = 0.0;
-    {
-        double nn = 0.0;
-#pragma unroll
-        for (int r = 0; r < 7; ++r) nn += a[r] * a[r];
-#pragma unroll
-        for (int q = 0; q < FR_GROUP; ++q) scale2 += __shfl(nn, gb + q);
-    }
-    const double signal = 1e-26 * scale2;
-    const unsigned long long gmask = 0x1ffull << gb;
-    bool active = live;                                    // (uniform over the group; lane 63 and the samples past the schedule rest)
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        bool rotated = false;
-#pragma unroll 1
-        for (int rd = 0; rd < FR_GROUP; ++rd) {
-            int p = rd - c;
-            p = p < 0 ? p + FR_GROUP : p;
-            const bool lo = c < p;
-            double b[7], w[9];
-#pragma unroll
-            for (int r = 0; r < 7; ++r) b[r] = __shfl(a[r], gb + p);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) w[e] = __shfl(v[e], gb + p);
-            // (al, be, ga) of the pair as the column with the smaller index sees them: both lanes form the same sums
-            double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-            for (int r = 0; r < 7; ++r) {
-                const double x = lo ? a[r] : b[r], y = lo ? b[r] : a[r];
-                al += x * x; be += y * y; ga += x * y;
-            }
-            if (active && p != c && fabs(ga) > 1e-15 * sqrt(al * be) && ga != 0.0) {
-                rotated = rotated || (al > signal && be > signal);
-                const double zeta = (be - al) / (2.0 * ga);
-                const double tn = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / sqrt(1.0 + tn * tn), sn = cs * tn;
-                // column lo: cs x - sn y; column hi: sn x + cs y  (x = the lo column, y = the hi column)
-#pragma unroll
-                for (int r = 0; r < 7; ++r) a[r] = lo ? cs * a[r] - sn * b[r] : sn * b[r] + cs * a[r];
-#pragma unroll
-                for (int e = 0; e < 9; ++e) v[e] = lo ? cs * v[e] - sn * w[e] : sn * w[e] + cs * v[e];
-            }
-        }
-        active = active && (__ballot(rotated) & gmask) != 0ull;
-        if (!__any(active)) break;
-    }
-    int i2 = 0, i1 = -1;                                  // i2: smallest column norm, i1: second smallest
-    {
-        double nn = 0.0;
-#pragma unroll
-        for (int r = 0; r < 7; ++r) nn += a[r] * a[r];
-        double nrm[9];
-#pragma unroll
-        for (int q = 0; q < FR_GROUP; ++q) nrm[q] = __shfl(nn, gb + q);
-        double n2 = 0.0, n1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 9; ++q)
-            if (q == 0 || nrm[q] < n2) { n2 = nrm[q]; i2 = q; }
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            if (q == i2) continue;
-            if (i1 < 0 || nrm[q] < n1) { n1 = nrm[q]; i1 = q; }
-        }
-    }
-    // the two null vectors = columns i2 and i1 of V, fetched from the lanes that own them; from here on every lane of the group computes
-    // the same numbers and lane 0 of the group stores them
-    double f1[9], f2[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) {
-        const double v2 = __shfl(v[e], gb + i2), v1 = __shfl(v[e], gb + i1);
-        f2[e] = v2; f1[e] = v1 - v2;
-    }
-    double cf[4];
-    {
-        double t0 = f2[4] * f2[8] - f2[5] * f2[7], t1 = f2[3] * f2[8] - f2[5] * f2[6], t2 = f2[3] * f2[7] - f2[4] * f2[6];
-        cf[3] = f2[0] * t0 - f2[1] * t1 + f2[2] * t2;
-        cf[2] = f1[0] * t0 - f1[1] * t1 + f1[2] * t2 - f1[3] * (f2[1] * f2[8] - f2[2] * f2[7]) + f1[4] * (f2[0] * f2[8] - f2[2] * f2[6]) -
-                f1[5] * (f2[0] * f2[7] - f2[1] * f2[6]) + f1[6] * (f2[1] * f2[5] - f2[2] * f2[4]) - f1[7] * (f2[0] * f2[5] - f2[2] * f2[3]) +
-                f1[8] * (f2[0] * f2[4] - f2[1] * f2[3]);
-        t0 = f1[4] * f1[8] - f1[5] * f1[7]; t1 = f1[3] * f1[8] - f1[5] * f1[6]; t2 = f1[3] * f1[7] - f1[4] * f1[6];
-        cf[0] = f1[0] * t0 - f1[1] * t1 + f1[2] * t2;
-        cf[1] = f2[0] * t0 - f2[1] * t1 + f2[2] * t2 - f2[3] * (f1[1] * f1[8] - f1[2] * f1[7]) + f2[4] * (f1[0] * f1[8] - f1[2] * f1[6]) -
-                f2[5] * (f1[0] * f1[7] - f1[1] * f1[6]) + f2[6] * (f1[1] * f1[5] - f1[2] * f1[4]) - f2[7] * (f1[0] * f1[5] - f1[2] * f1[3]) +
-                f2[8] * (f1[0] * f1[4] - f1[1] * f1[3]);
-    }
-    double roots[3] = {0, 0, 0};
-    const int nr = fr_solve_cubic(cf, roots);
-    // the up-to-three models of the sample, in the order of the roots; a model that is not finite is marked by F[0] = NaN
-    for (int m = 0; m < 3; ++m) {
-        double F[9];
-        bool ok = (nr >= 1 && nr <= 3) && m < nr;
-        if (ok) {
-            double lambda = roots[m], mu = 1.0;
-            const double sc = f1[8] * roots[m] + f2[8];
-            if (fabs(sc) > 2.220446049250313e-16) { mu = 1.0 / sc; lambda *= mu; F[8] = 1.0; } else F[8] = 0.0;
-            for (int e = 0; e < 8; ++e) F[e] = f1[e] * lambda + f2[e] * mu;
-            for (int e = 0; e < 9; ++e) ok = ok && (F[e] == F[e]) && fabs(F[e]) < 1e300;
-        }
-        if (live && c == 0)
-            for (int e = 0; e < 9; ++e) models[((size_t)k * 3 + m) * 9 + e] = ok ? F[e] : __builtin_nan("");
-    }
+#define FR_FIRST_SAMPLE (blockIdx.x * FR_PER_WAVE)
+#include "fe_ransac7_body.h"
+#undef FR_FIRST_SAMPLE
 }
 
 // Second half of an iteration, one WAVEFRONT per sample (round 4: the thread that solved the sample used to walk all n points for each
@@ -269,62 +148,75 @@ extern "C" __global__ __launch_bounds__(64) void fe_ransac_count_kernel(const fl
         if (n < 15 || n > FE_RANSAC_MAXPTS || ctl[RI_PUBLISH] == 0) return;
     }
     if (k >= nsched) return;
-    const int nw = (n + 63) >> 6;
-    double bestF[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int bgood = -1;
-    double bmed = 0.0;
-    bool have = false;
-    for (int m = 0; m < 3; ++m) {
-        double F[9];
-        for (int e = 0; e < 9; ++e) F[e] = models[((size_t)k * 3 + m) * 9 + e];
-        if (!(F[0] == F[0])) continue;                      // (uniform: no such model)
-        if (!lmeds) {
-            int good = 0;
-            for (int w = 0; w < nw; ++w) {
-                const int i = 64 * w + lane;
-                const bool in = i < n && fr_error(F, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]) <= thresh2;
-                good += __popcll(__ballot(in));
-            }
-            if (!have || good > bgood || (good == bgood && fr_model_before(F, bestF))) {
-                bgood = good; have = true;
-                for (int e = 0; e < 9; ++e) bestF[e] = F[e];
-            }
-        } else {
-            float er[FE_LMEDS_MAXPTS];
-            for (int i = 0; i < FE_LMEDS_MAXPTS; ++i) er[i] = i < n ? fr_error(F, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]) : 3.0e38f;
-            bool nan = false;
-            for (int i = 0; i < FE_LMEDS_MAXPTS; ++i) nan = nan || (i < n && !(er[i] == er[i]));
-            // selection by rank (no dynamically indexed sort of a register array): median = element(s) of rank n/2 (and n/2 - 1)
-            float lo = 0.f, hi = 0.f;
-            for (int i = 0; i < FE_LMEDS_MAXPTS; ++i) {
-                if (i >= n) continue;
-                int rk = 0;
-                for (int j = 0; j < FE_LMEDS_MAXPTS; ++j) rk += (j < n && (er[j] < er[i] || (er[j] == er[i] && j < i))) ? 1 : 0;
-                if (rk == n / 2) hi = er[i];
-                if (rk == n / 2 - 1) lo = er[i];
-            }
-            double med = (n & 1) ? (double)hi : (double)(lo + hi) * 0.5;
-            if (nan) continue;
-            // (n <= 13: the median of a model that fits its 7 sample points exactly lies inside the fitted set and is rounding noise;
-            //  snapped to zero so that the FIRST such sample wins instead of noise: oracle/ASSUMPTIONS.md F9)
-            if (med < 1e-12) med = 0.0;
-            if (!have || med < bmed || (med == bmed && fr_model_before(F, bestF))) {
-                bmed = med; have = true; bgood = 0;
-                for (int e = 0; e < 9; ++e) bestF[e] = F[e];
-            }
+#include "fe_ransac_count_body.h"
+}
+
+// ---- vg_fe_read_image_batch: the two kernels above with a stream dimension (blockIdx.y) and per-stream scratch, RANSAC only (a stream in
+// the LMedS range goes back to the host as in the single call).  The registrator's loop never looks at an iteration at or beyond its
+// bound, and the bound only shrinks; at 256 streams the 1000 iterations of the single call would be 256K wavefronts of which the
+// bookkeeping reads a few dozen per stream.  So the iterations run in two parts with the bookkeeping (fe_rb_pick_kernel) between them:
+//   part 0   iterations [0, RB_CHUNK0) of every stream, and the collinearity test of ALL 1000 samples of its schedule (the fall-back
+//            flag of the single call does not depend on where the loop ends; neither does this one);
+//   part 1   iterations [RB_CHUNK0, bound after part 0) -- nothing for most streams; a wavefront takes several iterations in turn.
+// Every iteration below the final bound has been evaluated when the bookkeeping reaches it: the outputs are those of the single call.
+DEV bool rb_ransac_stream(const RbDev& b, const int c, int& n) {
+    const int* ctl = b.ctl + (size_t)c * RI_CTL_INTS;
+    n = ctl[RI_N1];
+    return !(n < 15 || n > FE_RANSAC_MAXPTS || ctl[RI_PUBLISH] == 0);
+}
+extern "C" __global__ __launch_bounds__(64) void fe_rb_ransac7_kernel(RbDev b, const int* __restrict__ sched, int part) {
+    const int cam = blockIdx.y;
+    int n;
+    if (!rb_ransac_stream(b, cam, n)) return;
+    int* const sctl = b.ctl + (size_t)cam * RI_CTL_INTS;
+    sched += (size_t)(n - 15) * 7 * FE_RANSAC_MAXIT;
+    const float* __restrict__ p1 = b.p1 + (size_t)cam * b.cap * 2;
+    const float* __restrict__ p2 = b.p2 + (size_t)cam * b.cap * 2;
+    double* __restrict__ models = b.models + (size_t)cam * FE_RANSAC_MAXIT * 27;
+    int first = blockIdx.x * FR_PER_WAVE, nsched = RB_CHUNK0;
+    if (part == 0) {
+        for (int q = blockIdx.x * 64 + threadIdx.x; q < FE_RANSAC_MAXIT; q += gridDim.x * 64) {
+            int idx[7];
+#pragma unroll
+            for (int i = 0; i < 7; ++i) idx[i] = sched[(size_t)q * 7 + i];
+            if (fr_last_collinear(p1, idx) || fr_last_collinear(p2, idx)) atomicOr(&sctl[RI_FALLBACK], RI_FB_COLLINEAR);
         }
+    } else {
+        const int bound = sctl[RI_NITERS];
+        nsched = bound < FE_RANSAC_MAXIT ? bound : FE_RANSAC_MAXIT;
+        first += RB_CHUNK0;
     }
-    if (have && !lmeds)
-        for (int w = 0; w < nw; ++w) {
-            const int i = 64 * w + lane;
-            const bool in = i < n && fr_error(bestF, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]) <= thresh2;
-            const unsigned long long bal = __ballot(in);
-            if (lane == 0) inl_words[(size_t)k * nw + w] = bal;
-        }
-    if (lane == 0) {
-        for (int e = 0; e < 9; ++e) Fout[(size_t)k * 9 + e] = bestF[e];
-        count[k] = have ? bgood : -1;
-        median[k] = bmed;
+    int* const ctl = nullptr;                              // (the collinearity test above covers the whole schedule)
+#pragma unroll 1
+    for (int k0 = first; k0 < nsched; k0 += gridDim.x * FR_PER_WAVE) {
+#define FR_FIRST_SAMPLE k0
+#include "fe_ransac7_body.h"
+#undef FR_FIRST_SAMPLE
+    }
+}
+extern "C" __global__ __launch_bounds__(64) void fe_rb_count_kernel(RbDev b, int part) {
+    const int cam = blockIdx.y, lane = threadIdx.x;
+    int n;
+    if (!rb_ransac_stream(b, cam, n)) return;
+    const float* __restrict__ p1 = b.p1 + (size_t)cam * b.cap * 2;
+    const float* __restrict__ p2 = b.p2 + (size_t)cam * b.cap * 2;
+    const double* __restrict__ models = b.models + (size_t)cam * FE_RANSAC_MAXIT * 27;
+    int* __restrict__ count = b.count + (size_t)cam * FE_RANSAC_MAXIT;
+    unsigned long long* __restrict__ inl_words = b.words + (size_t)cam * FE_RANSAC_MAXIT * b.words_n;
+    const float thresh2 = b.cam[cam].thresh2;
+    const int lmeds = 0;
+    int k0 = blockIdx.x, end = RB_CHUNK0;
+    if (part != 0) {
+        const int bound = b.ctl[(size_t)cam * RI_CTL_INTS + RI_NITERS];
+        end = bound < FE_RANSAC_MAXIT ? bound : FE_RANSAC_MAXIT;
+        k0 += RB_CHUNK0;
+    }
+#pragma unroll 1
+    for (; k0 < end; k0 += gridDim.x) {
+        const int k = k0;
+#define FR_COUNT_ONLY
+#include "fe_ransac_count_body.h"
+#undef FR_COUNT_ONLY
     }
 }
 

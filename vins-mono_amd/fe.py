@@ -55,6 +55,8 @@ class FrontEnd:
         L.vg_fe_undistort.argtypes = [C.c_void_p, _f4, C.c_int, C.POINTER(C.c_double), _f4]
         L.vg_fe_reject_with_f.argtypes = [C.c_void_p, _f4, _f4, C.c_int, C.c_double, _u8, _i4, C.POINTER(C.c_double)]
         L.vg_fe_read_image.argtypes = [C.c_void_p, C.POINTER(FrameIn), C.POINTER(FrameOut)]
+        if hasattr(L, "vg_fe_read_image_batch"):          # (a library built before the batched call: read_image_batch() raises AttributeError)
+            L.vg_fe_read_image_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameIn), C.POINTER(FrameOut)]
         self.hd._chk(L.vg_fe_configure(self.h, width, height, n_cams, max_points), "vg_fe_configure")
 
     def _imgs(self, frames):
@@ -222,6 +224,86 @@ class FrontEnd:
         out["new_xy"] = arr(fo.new_xy, (fo.n_new, 2)) if publish else None
         out["un_xy"] = arr(fo.un_xy, (fo.n_final, 2))
         return out
+
+    def read_image_batch(self, imgs, cur_pts_list, publish_list, intr_list, max_cnt=150, min_dist=30, equalize=False, f_threshold=1.0,
+                         focal_length=460.0, quality=0.01, base_masks=None, orders=None, n_streams=None):
+        """vg_fe_read_image_batch: FeatureTracker::readImage of every stream of the handle in one call.  imgs: one frame per stream, or None
+        for the frames the last upload_frames() left on the device (a list may hold None entries: the library refuses a mixture).
+        cur_pts_list / publish_list / intr_list: one entry per stream.  max_cnt, min_dist, equalize, f_threshold, focal_length, quality: one
+        value for all streams or a list (the library wants equalize uniform, and quality / min_dist uniform over the publishing streams).
+        base_masks / orders: None or lists with None entries; orders[c] as `order` of read_image().  n_streams: what is passed to the
+        library (default: the number of list entries).  Returns the list of the dictionaries read_image() returns."""
+        S = len(cur_pts_list) if n_streams is None else int(n_streams)
+        m = len(cur_pts_list)
+
+        def per(v):
+            return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * m
+
+        max_cnt, min_dist, equalize, f_threshold, focal_length, quality = [per(v) for v in (max_cnt, min_dist, equalize, f_threshold, focal_length, quality)]
+        frames = [None] * m if imgs is None else [None if f is None else np.ascontiguousarray(f, np.uint8) for f in imgs]
+        masks = [None] * m if base_masks is None else [None if b is None else np.ascontiguousarray(b, np.uint8) for b in base_masks]
+        orders = [None] * m if orders is None else list(orders)
+        pts = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in cur_pts_list]
+        assert len(frames) == m and len(publish_list) == m and len(intr_list) == m and len(masks) == m and len(orders) == m
+        assert all(f is None or f.shape == (self.H, self.W) for f in frames) and all(b is None or b.shape == (self.H, self.W) for b in masks)
+        self._bkeep_batch = masks                      # (the library remembers the mask pointers it has uploaded)
+        fin = (FrameIn * m)()
+        cbs = []
+
+        def make_cb(c):
+            n, order = len(pts[c]), orders[c]
+
+            def _cb(_user, after, out_order):
+                try:
+                    a = after.contents
+                    st = np.ctypeslib.as_array(a.status_lk, (max(n, 1),))[:n].copy()
+                    sf = np.ctypeslib.as_array(a.status_f, (max(a.n1, 1),))[:a.n1].copy() if a.ransac_ran else None
+                    fw = np.ctypeslib.as_array(a.forw_xy, (max(n, 1), 2))[:n].copy()
+                    perm = np.asarray(order(st, sf, fw, a.n2), np.int32)
+                    if perm.shape != (a.n2,):
+                        return 1
+                    for q in range(a.n2):
+                        out_order[q] = int(perm[q])
+                    return 0
+                except Exception:                      # (an exception must not travel through the C frames)
+                    return 1
+
+            return ORDER_FN(_cb)
+
+        for c in range(m):
+            f = fin[c]
+            f.struct_size = C.sizeof(FrameIn)
+            f.img = frames[c].ctypes.data_as(_u8) if frames[c] is not None else None
+            f.stride = self.W; f.equalize = int(equalize[c]); f.publish = int(bool(publish_list[c]))
+            f.cur_xy = pts[c].ctypes.data_as(_f4) if len(pts[c]) else None
+            f.n = len(pts[c]); f.max_cnt = int(max_cnt[c]); f.min_dist = int(min_dist[c]); f.quality = float(quality[c])
+            f.f_threshold = float(f_threshold[c]); f.focal_length = float(focal_length[c])
+            for i, v in enumerate(intr_list[c]):
+                f.intr[i] = float(v)
+            if masks[c] is not None:
+                f.base_mask = masks[c].ctypes.data_as(_u8)
+            cbs.append(make_cb(c) if orders[c] is not None else C.cast(None, ORDER_FN))
+            f.order = cbs[-1]
+        fo = (FrameOut * m)()
+        self.hd._chk(self.lib.vg_fe_read_image_batch(self.h, S, fin, fo), "vg_fe_read_image_batch")
+
+        def arr(ptr, shape):
+            k = int(np.prod(shape))
+            return np.ctypeslib.as_array(ptr, shape).copy() if k and ptr else np.zeros(shape, np.float32 if len(shape) == 2 else np.int32)
+
+        outs = []
+        for c in range(m):
+            o, n, publish = fo[c], len(pts[c]), bool(publish_list[c])
+            out = dict(n1=o.n1, n2=o.n2, ransac_ran=bool(o.ransac_ran), n_kept=o.n_kept, n_new=o.n_new, n_final=o.n_final,
+                       ransac_best=o.ransac_best, ransac_niters=o.ransac_niters, fallback=o.fallback)
+            out["status_lk"] = arr(o.status_lk, (n,)).astype(np.uint8)
+            out["status_f"] = arr(o.status_f, (o.n1,)).astype(np.uint8) if o.ransac_ran else None
+            out["forw_xy"] = arr(o.forw_xy, (n, 2))
+            out["kept"] = arr(o.kept, (o.n_kept,)).astype(np.int32) if publish else None
+            out["new_xy"] = arr(o.new_xy, (o.n_new, 2)) if publish else None
+            out["un_xy"] = arr(o.un_xy, (o.n_final, 2))
+            outs.append(out)
+        return outs
 
     def detect_upload(self, max_corners, masks=None):
         mc = np.ascontiguousarray(max_corners, np.int32)

@@ -145,7 +145,7 @@ namespace {
 struct OrderCtx {
     FeatureTracker* t;
     int n_in;
-    vector<pair<int, pair<cv::Point2f, int>>> sorted;      // setMask's cnt_pts_id (:43) with the list index in the place of the id
+    FeatureTracker::SortedList sorted;                     // setMask's cnt_pts_id (:43) with the list index in the place of the id
 };
 // The order of setMask's walk = the reference's sort call (:47-51): std::sort by track_cnt is not stable, the order among equal counts is
 // what the platform's std::sort makes of the sequence; its permutation depends on the comparisons only, and those look at the counts.
@@ -184,6 +184,15 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {    // :8
     }
     if ((int)cur_pts.size() > fe_capacity_) throw std::runtime_error("FeatureTracker::readImage: more points than the configured capacity");
     vg_fe_frame_in in;
+    frameInput(_img, in);
+    OrderCtx ctx{this, in.n, {}};
+    in.order = order_callback; in.user = &ctx;
+    vg_fe_frame_out out;
+    chk(vg_fe_read_image(vg_, &in, &out), vg_, "vg_fe_read_image");
+    applyFrame(_img, out, in.n, ctx.sorted);
+}
+
+void FeatureTracker::frameInput(const cv::Mat& _img, vg_fe_frame_in& in) const {
     std::memset(&in, 0, sizeof(in));
     in.struct_size = (int)sizeof(in);
     in.img = _img.data; in.stride = (int)_img.step; in.equalize = EQUALIZE; in.publish = PUB_THIS_FRAME ? 1 : 0;
@@ -192,18 +201,17 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {    // :8
     const double intr[8] = {m_camera.fx, m_camera.fy, m_camera.cx, m_camera.cy, m_camera.k1, m_camera.k2, m_camera.p1, m_camera.p2};
     std::memcpy(in.intr, intr, sizeof(intr));
     in.base_mask = (FISHEYE && PUB_THIS_FRAME) ? fisheye_mask.data : nullptr;           // :38-41 (contiguous ROW x COL, readFeatureTrackerParameters)
-    OrderCtx ctx{this, in.n, {}};
-    in.order = order_callback; in.user = &ctx;
-    vg_fe_frame_out out;
-    chk(vg_fe_read_image(vg_, &in, &out), vg_, "vg_fe_read_image");
+}
+
+void FeatureTracker::applyFrame(const cv::Mat& _img, const vg_fe_frame_out& out, int n_in, const SortedList& sorted) {
     if (forw_img.empty()) prev_img = cur_img = forw_img = _img;
     else forw_img = _img;
-    applyStatuses(out, in.n);                                                // only now: the call returned VG_OK
+    applyStatuses(out, n_in);                                                // only now: the call returned VG_OK
     if (PUB_THIS_FRAME) {
         vector<cv::Point2f> kept_pts;                                        // setMask's outcome (:53-68): the kept points in walk order
         vector<int> kept_ids, kept_cnt;
         for (int k = 0; k < out.n_kept; k++) {
-            const auto& it = ctx.sorted[out.kept[k]];
+            const auto& it = sorted[out.kept[k]];
             kept_pts.push_back(it.second.first);
             kept_ids.push_back(ids[it.second.second]);
             kept_cnt.push_back(it.first);
@@ -308,4 +316,34 @@ void FeatureTracker::liftedPoints(const float* un) {
         for (unsigned int i = 0; i < cur_pts.size(); i++) pts_velocity.push_back(cv::Point2f(0, 0));
     }
     prev_un_pts_map = cur_un_pts_map;
+}
+
+// ---- FeatureTrackerBatch: the node's loop over trackerData[i].readImage (feature_tracker_node.cpp:82-101) with one library call
+FeatureTrackerBatch::FeatureTrackerBatch(int n_streams) : trackers((size_t)std::max(n_streams, 1)) {}
+FeatureTrackerBatch::~FeatureTrackerBatch() { if (vg_) vg_destroy(vg_); }
+
+void FeatureTrackerBatch::readImages(const vector<cv::Mat>& imgs, const vector<double>& stamps) {
+    const int S = size();
+    if ((int)imgs.size() != S || (int)stamps.size() != S) throw std::runtime_error("FeatureTrackerBatch::readImages: one image and one stamp per stream");
+    if (!configured_) {
+        chk(vg_create(&vg_), vg_, "vg_create");
+        if (MAX_CNT > 2048) throw std::runtime_error("FeatureTrackerBatch::readImages: max_cnt > 2048 is not offered (vg_fe_read_image_batch)");
+        fe_capacity_ = std::min(std::max(MAX_CNT, 1) * 4, 2048);
+        chk(vg_fe_configure(vg_, COL, ROW, S, fe_capacity_), vg_, "vg_fe_configure");
+        configured_ = true;
+    }
+    vector<vg_fe_frame_in> in((size_t)S);
+    vector<vg_fe_frame_out> out((size_t)S);
+    vector<OrderCtx> ctx((size_t)S);
+    for (int c = 0; c < S; c++) {
+        if ((int)trackers[c].cur_pts.size() > fe_capacity_) throw std::runtime_error("FeatureTrackerBatch::readImages: more points than the configured capacity");
+        trackers[c].frameInput(imgs[c], in[c]);
+        ctx[c].t = &trackers[c]; ctx[c].n_in = in[c].n;
+        in[c].order = order_callback; in[c].user = &ctx[c];
+    }
+    chk(vg_fe_read_image_batch(vg_, S, in.data(), out.data()), vg_, "vg_fe_read_image_batch");
+    for (int c = 0; c < S; c++) {                                            // only now: the call returned VG_OK
+        trackers[c].cur_time = stamps[c];
+        trackers[c].applyFrame(imgs[c], out[c], in[c].n, ctx[c].sorted);
+    }
 }

@@ -50,6 +50,11 @@ class FeatureTracker {
     // the two halves of readImage around the library call (public for the order callback; not part of the reference's interface)
     void applyStatuses(const vg_fe_frame_out& after, int n_in);
     void liftedPoints(const float* un_xy);
+    // readImage around the library call: the arguments of this tracker's frame, and everything readImage does once the call has returned
+    // VG_OK (`sorted`: setMask's list as the order callback made it).  FeatureTrackerBatch runs them for S trackers around ONE call.
+    typedef vector<pair<int, pair<cv::Point2f, int>>> SortedList;
+    void frameInput(const cv::Mat& _img, vg_fe_frame_in& in) const;
+    void applyFrame(const cv::Mat& _img, const vg_fe_frame_out& out, int n_in, const SortedList& sorted);
 
     cv::Mat mask;
     cv::Mat fisheye_mask;
@@ -70,6 +75,26 @@ class FeatureTracker {
 
   private:
     vg_handle* vg_ = nullptr;      // owns the device-side pyramids of cur_img / forw_img
+    int fe_capacity_ = 0;
+    bool configured_ = false;
+};
+
+// S stand-alone trackers on ONE handle: readImages() is the loop of the reference's node over trackerData[i].readImage(...)
+// (feature_tracker_node.cpp:82-101) made with one library call, vg_fe_read_image_batch.  Every tracker keeps its own camera and its own
+// lists; COL, ROW, MAX_CNT, MIN_DIST, EQUALIZE, F_THRESHOLD and PUB_THIS_FRAME are the process-wide globals they already are (so all
+// streams publish or none does).  No tracker is touched before the call has returned VG_OK.
+class FeatureTrackerBatch {
+  public:
+    explicit FeatureTrackerBatch(int n_streams);
+    ~FeatureTrackerBatch();
+    FeatureTrackerBatch(const FeatureTrackerBatch&) = delete;
+    FeatureTrackerBatch& operator=(const FeatureTrackerBatch&) = delete;
+    void readImages(const vector<cv::Mat>& imgs, const vector<double>& stamps);
+    int size() const { return (int)trackers.size(); }
+    vector<FeatureTracker> trackers;
+
+  private:
+    vg_handle* vg_ = nullptr;
     int fe_capacity_ = 0;
     bool configured_ = false;
 };

@@ -63,6 +63,65 @@ static int replay_fe(const char* in, const char* out) {
     return 0;
 }
 
+// `fe` for S streams advancing together on one handle (FeatureTrackerBatch): list.txt names S files of the `fe` input format with the
+// same size, frame count and pub_every; stream c's lines go to <out_prefix><c>.txt in the `fe` output format
+static int replay_fe_batch(const char* list, const char* out_prefix) {
+    std::vector<std::string> names;
+    {
+        FILE* l = fopen(list, "r");
+        if (!l) { perror("list"); return 2; }
+        char line[4096];
+        while (fgets(line, sizeof(line), l)) {
+            std::string s(line);
+            while (!s.empty() && (s.back() == '\n' || s.back() == '\r' || s.back() == ' ')) s.pop_back();
+            if (!s.empty()) names.push_back(s);
+        }
+        fclose(l);
+    }
+    const int S = (int)names.size();
+    if (S < 1) { fprintf(stderr, "vins_replay fe_batch: empty list\n"); return 2; }
+    std::vector<FILE*> f((size_t)S, nullptr), o((size_t)S, nullptr);
+    int n = 0, w = 0, h = 0, pub_every = 1;
+    for (int c = 0; c < S; ++c) {
+        f[c] = fopen(names[c].c_str(), "rb");
+        if (!f[c]) { perror(names[c].c_str()); return 2; }
+        int hdr[4];
+        if (fread(hdr, sizeof(int), 4, f[c]) != 4) return 2;
+        if (c == 0) { n = hdr[0]; w = hdr[1]; h = hdr[2]; pub_every = hdr[3]; }
+        else if (hdr[0] != n || hdr[1] != w || hdr[2] != h || hdr[3] != pub_every) {
+            fprintf(stderr, "vins_replay fe_batch: %s differs from the first file in size, frame count or pub_every\n", names[c].c_str());
+            return 2;
+        }
+        o[c] = fopen((std::string(out_prefix) + std::to_string(c) + ".txt").c_str(), "w");
+        if (!o[c]) { perror("output"); return 2; }
+    }
+    COL = w; ROW = h;
+    std::vector<std::vector<unsigned char>> buf((size_t)S, std::vector<unsigned char>((size_t)w * h));
+    FeatureTrackerBatch batch(S);
+    std::vector<cv::Mat> imgs;
+    std::vector<double> stamps((size_t)S);
+    for (int k = 0; k < n; ++k) {
+        imgs.clear();
+        for (int c = 0; c < S; ++c) {
+            if (fread(buf[c].data(), 1, buf[c].size(), f[c]) != buf[c].size()) return 2;
+            imgs.push_back(cv::Mat(h, w, cv::CV_8UC1, buf[c].data(), (size_t)w));
+            stamps[c] = 0.05 * k;
+        }
+        PUB_THIS_FRAME = (k % pub_every) == 0;
+        batch.readImages(imgs, stamps);
+        for (int c = 0; c < S; ++c) {
+            FeatureTracker& tracker = batch.trackers[c];
+            for (unsigned int i = 0;; i++) if (!tracker.updateID(i)) break;
+            fprintf(o[c], "frame %d n %zu\n", k, tracker.cur_pts.size());
+            for (size_t i = 0; i < tracker.cur_pts.size(); ++i)
+                fprintf(o[c], "%d %d %.9g %.9g %.9g %.9g %.9g %.9g\n", tracker.ids[i], tracker.track_cnt[i], tracker.cur_pts[i].x, tracker.cur_pts[i].y,
+                        tracker.cur_un_pts[i].x, tracker.cur_un_pts[i].y, tracker.pts_velocity[i].x, tracker.pts_velocity[i].y);
+        }
+    }
+    for (int c = 0; c < S; ++c) { fclose(o[c]); fclose(f[c]); }
+    return 0;
+}
+
 namespace {
 struct Reader {
     FILE* f;
@@ -363,6 +422,10 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
 
 int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "fe")) return replay_fe(argv[2], argv[3]);
+    if (argc >= 4 && !strcmp(argv[1], "fe_batch")) {
+        try { return replay_fe_batch(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay fe_batch: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "ba")) {
         try { return replay_ba(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay ba: %s\n", e.what()); return 1; }
@@ -375,6 +438,6 @@ int main(int argc, char** argv) {
         try { return replay_seq(argv[2], argv[4], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay vio: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> | vins_replay fe_batch <list.txt> <out_prefix> | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv>\n");
     return 2;
 }
