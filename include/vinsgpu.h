@@ -28,7 +28,8 @@ extern "C" {
                              * 7: vg_ba_seq_export / vg_ba_seq_import; 8: vg_host_register, vg_ba_set_fused_min_windows, vg_ba_batch_is_fused;
                              * 9: vg_fe_keep_eig (the min-eigenvalue map is no longer written unless asked for);
                              * 10: vg_config / vg_create_config; vg_ba_batch_is_fused no longer returns 2; 11: vg_fe_read_image;
-                             * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode */
+                             * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
+                             * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -510,8 +511,32 @@ int vg_fe_set_mask(vg_handle* h, const float* pts_xy, const int* track_cnt, cons
 int vg_fe_detect_masked(vg_handle* h, int cam, int max_corners, double quality, double min_dist, float* out_xy, int* out_n);
 /* FeatureTracker::undistortedPoints() lifting (:258-271): PinholeCamera::liftProjective with the 8-step recursive
  * distortion model (camera_model PinholeCamera.cc:450-510, :646-661).  intr = fx fy cx cy k1 k2 p1 p2; out = (x/z, y/z)
- * as float (cv::Point2f). */
+ * as float (cv::Point2f).  The same as vg_fe_lift with a VG_CAM_PINHOLE camera of these eight numbers. */
 int vg_fe_undistort(vg_handle* h, const float* pts_xy, int n, const double* intr, float* out_xy);
+/* ---- Camera models (added within ABI 12).  The models whose liftProjective runs on the device, in double and in the reference's
+ * expression order (bit-identical to camodocal's):
+ *   VG_CAM_PINHOLE  PinholeCamera (PinholeCamera.cc:450-510): what vg_fe_frame_in::intr and vg_fe_undistort describe
+ *   VG_CAM_MEI      CataCamera, the unified model (CataCamera.cc:556-626): the pinhole lift with gamma1 gamma2 u0 v0, then
+ *                   z = 1 - xi (rho2 + 1) / (xi + sqrt(1 + (1 - xi^2) rho2)), or (1 - rho2) / 2 when xi == 1.0
+ * KANNALA_BRANDT and SCARAMUZZA are not offered (their lift is an eigenvalue problem per point). */
+#define VG_CAM_PINHOLE 0
+#define VG_CAM_MEI     1
+typedef struct vg_fe_camera {
+    int struct_size;             /* sizeof(vg_fe_camera) */
+    int model;                   /* VG_CAM_* */
+    double p[8];                 /* PINHOLE: fx fy cx cy k1 k2 p1 p2;  MEI: gamma1 gamma2 u0 v0 k1 k2 p1 p2 */
+    double xi;                   /* MEI: mirror_parameters.xi; ignored for PINHOLE */
+} vg_fe_camera;
+/* Set the camera of stream `cam` of a configured handle: from then on vg_fe_read_image / vg_fe_read_image_batch lift that stream's
+ * points with it (rejectWithF's two point sets and undistortedPoints' list) and ignore vg_fe_frame_in::intr for that stream.
+ * camera == NULL returns the stream to "pinhole from intr"; vg_fe_configure clears every stream's camera; a stream that never had a
+ * camera set behaves as it always did.  Refused with VG_ERR_BAD_ARG before anything is touched (the stream keeps the camera it had;
+ * vg_last_error says why): a wrong struct_size, an unknown model, cam outside [0, n_cams), a handle that is not configured, a
+ * non-finite parameter, p[0] or p[1] zero.  No device work, no allocation: the camera travels with the next frame's one upload. */
+int vg_fe_set_camera(vg_handle* h, int cam, const vg_fe_camera* camera);
+/* vg_fe_undistort for any model: out = ((float)(x / z), (float)(y / z)) of `camera`'s liftProjective for n points, n at most
+ * n_cams * max_points of vg_fe_configure.  Independent of the streams' cameras.  The same refusals as vg_fe_set_camera. */
+int vg_fe_lift(vg_handle* h, const vg_fe_camera* camera, const float* pts_xy, int n, float* out_xy);
 /* FeatureTracker::rejectWithF() (feature_tracker.cpp:169-202): cv::findFundamentalMat(un_cur_pts, un_forw_pts, FM_RANSAC,
  * threshold, 0.99, status) on n >= 8 correspondences given in the pixel coordinates of the virtual pinhole camera
  * (FOCAL_LENGTH * x/z + COL/2, ...).  Follows OpenCV 3.3's registrators as recalled (oracle/ASSUMPTIONS.md F9): cv::RNG((uint64)-1)
@@ -585,7 +610,7 @@ typedef struct vg_fe_frame_in {
     double quality;              /* goodFeaturesToTrack qualityLevel: 0.01 at :149 */
     double f_threshold;          /* F_THRESHOLD */
     double focal_length;         /* FOCAL_LENGTH (rejectWithF's virtual camera, :178) */
-    double intr[8];              /* PinholeCamera: fx fy cx cy k1 k2 p1 p2 */
+    double intr[8];              /* PinholeCamera: fx fy cx cy k1 k2 p1 p2 (ignored for a stream with a vg_fe_set_camera camera) */
     const uint8_t* base_mask;    /* fisheye_mask (height x width, contiguous) or NULL; uploaded when the pointer changes */
     vg_fe_order_fn order;        /* or NULL */
     void* user;
@@ -601,6 +626,8 @@ int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* ou
  * sequences replayed together -> one handle with n_cams streams and this call.
  *   per stream  (from in[c]):  img / stride, cur_xy / n, publish, max_cnt, intr, focal_length, f_threshold, base_mask, order / user.
  *               Streams that publish and streams that do not may be mixed; one that does not costs the detection an early exit.
+ *               The camera is per stream too (vg_fe_set_camera, else the pinhole of in[c].intr): streams of different models may
+ *               be mixed in one call.
  *   uniform     equalize over all streams; quality and min_dist over the streams that publish (the batched image build and the
  *               detection take ONE value each): a call that mixes them is VG_ERR_BAD_ARG.
  *   frames      every in[c].img NULL: the frames are the ones the last vg_fe_upload_frames put into the selected slot (nothing is

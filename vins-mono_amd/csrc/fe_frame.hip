@@ -1,13 +1,13 @@
 // fe_frame.hip — what FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:81-167) does BETWEEN its OpenCV calls, on
 // the device, so that vg_fe_read_image (fe_host.hip) runs a frame without handing intermediate results to the host:
 //   :115-124  status[i] && inBorder(forw_pts[i]) + reduceVector        -> fe_ri_after_lk_kernel (ordered compaction = reduceVector)
-//   :175-188  liftProjective of cur_pts / forw_pts for findFundamentalMat -> the same kernel (PinholeCamera, double, reference order)
+//   :175-188  liftProjective of cur_pts / forw_pts for findFundamentalMat -> the same kernel (the stream's camera, double, reference order)
 //   :191-198  the registrator's sequential bookkeeping over the RANSAC iterations + reduceVector by its mask -> fe_ri_pick_kernel
 //   :36-69    setMask's walk in the order the host's sort produced     -> fe_ri_setmask_kernel (+ fe_stamp_kernel of fe_kernels.hip)
 //   :144      n_max_cnt = MAX_CNT - forw_pts.size()                    -> written by the same kernel where fe_select_kernel reads it
 //   :71-79, :258-268  addPoints + undistortedPoints (liftProjective of the final list) -> fe_ri_finish_kernel
 // All of them are single-workgroup kernels on <= a few hundred points: what matters is that they need no round trip, not their
-// arithmetic.  Compiled with -ffp-contract=off: the lifting evaluates the reference's double expressions as written.
+// arithmetic.  Compiled with -ffp-contract=off: the lifting (fe_camera.h) evaluates the reference's double expressions as written.
 //
 // vg_fe_read_image_batch runs the same frame for every stream of a handle: the fe_rb_* kernels at the end of this file have one
 // workgroup (the walk: one wavefront) PER STREAM, rebuild the stream's RiDev from the device tables of RbDev and run the very bodies
@@ -19,19 +19,15 @@
 
 #define FDEV __device__ __forceinline__
 
-// PinholeCamera::liftProjective (PinholeCamera.cc:450-510), recursive distortion model with n = 8: the same expressions as
-// fe_lift_kernel (fe_kernels.hip)
-FDEV void ri_lift(const RiDev& r, float px, float py, double& mx_u, double& my_u) {
-    const double mx_d = (1.0 / r.fx) * (double)px + (-r.cx / r.fx), my_d = (1.0 / r.fy) * (double)py + (-r.cy / r.fy);
-    mx_u = mx_d; my_u = my_d;
-#pragma unroll 1
-    for (int it = 0; it < 8; ++it) {
-        const double mx2 = mx_u * mx_u, my2 = my_u * my_u, mxy = mx_u * my_u, rho2 = mx2 + my2;
-        const double rad = r.k1 * rho2 + r.k2 * rho2 * rho2;
-        const double dx = mx_u * rad + 2.0 * r.pp1 * mxy + r.pp2 * (rho2 + 2.0 * mx2);
-        const double dy = my_u * rad + 2.0 * r.pp2 * mxy + r.pp1 * (rho2 + 2.0 * my2);
-        mx_u = mx_d - dx; my_u = my_d - dy;
-    }
+// liftProjective of the stream's camera (fe_camera.h: PinholeCamera or CataCamera, the same function as fe_lift_kernel of
+// fe_kernels.hip).  r.cam.model is uniform over the workgroup.
+FDEV void ri_lift(const RiDev& r, float px, float py, double& x, double& y, double& z) { fe_cam_lift(r.cam, px, py, x, y, z); }
+// FOCAL_LENGTH * x / z + COL / 2.0 (feature_tracker.cpp:176-187), rounded to float by cv::Point2f; the pinhole's z is 1.0
+FDEV void ri_virtual(const RiDev& r, float px, float py, float* out) {
+    double x, y, z;
+    ri_lift(r, px, py, x, y, z);
+    if (r.cam.model == FE_CAM_MEI) { out[0] = (float)(r.focal * x / z + r.half_w); out[1] = (float)(r.focal * y / z + r.half_h); }
+    else { out[0] = (float)(r.focal * x + r.half_w); out[1] = (float)(r.focal * y + r.half_h); }
 }
 
 // ordered compaction of a flag over [0, n) by one workgroup of 256 threads: dst[rank of i among the set flags] = src ? src[i] : i.
@@ -74,16 +70,12 @@ FDEV void ri_after_lk_body(const FeDev& d, const RiDev& r, int* wsum) {
     const bool ransac = publish && n1 >= 8;                         // rejectWithF: `if (forw_pts.size() >= 8)` (:171)
     for (int k = tid; k < n1; k += 256) {
         const int i = r.idx1[k];
-        double ux, uy;
-        ri_lift(r, d.next_xy[2 * i], d.next_xy[2 * i + 1], ux, uy);
         if (!publish) {                                             // undistortedPoints of the list this frame ends with (:262-267)
-            r.a_un_xy[2 * k] = (float)ux; r.a_un_xy[2 * k + 1] = (float)uy;
+            fe_cam_lift_xy(r.cam, d.next_xy[2 * i], d.next_xy[2 * i + 1], r.a_un_xy[2 * k], r.a_un_xy[2 * k + 1]);
         } else {
-            if (ransac) {                                           // :176-187: FOCAL_LENGTH * x / z + COL / 2.0, rounded to float by cv::Point2f
-                r.p2[2 * k] = (float)(r.focal * ux / 1.0 + r.half_w); r.p2[2 * k + 1] = (float)(r.focal * uy / 1.0 + r.half_h);
-                double cx, cy;
-                ri_lift(r, r.xy_in[2 * i], r.xy_in[2 * i + 1], cx, cy);
-                r.p1[2 * k] = (float)(r.focal * cx / 1.0 + r.half_w); r.p1[2 * k + 1] = (float)(r.focal * cy / 1.0 + r.half_h);
+            if (ransac) {                                           // :176-187
+                ri_virtual(r, d.next_xy[2 * i], d.next_xy[2 * i + 1], r.p2 + 2 * k);
+                ri_virtual(r, r.xy_in[2 * i], r.xy_in[2 * i + 1], r.p1 + 2 * k);
             } else
                 r.idx2[k] = i;
         }
@@ -238,9 +230,7 @@ FDEV void ri_finish_body(const FeDev& d, const RiDev& r) {
             x = d.corners[2 * (k - nk)]; y = d.corners[2 * (k - nk) + 1];
             r.b_new_xy[2 * (k - nk)] = x; r.b_new_xy[2 * (k - nk) + 1] = y;
         }
-        double ux, uy;
-        ri_lift(r, x, y, ux, uy);
-        r.b_un_xy[2 * k] = (float)ux; r.b_un_xy[2 * k + 1] = (float)uy;
+        fe_cam_lift_xy(r.cam, x, y, r.b_un_xy[2 * k], r.b_un_xy[2 * k + 1]);
     }
     if (tid == 0) {
         r.ctl[RI_NNEW] = nc;
@@ -269,7 +259,7 @@ FDEV void rb_stream(const RbDev& b, const int c, FeDev& d, RiDev& r) {
     r.niters_tab = b.niters_tab; r.tab_stride = b.tab_stride;
     r.count = b.count + (size_t)c * FE_RANSAC_MAXIT; r.words = b.words + (size_t)c * FE_RANSAC_MAXIT * b.words_n;
     r.focal = k.focal; r.half_w = k.half_w; r.half_h = k.half_h;
-    r.fx = k.fx; r.fy = k.fy; r.cx = k.cx; r.cy = k.cy; r.k1 = k.k1; r.k2 = k.k2; r.pp1 = k.pp1; r.pp2 = k.pp2;
+    r.cam = k.cam;
     r.max_cnt = k.max_cnt; r.radius = k.radius;
     r.kept_xy = b.kept_xy + c * cap * 2;
     r.base_mask = (b.base && k.has_base) ? b.base + (size_t)c * d.W * d.H : nullptr;

@@ -33,8 +33,7 @@ hipError_t fe_launch_select(const FeDev& d, double quality, float min_dist, hipS
 __global__ void fe_setmask_kernel(FeDev d, const float* pts_xy, const int* track_cnt, const int* npts, const uint8_t* const* base_masks,
                                   int radius, int* kept_index, int* n_kept, int* kept_xy);
 __global__ void fe_stamp_kernel(FeDev d, const int* n_kept, const int* kept_xy, int radius);
-__global__ void fe_lift_kernel(const float* pts_xy, int n, double fx, double fy, double cx, double cy, double k1, double k2, double p1,
-                               double p2, float* out_xy);
+__global__ void fe_lift_kernel(const float* pts_xy, int n, FeCamera cam, float* out_xy);
 // vg_fe_read_image (fe_frame.hip, fe_ransac.hip)
 __global__ void fe_ri_after_lk_kernel(FeDev d, RiDev r);
 __global__ void fe_ri_pick_kernel(RiDev r);
@@ -127,6 +126,8 @@ struct FeState {
     bool have_prev = false;
     bool prev_clobbered = false;     // an upload has overwritten the frame slot the PREVIOUS pyramid uses as its level 0: no tracking until the next build
     std::vector<char> pushed_once;
+    std::vector<FeCamera> cam;       // [cams] vg_fe_set_camera; cam_set[c] == 0: the pinhole of vg_fe_frame_in::intr
+    std::vector<char> cam_set;
     RiState* ri = nullptr;
     RbState* rb = nullptr;
 };
@@ -228,6 +229,8 @@ extern "C" int vg_fe_configure(vg_handle* h, int width, int height, int n_cams, 
     d.max_corners = s->max_corners; d.corners = s->corners; d.ncorners = s->ncorners;
     s->h_npts.assign(n_cams, 0);
     s->pushed_once.assign(n_cams, 0);
+    s->cam.assign(n_cams, FeCamera());
+    s->cam_set.assign(n_cams, 0);
     refresh(s);
     return VG_OK;
 }
@@ -546,23 +549,74 @@ extern "C" int vg_fe_get_mask(vg_handle* h, int cam, uint8_t* out) {
     return VG_OK;
 }
 
-// PinholeCamera::liftProjective for a batch of points (feature_tracker.cpp:258-271)
-extern "C" int vg_fe_undistort(vg_handle* h, const float* pts_xy, int n, const double* intr, float* out_xy) {
-    if (!h || !h->fe || n < 0 || !intr || (n > 0 && (!pts_xy || !out_xy))) return VG_ERR_BAD_ARG;
+// ---- camera models (fe_camera.h)
+static FeCamera fe_pinhole(const double* intr) {
+    FeCamera c;
+    c.model = FE_CAM_PINHOLE;
+    for (int i = 0; i < 8; ++i) c.p[i] = intr[i];
+    c.xi = 0.0;
+    return c;
+}
+// the camera stream `c` lifts with: the one vg_fe_set_camera gave it, else the pinhole of the frame's intr
+static FeCamera fe_stream_camera(const FeState* s, int c, const double* intr) { return s->cam_set[c] ? s->cam[c] : fe_pinhole(intr); }
+
+// a caller's vg_fe_camera -> FeCamera, or the reason it is refused
+static const char* fe_camera_check(const vg_fe_camera* in, FeCamera* out) {
+    if (in->struct_size != (int)sizeof(vg_fe_camera)) return "struct_size is not sizeof(vg_fe_camera)";
+    if (in->model != VG_CAM_PINHOLE && in->model != VG_CAM_MEI) return "unknown camera model";
+    for (int i = 0; i < 8; ++i)
+        if (!std::isfinite(in->p[i])) return "a camera parameter is not finite";
+    if (in->model == VG_CAM_MEI && !std::isfinite(in->xi)) return "xi is not finite";
+    if (in->p[0] == 0.0 || in->p[1] == 0.0) return "a zero focal length (p[0] / p[1])";
+    out->model = in->model == VG_CAM_MEI ? FE_CAM_MEI : FE_CAM_PINHOLE;
+    for (int i = 0; i < 8; ++i) out->p[i] = in->p[i];
+    out->xi = in->model == VG_CAM_MEI ? in->xi : 0.0;
+    return nullptr;
+}
+
+extern "C" int vg_fe_set_camera(vg_handle* h, int cam, const vg_fe_camera* camera) {
+    if (!h) return VG_ERR_BAD_ARG;
+    if (!h->fe) { h->err = "vg_fe_set_camera: the handle has no front end (vg_fe_configure)"; return VG_ERR_BAD_ARG; }
+    FeState* s = h->fe;
+    if (cam < 0 || cam >= s->cams) { h->err = "vg_fe_set_camera: no such stream"; return VG_ERR_BAD_ARG; }
+    if (!camera) { s->cam_set[cam] = 0; return VG_OK; }
+    FeCamera c;
+    if (const char* why = fe_camera_check(camera, &c)) { h->err = std::string("vg_fe_set_camera: ") + why; return VG_ERR_BAD_ARG; }
+    s->cam[cam] = c;
+    s->cam_set[cam] = 1;
+    return VG_OK;
+}
+
+static int fe_lift_points(vg_handle* h, const char* who, const FeCamera& c, const float* pts_xy, int n, float* out_xy) {
     FeState* s = h->fe;
     if (n == 0) return VG_OK;
-    if ((size_t)n > (size_t)s->cams * s->max_pts) { h->err = "vg_fe_undistort: more points than configured"; return VG_ERR_BAD_ARG; }
+    if ((size_t)n > (size_t)s->cams * s->max_pts) { h->err = std::string(who) + ": more points than configured"; return VG_ERR_BAD_ARG; }
     if (!s->lift_in) {
         HIPCHK(h, hipMalloc((void**)&s->lift_in, sizeof(float) * 2 * s->cams * s->max_pts));
         HIPCHK(h, hipMalloc((void**)&s->lift_out, sizeof(float) * 2 * s->cams * s->max_pts));
     }
     HIPCHK(h, hipMemcpyAsync(s->lift_in, pts_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(fe_lift_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, s->lift_in, n, intr[0], intr[1], intr[2], intr[3],
-                       intr[4], intr[5], intr[6], intr[7], s->lift_out);
+    hipLaunchKernelGGL(fe_lift_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const float*)s->lift_in, n, c, s->lift_out);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out_xy, s->lift_out, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return VG_OK;
+}
+
+// liftProjective of any camera model for a batch of points (feature_tracker.cpp:258-271)
+extern "C" int vg_fe_lift(vg_handle* h, const vg_fe_camera* camera, const float* pts_xy, int n, float* out_xy) {
+    if (!h) return VG_ERR_BAD_ARG;
+    if (!h->fe) { h->err = "vg_fe_lift: the handle has no front end (vg_fe_configure)"; return VG_ERR_BAD_ARG; }
+    if (n < 0 || !camera || (n > 0 && (!pts_xy || !out_xy))) { h->err = "vg_fe_lift: camera / points / n"; return VG_ERR_BAD_ARG; }
+    FeCamera c;
+    if (const char* why = fe_camera_check(camera, &c)) { h->err = std::string("vg_fe_lift: ") + why; return VG_ERR_BAD_ARG; }
+    return fe_lift_points(h, "vg_fe_lift", c, pts_xy, n, out_xy);
+}
+
+// PinholeCamera::liftProjective for a batch of points: vg_fe_lift with the pinhole of `intr`
+extern "C" int vg_fe_undistort(vg_handle* h, const float* pts_xy, int n, const double* intr, float* out_xy) {
+    if (!h || !h->fe || n < 0 || !intr || (n > 0 && (!pts_xy || !out_xy))) return VG_ERR_BAD_ARG;
+    return fe_lift_points(h, "vg_fe_undistort", fe_pinhole(intr), pts_xy, n, out_xy);
 }
 
 extern "C" int vg_fe_get_level(vg_handle* h, int cam, int which, int level, uint8_t* out, int* w, int* hgt) {
@@ -674,8 +728,7 @@ extern "C" int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_fr
     memset(out, 0, sizeof(*out));
     RiDev r = q->r;
     r.focal = in->focal_length; r.half_w = s->W / 2.0; r.half_h = s->H / 2.0;
-    r.fx = in->intr[0]; r.fy = in->intr[1]; r.cx = in->intr[2]; r.cy = in->intr[3];
-    r.k1 = in->intr[4]; r.k2 = in->intr[5]; r.pp1 = in->intr[6]; r.pp2 = in->intr[7];
+    r.cam = fe_stream_camera(s, 0, in->intr);
     r.max_cnt = in->max_cnt; r.radius = in->min_dist;
     FeRansacBufs rb;
     { const hipError_t e = fe_ransac_buffers(h, &rb); if (e != hipSuccess) { h->err = std::string("vg_fe_read_image: ") + hipGetErrorString(e); return VG_ERR_HIP; } }
@@ -938,8 +991,7 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
             hctl[c * RI_CTL_INTS + RI_N] = f.n; hctl[c * RI_CTL_INTS + RI_PUBLISH] = f.publish ? 1 : 0; hctl[c * RI_CTL_INTS + RI_BEST] = -1;
             RiCam& k = hcam[c];
             k.focal = f.focal_length; k.half_w = s->W / 2.0; k.half_h = s->H / 2.0;
-            k.fx = f.intr[0]; k.fy = f.intr[1]; k.cx = f.intr[2]; k.cy = f.intr[3];
-            k.k1 = f.intr[4]; k.k2 = f.intr[5]; k.pp1 = f.intr[6]; k.pp2 = f.intr[7];
+            k.cam = fe_stream_camera(s, c, f.intr);
             k.thresh2 = (float)(f.f_threshold * f.f_threshold);
             k.max_cnt = f.max_cnt; k.radius = f.min_dist; k.has_base = (f.publish && f.base_mask) ? 1 : 0;
             if (f.n) memcpy(hxy + (size_t)c * cap * 2, f.cur_xy, sizeof(float) * 2 * f.n);

@@ -1295,23 +1295,13 @@ extern "C" __global__ __launch_bounds__(256) void fe_stamp_kernel(FeDev d, const
         if (x >= 0 && y >= 0 && x < d.W && y < d.H && dx * dx + dy * dy <= r2) m[(size_t)y * d.W + x] = 0;
     }
 }
-// PinholeCamera::liftProjective, recursive distortion model with n = 8 (PinholeCamera.cc:450-510, :646-661); thread per
-// point, double arithmetic in the reference's order (this file is compiled with -ffp-contract=off)
-extern "C" __global__ __launch_bounds__(256) void fe_lift_kernel(const float* __restrict__ pts_xy, int n, double fx, double fy, double cx, double cy,
-                                                                 double k1, double k2, double p1, double p2, float* __restrict__ out_xy) {
+// liftProjective of one camera (fe_camera.h: PinholeCamera or CataCamera) for a list of points, (x / z, y / z) as float; thread per
+// point, double arithmetic in the reference's order (this file is compiled with -ffp-contract=off).  The model is a kernel argument:
+// the branch on it is scalar.
+extern "C" __global__ __launch_bounds__(256) void fe_lift_kernel(const float* __restrict__ pts_xy, int n, FeCamera cam, float* __restrict__ out_xy) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double mx_d = (1.0 / fx) * (double)pts_xy[2 * i] + (-cx / fx), my_d = (1.0 / fy) * (double)pts_xy[2 * i + 1] + (-cy / fy);
-    double mx_u = mx_d, my_u = my_d;
-#pragma unroll 1
-    for (int it = 0; it < 8; ++it) {
-        const double mx2 = mx_u * mx_u, my2 = my_u * my_u, mxy = mx_u * my_u, rho2 = mx2 + my2;
-        const double rad = k1 * rho2 + k2 * rho2 * rho2;
-        const double dx = mx_u * rad + 2.0 * p1 * mxy + p2 * (rho2 + 2.0 * mx2);
-        const double dy = my_u * rad + 2.0 * p2 * mxy + p1 * (rho2 + 2.0 * my2);
-        mx_u = mx_d - dx; my_u = my_d - dy;
-    }
-    out_xy[2 * i] = (float)mx_u; out_xy[2 * i + 1] = (float)my_u;
+    fe_cam_lift_xy(cam, pts_xy[2 * i], pts_xy[2 * i + 1], out_xy[2 * i], out_xy[2 * i + 1]);
 }
 
 #define FE_SEL_LDS_BYTES (FE_SEL_CAP * 8 + FE_SEL_BINS * 4 + 64 * 4 + 8 * 4 + FE_MAX_CELLS * 7 * 2 * 2 + FE_MAX_CELLS)

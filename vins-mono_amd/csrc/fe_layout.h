@@ -1,6 +1,7 @@
 // fe_layout.h — device-side descriptor of the front-end state (shared by fe_host.hip and fe_kernels.hip).
 #pragma once
 #include <stdint.h>
+#include "fe_camera.h"
 #define FE_MAX_LEVELS 4
 #define FE_MAX_CELLS 1024
 #define FE_CAND_CAP 65536           // power of two >= number of 3x3 local maxima of a 752x480 frame
@@ -80,7 +81,7 @@ struct RiDev {
     const int* count;               // [FE_RANSAC_MAXIT] inliers of the iteration's best model (-1: no model)
     const unsigned long long* words;  // [FE_RANSAC_MAXIT][ceil(n1 / 64)] its inlier set
     double focal, half_w, half_h;   // FOCAL_LENGTH, COL / 2.0, ROW / 2.0
-    double fx, fy, cx, cy, k1, k2, pp1, pp2;
+    FeCamera cam;                   // the stream's camera (vg_fe_set_camera, or the pinhole of vg_fe_frame_in::intr)
     int max_cnt, radius;
     int* kept_xy;                   // [cap][2] rounded positions of the kept points (fe_stamp_kernel)
     const uint8_t* base_mask;       // fisheye mask or nullptr
@@ -91,7 +92,7 @@ struct RiDev {
 #define RB_CHUNK0 63                // RANSAC iterations every stream evaluates before the bookkeeping first looks (9 wavefronts of 7 samples)
 struct RiCam {                      // per stream, uploaded with the points
     double focal, half_w, half_h;
-    double fx, fy, cx, cy, k1, k2, pp1, pp2;
+    FeCamera cam;
     float thresh2;                  // (float)(F_THRESHOLD^2)
     int max_cnt, radius, has_base;
 };

@@ -25,6 +25,30 @@ class FrameIn(C.Structure):
                 ("focal_length", C.c_double), ("intr", C.c_double * 8), ("base_mask", _u8), ("order", ORDER_FN), ("user", C.c_void_p)]
 
 
+CAM_PINHOLE, CAM_MEI = 0, 1
+
+
+class Camera(C.Structure):
+    """vg_fe_camera (include/vinsgpu.h): Camera.pinhole(fx, fy, cx, cy, k1, k2, p1, p2) or Camera.mei(xi, gamma1, gamma2, u0, v0, k1, k2, p1, p2)"""
+    _fields_ = [("struct_size", C.c_int), ("model", C.c_int), ("p", C.c_double * 8), ("xi", C.c_double)]
+
+    @classmethod
+    def make(cls, model, p, xi=0.0):
+        c = cls()
+        c.struct_size, c.model, c.xi = C.sizeof(cls), int(model), float(xi)
+        for i, v in enumerate(p):
+            c.p[i] = float(v)
+        return c
+
+    @classmethod
+    def pinhole(cls, *p):
+        return cls.make(CAM_PINHOLE, p)
+
+    @classmethod
+    def mei(cls, xi, *p):
+        return cls.make(CAM_MEI, p, xi)
+
+
 class FrontEnd:
     """`n_cams` camera streams on one vg_handle (ba.Handle)."""
 
@@ -57,6 +81,9 @@ class FrontEnd:
         L.vg_fe_read_image.argtypes = [C.c_void_p, C.POINTER(FrameIn), C.POINTER(FrameOut)]
         if hasattr(L, "vg_fe_read_image_batch"):          # (a library built before the batched call: read_image_batch() raises AttributeError)
             L.vg_fe_read_image_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameIn), C.POINTER(FrameOut)]
+        if hasattr(L, "vg_fe_set_camera"):                # (a library built before the camera models: set_camera() / lift() raise AttributeError)
+            L.vg_fe_set_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(Camera)]
+            L.vg_fe_lift.argtypes = [C.c_void_p, C.POINTER(Camera), _f4, C.c_int, _f4]
         self.hd._chk(L.vg_fe_configure(self.h, width, height, n_cams, max_points), "vg_fe_configure")
 
     def _imgs(self, frames):
@@ -157,6 +184,17 @@ class FrontEnd:
                                               out.ctypes.data_as(_f4)), "vg_fe_undistort")
         return out
 
+    def set_camera(self, cam, camera):
+        """vg_fe_set_camera: stream `cam` lifts with `camera` (a Camera) from now on; None: back to the pinhole of the frames' intr."""
+        self.hd._chk(self.lib.vg_fe_set_camera(self.h, int(cam), None if camera is None else C.byref(camera)), "vg_fe_set_camera")
+
+    def lift(self, pts, camera):
+        """vg_fe_lift: (x / z, y / z) of `camera`'s liftProjective, float32 [n, 2]"""
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        out = np.zeros_like(p)
+        self.hd._chk(self.lib.vg_fe_lift(self.h, C.byref(camera), p.ctypes.data_as(_f4), len(p), out.ctypes.data_as(_f4)), "vg_fe_lift")
+        return out
+
     def reject_with_f(self, p1, p2, threshold=1.0):
         """FeatureTracker::rejectWithF's findFundamentalMat(FM_RANSAC, threshold, 0.99) on the device (deterministic RANSAC).
         p1, p2: [n, 2] float32 virtual-pinhole pixel coordinates.  Returns (status u8 [n], F 3x3)."""
@@ -172,9 +210,12 @@ class FrontEnd:
         return st, Fm.reshape(3, 3)
 
     def read_image(self, img, cur_pts, publish, intr, max_cnt=150, min_dist=30, equalize=False, f_threshold=1.0, focal_length=460.0,
-                   quality=0.01, base_mask=None, order=None):
+                   quality=0.01, base_mask=None, order=None, camera=None):
         """vg_fe_read_image: FeatureTracker::readImage of one stream in one call.  `order(status_lk, status_f or None, forw_xy, n2)` returns
-        the walk order of setMask as indices into the n2 survivors (None: the list as it stands).  Returns a dict of numpy copies."""
+        the walk order of setMask as indices into the n2 survivors (None: the list as it stands).  `camera`: a Camera that is set on the
+        stream first (set_camera; it stays), `intr` may then be None.  Returns a dict of numpy copies."""
+        if camera is not None:
+            self.set_camera(0, camera)
         img = np.ascontiguousarray(img, np.uint8)
         assert img.shape == (self.H, self.W)
         pts = np.ascontiguousarray(cur_pts, np.float32).reshape(-1, 2)
@@ -185,7 +226,7 @@ class FrontEnd:
         fin.cur_xy = pts.ctypes.data_as(_f4) if n else None
         fin.n = n; fin.max_cnt = int(max_cnt); fin.min_dist = int(min_dist); fin.quality = float(quality)
         fin.f_threshold = float(f_threshold); fin.focal_length = float(focal_length)
-        for i, v in enumerate(intr):
+        for i, v in enumerate(intr if intr is not None else ()):
             fin.intr[i] = float(v)
         if base_mask is not None:
             self._base = np.ascontiguousarray(base_mask, np.uint8)
@@ -226,13 +267,17 @@ class FrontEnd:
         return out
 
     def read_image_batch(self, imgs, cur_pts_list, publish_list, intr_list, max_cnt=150, min_dist=30, equalize=False, f_threshold=1.0,
-                         focal_length=460.0, quality=0.01, base_masks=None, orders=None, n_streams=None):
+                         focal_length=460.0, quality=0.01, base_masks=None, orders=None, n_streams=None, cameras=None):
         """vg_fe_read_image_batch: FeatureTracker::readImage of every stream of the handle in one call.  imgs: one frame per stream, or None
         for the frames the last upload_frames() left on the device (a list may hold None entries: the library refuses a mixture).
         cur_pts_list / publish_list / intr_list: one entry per stream.  max_cnt, min_dist, equalize, f_threshold, focal_length, quality: one
         value for all streams or a list (the library wants equalize uniform, and quality / min_dist uniform over the publishing streams).
         base_masks / orders: None or lists with None entries; orders[c] as `order` of read_image().  n_streams: what is passed to the
-        library (default: the number of list entries).  Returns the list of the dictionaries read_image() returns."""
+        library (default: the number of list entries).  cameras: None or a list with a Camera (set on that stream first; it stays) or None
+        per stream; intr_list[c] may be None for a stream with a camera.  Returns the list of the dictionaries read_image() returns."""
+        for c, cam in enumerate(cameras or ()):
+            if cam is not None:
+                self.set_camera(c, cam)
         S = len(cur_pts_list) if n_streams is None else int(n_streams)
         m = len(cur_pts_list)
 
@@ -278,7 +323,7 @@ class FrontEnd:
             f.cur_xy = pts[c].ctypes.data_as(_f4) if len(pts[c]) else None
             f.n = len(pts[c]); f.max_cnt = int(max_cnt[c]); f.min_dist = int(min_dist[c]); f.quality = float(quality[c])
             f.f_threshold = float(f_threshold[c]); f.focal_length = float(focal_length[c])
-            for i, v in enumerate(intr_list[c]):
+            for i, v in enumerate(intr_list[c] if intr_list[c] is not None else ()):
                 f.intr[i] = float(v)
             if masks[c] is not None:
                 f.base_mask = masks[c].ctypes.data_as(_u8)

@@ -58,22 +58,19 @@ void reduceVector(vector<int>& v, vector<uchar> status) {           // :22-29
     v.resize(j);
 }
 
-void PinholeModel::liftProjective(double u, double v, double& x, double& y) const {
-    // PinholeCamera::liftProjective, recursive distortion model with n = 8 (PinholeCamera.cc:450-510, :646-661)
-    const double mx_d = (1.0 / fx) * u + (-cx / fx), my_d = (1.0 / fy) * v + (-cy / fy);
-    auto distortion = [&](double px, double py, double& dx, double& dy) {
-        const double mx2 = px * px, my2 = py * py, mxy = px * py, rho2 = mx2 + my2, rad = k1 * rho2 + k2 * rho2 * rho2;
-        dx = px * rad + 2.0 * p1 * mxy + p2 * (rho2 + 2.0 * mx2);
-        dy = py * rad + 2.0 * p2 * mxy + p1 * (rho2 + 2.0 * my2);
-    };
-    double dx, dy;
-    distortion(mx_d, my_d, dx, dy);
-    double mx_u = mx_d - dx, my_u = my_d - dy;
-    for (int i = 1; i < 8; ++i) {
-        distortion(mx_u, my_u, dx, dy);
-        mx_u = mx_d - dx; my_u = my_d - dy;
-    }
-    x = mx_u; y = my_u;
+void CameraModel::liftProjective(float u, float v, double& x, double& y, double& z) const {
+    FeCamera c;
+    c.model = model == VG_CAM_MEI ? FE_CAM_MEI : FE_CAM_PINHOLE;
+    for (int i = 0; i < 8; ++i) c.p[i] = p[i];
+    c.xi = xi;
+    fe_cam_lift(c, u, v, x, y, z);
+}
+vg_fe_camera CameraModel::abi() const {
+    vg_fe_camera c;
+    std::memset(&c, 0, sizeof(c));
+    c.struct_size = (int)sizeof(c); c.model = model; c.xi = xi;
+    for (int i = 0; i < 8; ++i) c.p[i] = p[i];
+    return c;
 }
 
 FeatureTracker::FeatureTracker() : cur_time(0), prev_time(0) {}
@@ -181,6 +178,12 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {    // :8
         fe_capacity_ = std::min(std::max(MAX_CNT, 1) * 4, 2048);
         chk(vg_fe_configure(vg_, COL, ROW, 1, fe_capacity_), vg_, "vg_fe_configure");
         configured_ = true;
+        camera_sent_ = false;                                                // (vg_fe_configure clears the stream's camera)
+    }
+    if (!camera_sent_) {
+        const vg_fe_camera cam = m_camera.abi();
+        chk(vg_fe_set_camera(vg_, 0, &cam), vg_, "vg_fe_set_camera");
+        camera_sent_ = true;
     }
     if ((int)cur_pts.size() > fe_capacity_) throw std::runtime_error("FeatureTracker::readImage: more points than the configured capacity");
     vg_fe_frame_in in;
@@ -198,8 +201,7 @@ void FeatureTracker::frameInput(const cv::Mat& _img, vg_fe_frame_in& in) const {
     in.img = _img.data; in.stride = (int)_img.step; in.equalize = EQUALIZE; in.publish = PUB_THIS_FRAME ? 1 : 0;
     in.cur_xy = cur_pts.empty() ? nullptr : &cur_pts[0].x; in.n = (int)cur_pts.size();
     in.max_cnt = MAX_CNT; in.min_dist = MIN_DIST; in.quality = 0.01; in.f_threshold = F_THRESHOLD; in.focal_length = FOCAL_LENGTH;
-    const double intr[8] = {m_camera.fx, m_camera.fy, m_camera.cx, m_camera.cy, m_camera.k1, m_camera.k2, m_camera.p1, m_camera.p2};
-    std::memcpy(in.intr, intr, sizeof(intr));
+    std::memcpy(in.intr, m_camera.p, sizeof(in.intr));                                  // (the stream lifts with its vg_fe_set_camera camera)
     in.base_mask = (FISHEYE && PUB_THIS_FRAME) ? fisheye_mask.data : nullptr;           // :38-41 (contiguous ROW x COL, readFeatureTrackerParameters)
 }
 
@@ -236,14 +238,14 @@ void FeatureTracker::rejectWithF() {                                       // fe
         const int n = (int)forw_pts.size();
         vector<cv::Point2f> un_cur_pts(cur_pts.size()), un_forw_pts(forw_pts.size());
         for (unsigned int i = 0; i < cur_pts.size(); i++) {
-            double x, y;
-            m_camera.liftProjective(cur_pts[i].x, cur_pts[i].y, x, y);
-            x = FOCAL_LENGTH * x + COL / 2.0;
-            y = FOCAL_LENGTH * y + ROW / 2.0;
+            double x, y, z;
+            m_camera.liftProjective(cur_pts[i].x, cur_pts[i].y, x, y, z);
+            x = FOCAL_LENGTH * x / z + COL / 2.0;
+            y = FOCAL_LENGTH * y / z + ROW / 2.0;
             un_cur_pts[i] = cv::Point2f((float)x, (float)y);
-            m_camera.liftProjective(forw_pts[i].x, forw_pts[i].y, x, y);
-            x = FOCAL_LENGTH * x + COL / 2.0;
-            y = FOCAL_LENGTH * y + ROW / 2.0;
+            m_camera.liftProjective(forw_pts[i].x, forw_pts[i].y, x, y, z);
+            x = FOCAL_LENGTH * x / z + COL / 2.0;
+            y = FOCAL_LENGTH * y / z + ROW / 2.0;
             un_forw_pts[i] = cv::Point2f((float)x, (float)y);
         }
         vector<uchar> status(n);
@@ -267,24 +269,37 @@ bool FeatureTracker::updateID(unsigned int i) {                              // 
 }
 
 void FeatureTracker::readIntrinsicParameter(const string& calib_file) {
-    // feature_tracker.cpp:216-220 -> CameraFactory::generateCameraFromYamlFile -> PinholeCamera::Parameters::readFromYamlFile
-    // (camera_model/src/camera_models/PinholeCamera.cc): model_type PINHOLE, distortion_parameters k1 k2 p1 p2, projection_parameters
-    // fx fy cx cy.  Other camera models (MEI, KANNALA_BRANDT) are outside this front end (camodocal is out of scope).
+    // feature_tracker.cpp:216-220 -> CameraFactory::generateCameraFromYamlFile ->
+    //   model_type PINHOLE: PinholeCamera::Parameters::readFromYamlFile (PinholeCamera.cc:144-183): distortion_parameters k1 k2 p1 p2,
+    //                       projection_parameters fx fy cx cy
+    //   model_type MEI:     CataCamera::Parameters::readFromYamlFile (CataCamera.cc:161-203): mirror_parameters xi,
+    //                       distortion_parameters k1 k2 p1 p2, projection_parameters gamma1 gamma2 u0 v0
+    // These two lift on the device (csrc/fe_camera.h).  KANNALA_BRANDT and SCARAMUZZA are refused by name: their lift is an eigenvalue
+    // problem per point (EquidistantCamera.cc:716-800) and is not offered.
     VinsYaml fs;
     if (!fs.load(calib_file)) throw std::runtime_error("readIntrinsicParameter: cannot read " + calib_file);
     const std::string model = fs.str("model_type", "PINHOLE");
-    if (model != "PINHOLE") throw std::runtime_error("readIntrinsicParameter: camera model " + model + " is not supported (PINHOLE only)");
-    m_camera.k1 = fs.number("distortion_parameters.k1"); m_camera.k2 = fs.number("distortion_parameters.k2");
-    m_camera.p1 = fs.number("distortion_parameters.p1"); m_camera.p2 = fs.number("distortion_parameters.p2");
-    m_camera.fx = fs.number("projection_parameters.fx"); m_camera.fy = fs.number("projection_parameters.fy");
-    m_camera.cx = fs.number("projection_parameters.cx"); m_camera.cy = fs.number("projection_parameters.cy");
+    const bool mei = model == "MEI";
+    if (model != "PINHOLE" && !mei)
+        throw std::runtime_error("readIntrinsicParameter: camera model " + model + " is not supported (PINHOLE and MEI lift on the device)");
+    CameraModel c;
+    c.model = mei ? VG_CAM_MEI : VG_CAM_PINHOLE;
+    c.xi = mei ? fs.number("mirror_parameters.xi") : 0.0;
+    c.p[0] = fs.number(mei ? "projection_parameters.gamma1" : "projection_parameters.fx");
+    c.p[1] = fs.number(mei ? "projection_parameters.gamma2" : "projection_parameters.fy");
+    c.p[2] = fs.number(mei ? "projection_parameters.u0" : "projection_parameters.cx");
+    c.p[3] = fs.number(mei ? "projection_parameters.v0" : "projection_parameters.cy");
+    c.p[4] = fs.number("distortion_parameters.k1"); c.p[5] = fs.number("distortion_parameters.k2");
+    c.p[6] = fs.number("distortion_parameters.p1"); c.p[7] = fs.number("distortion_parameters.p2");
+    m_camera = c;
+    camera_sent_ = false;                                                    // (a configured stream gets it with its next frame)
 }
 
 void FeatureTracker::undistortedPoints() {                                   // :258-306, lifting on the device
     const int n = (int)cur_pts.size();
     std::vector<float> un((size_t)std::max(n, 1) * 2);
-    const double intr[8] = {m_camera.fx, m_camera.fy, m_camera.cx, m_camera.cy, m_camera.k1, m_camera.k2, m_camera.p1, m_camera.p2};
-    if (n > 0) chk(vg_fe_undistort(vg_, &cur_pts[0].x, n, intr, un.data()), vg_, "vg_fe_undistort");
+    const vg_fe_camera cam = m_camera.abi();
+    if (n > 0) chk(vg_fe_lift(vg_, &cam, &cur_pts[0].x, n, un.data()), vg_, "vg_fe_lift");
     liftedPoints(un.data());
 }
 
@@ -330,7 +345,14 @@ void FeatureTrackerBatch::readImages(const vector<cv::Mat>& imgs, const vector<d
         if (MAX_CNT > 2048) throw std::runtime_error("FeatureTrackerBatch::readImages: max_cnt > 2048 is not offered (vg_fe_read_image_batch)");
         fe_capacity_ = std::min(std::max(MAX_CNT, 1) * 4, 2048);
         chk(vg_fe_configure(vg_, COL, ROW, S, fe_capacity_), vg_, "vg_fe_configure");
+        for (int c = 0; c < S; c++) trackers[c].camera_sent_ = false;        // (vg_fe_configure clears every stream's camera)
         configured_ = true;
+    }
+    for (int c = 0; c < S; c++) {                                            // every tracker keeps its own camera: the models may differ
+        if (trackers[c].camera_sent_) continue;
+        const vg_fe_camera cam = trackers[c].m_camera.abi();
+        chk(vg_fe_set_camera(vg_, c, &cam), vg_, "vg_fe_set_camera");
+        trackers[c].camera_sent_ = true;
     }
     vector<vg_fe_frame_in> in((size_t)S);
     vector<vg_fe_frame_out> out((size_t)S);

@@ -6,14 +6,16 @@
 //   cv::calcOpticalFlowPyrLK         -> vg_fe_track                          (:113)
 //   cv::goodFeaturesToTrack          -> vg_fe_detect                         (:149)
 //   cv::findFundamentalMat(RANSAC)   -> vg_fe_reject_with_f                  (:191; deterministic RANSAC, ASSUMPTIONS F9)
-// Differences (documented in INTEGRATION.md): the camera model is the EuRoC pinhole restated from
-// camera_model/src/camera_models/PinholeCamera.cc:450-510,646-661 instead of camodocal::CameraPtr.
+// Differences (documented in INTEGRATION.md): the camera model is CameraModel below -- PinholeCamera or CataCamera (MEI) restated
+// from camera_model/src/camera_models/{PinholeCamera,CataCamera}.cc in csrc/fe_camera.h, the function the kernels lift with --
+// instead of camodocal::CameraPtr.
 #pragma once
 #include <map>
 #include <string>
 #include <vector>
 #include "compat/cv_compat.h"
 #include "../../include/vinsgpu.h"
+#include "../csrc/fe_camera.h"
 
 using namespace std;
 
@@ -30,9 +32,13 @@ bool inBorder(const cv::Point2f& pt);
 void reduceVector(vector<cv::Point2f>& v, vector<uchar> status);
 void reduceVector(vector<int>& v, vector<uchar> status);
 
-struct PinholeModel {            // camodocal::PinholeCamera parameters (config/euroc/euroc_config.yaml:13-22)
-    double fx = 461.6, fy = 460.3, cx = 363.0, cy = 248.1, k1 = -2.917e-01, k2 = 8.228e-02, p1 = 5.333e-05, p2 = -1.578e-04;
-    void liftProjective(double u, double v, double& x, double& y) const;
+// camodocal::PinholeCamera or camodocal::CataCamera parameters; the default is config/euroc/euroc_config.yaml:13-22
+struct CameraModel {
+    int model = VG_CAM_PINHOLE;
+    double p[8] = {461.6, 460.3, 363.0, 248.1, -2.917e-01, 8.228e-02, 5.333e-05, -1.578e-04};   // fx fy cx cy | gamma1 gamma2 u0 v0, then k1 k2 p1 p2
+    double xi = 0.0;             // MEI: mirror_parameters.xi
+    void liftProjective(float u, float v, double& x, double& y, double& z) const;     // the projective ray, as the kernels compute it
+    vg_fe_camera abi() const;    // what vg_fe_set_camera / vg_fe_lift take
 };
 
 class FeatureTracker {
@@ -44,7 +50,7 @@ class FeatureTracker {
     void setMask();
     void addPoints();
     bool updateID(unsigned int i);
-    void readIntrinsicParameter(const string& calib_file);   // PINHOLE section of the configuration file (host/yaml_config.h)
+    void readIntrinsicParameter(const string& calib_file);   // PINHOLE or MEI section of the configuration file (host/yaml_config.h)
     void rejectWithF();
     void undistortedPoints();
     // the two halves of readImage around the library call (public for the order callback; not part of the reference's interface)
@@ -67,7 +73,7 @@ class FeatureTracker {
     vector<int> track_cnt;
     map<int, cv::Point2f> cur_un_pts_map;
     map<int, cv::Point2f> prev_un_pts_map;
-    PinholeModel m_camera;
+    CameraModel m_camera;
     double cur_time;
     double prev_time;
 
@@ -77,6 +83,8 @@ class FeatureTracker {
     vg_handle* vg_ = nullptr;      // owns the device-side pyramids of cur_img / forw_img
     int fe_capacity_ = 0;
     bool configured_ = false;
+    bool camera_sent_ = false;     // m_camera has gone to the stream that runs this tracker's frames (vg_fe_set_camera)
+    friend class FeatureTrackerBatch;
 };
 
 // S stand-alone trackers on ONE handle: readImages() is the loop of the reference's node over trackerData[i].readImage(...)

@@ -291,11 +291,26 @@ extern "C" int vins_host_read_parameters(const char* config_file, double* out /*
         k = 32;
         out[k++] = MAX_CNT; out[k++] = MIN_DIST; out[k++] = ROW; out[k++] = COL; out[k++] = FREQ; out[k++] = F_THRESHOLD; out[k++] = SHOW_TRACK;
         out[k++] = EQUALIZE; out[k++] = FISHEYE; out[k++] = FE_WINDOW_SIZE; out[k++] = FOCAL_LENGTH;
-        const double v[8] = {tr.m_camera.fx, tr.m_camera.fy, tr.m_camera.cx, tr.m_camera.cy, tr.m_camera.k1, tr.m_camera.k2, tr.m_camera.p1, tr.m_camera.p2};
-        memcpy(intr, v, sizeof(v));
+        memcpy(intr, tr.m_camera.p, sizeof(tr.m_camera.p));
         return 0;
     } catch (const std::exception& e) {
         fprintf(stderr, "vins_host_read_parameters: %s\n", e.what());
+        return -1;
+    }
+}
+// The camera FeatureTracker::readIntrinsicParameter reads: *model = VG_CAM_*, p8 = fx fy cx cy k1 k2 p1 p2 (MEI: gamma1 gamma2 u0 v0 ...),
+// *xi (MEI).  -1 when the file or its camera model is refused: vins_host_last_error() holds readIntrinsicParameter's message.
+static std::string g_last_error;
+extern "C" const char* vins_host_last_error() { return g_last_error.c_str(); }
+extern "C" int vins_host_read_camera(const char* config_file, int* model, double* p8, double* xi) {
+    try {
+        FeatureTracker tr;
+        tr.readIntrinsicParameter(config_file);
+        *model = tr.m_camera.model; *xi = tr.m_camera.xi;
+        memcpy(p8, tr.m_camera.p, sizeof(tr.m_camera.p));
+        return 0;
+    } catch (const std::exception& e) {
+        g_last_error = e.what();
         return -1;
     }
 }

@@ -1,8 +1,11 @@
 // replay_main.cpp — ROS-free replay harness for the drop-in classes (SURVEY.md 8(d) configs[0] substitute).
 //
-//   vins_replay fe <frames.bin> <out.txt>   frames.bin = int32 n, w, h, pub_every ; n * w*h bytes
+//   vins_replay fe <frames.bin> <out.txt> [config.yaml]   frames.bin = int32 n, w, h, pub_every ; n * w*h bytes
 //     feeds the frames through FeatureTracker::readImage exactly as img_callback does (feature_tracker_node.cpp:86-111:
 //     readImage, then updateID for every feature) and dumps, per frame, ids / cur_pts / track_cnt / cur_un_pts / velocity.
+//     With config.yaml the front-end parameters and the camera (model_type PINHOLE or MEI) come from that file, through
+//     readFeatureTrackerParameters and FeatureTracker::readIntrinsicParameter as in the node (feature_tracker_node.cpp:205-208);
+//     without it: the built-in EuRoC values.  `fe_batch <list.txt> <out_prefix> [config.yaml]` takes the same argument for all streams.
 //
 //   vins_replay ba <sequence.bin> <out.csv>
 //     N consecutive sliding windows through the drop-in Estimator the way process() drives it once the system is
@@ -37,7 +40,14 @@
 #include "feature_tracker.h"
 #include "resident_estimator.h"
 
-static int replay_fe(const char* in, const char* out) {
+// the front-end globals of a configuration file; the frames of the replay must have its image size, and there is no fisheye mask here
+static void replay_fe_config(const char* config, int w, int h) {
+    readFeatureTrackerParameters(config);
+    if (COL != w || ROW != h) throw std::runtime_error("the configuration file's image size differs from the frames'");
+    if (FISHEYE) throw std::runtime_error("fisheye: 1 needs the mask image, which the replay does not load");
+}
+
+static int replay_fe(const char* in, const char* out, const char* config) {
     FILE* f = fopen(in, "rb");
     if (!f) { perror("frames"); return 2; }
     int hdr[4];
@@ -46,6 +56,10 @@ static int replay_fe(const char* in, const char* out) {
     COL = w; ROW = h;
     std::vector<unsigned char> buf((size_t)w * h);
     FeatureTracker tracker;
+    if (config) {
+        replay_fe_config(config, w, h);
+        tracker.readIntrinsicParameter(config);
+    }
     FILE* o = fopen(out, "w");
     for (int k = 0; k < n; ++k) {
         if (fread(buf.data(), 1, buf.size(), f) != buf.size()) return 2;
@@ -65,7 +79,7 @@ static int replay_fe(const char* in, const char* out) {
 
 // `fe` for S streams advancing together on one handle (FeatureTrackerBatch): list.txt names S files of the `fe` input format with the
 // same size, frame count and pub_every; stream c's lines go to <out_prefix><c>.txt in the `fe` output format
-static int replay_fe_batch(const char* list, const char* out_prefix) {
+static int replay_fe_batch(const char* list, const char* out_prefix, const char* config) {
     std::vector<std::string> names;
     {
         FILE* l = fopen(list, "r");
@@ -98,6 +112,10 @@ static int replay_fe_batch(const char* list, const char* out_prefix) {
     COL = w; ROW = h;
     std::vector<std::vector<unsigned char>> buf((size_t)S, std::vector<unsigned char>((size_t)w * h));
     FeatureTrackerBatch batch(S);
+    if (config) {
+        replay_fe_config(config, w, h);
+        for (int c = 0; c < S; ++c) batch.trackers[c].readIntrinsicParameter(config);
+    }
     std::vector<cv::Mat> imgs;
     std::vector<double> stamps((size_t)S);
     for (int k = 0; k < n; ++k) {
@@ -421,9 +439,12 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
 }
 
 int main(int argc, char** argv) {
-    if (argc >= 4 && !strcmp(argv[1], "fe")) return replay_fe(argv[2], argv[3]);
+    if (argc >= 4 && !strcmp(argv[1], "fe")) {
+        try { return replay_fe(argv[2], argv[3], argc >= 5 ? argv[4] : nullptr); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay fe: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "fe_batch")) {
-        try { return replay_fe_batch(argv[2], argv[3]); }
+        try { return replay_fe_batch(argv[2], argv[3], argc >= 5 ? argv[4] : nullptr); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay fe_batch: %s\n", e.what()); return 1; }
     }
     if (argc >= 4 && !strcmp(argv[1], "ba")) {
@@ -438,6 +459,6 @@ int main(int argc, char** argv) {
         try { return replay_seq(argv[2], argv[4], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay vio: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> | vins_replay fe_batch <list.txt> <out_prefix> | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv>\n");
     return 2;
 }
