@@ -571,8 +571,13 @@ int vg_fe_get_mask(vg_handle* h, int cam, uint8_t* out);          /* current dev
  * Two cases go back to the host inside the call (same results, more round trips): 8 <= survivors < 15 (findFundamentalMat switches to
  * LMedS) and a RANSAC sample OpenCV would have redrawn for collinearity (its schedule then depends on the points).
  * All pointers of vg_fe_frame_out point into pinned buffers of the handle and stay valid until the next vg_fe_* call on it.
- * The FIRST call on a stream builds its resident tables (RANSAC schedules for every point count up to max_points: 28 KB each, tens of
- * milliseconds of host time once); limits: n_cams == 1, max_points <= 2048, rejectWithF on at most 1024 tracking survivors. */
+ * This call IS vg_fe_read_image_batch (below) with one stream: one implementation, one resident state per handle, so the two calls may
+ * be mixed on a handle with n_cams == 1.  What it keeps of its own: img == NULL is VG_ERR_BAD_ARG (the batch reads that as "the resident
+ * frames"), a handle with n_cams != 1 is VG_ERR_UNSUPPORTED, and all 1000 RANSAC iterations are evaluated in one launch per step.
+ * The FIRST call on a handle builds its resident tables: the RANSAC schedules for every point count up to max_points (28 KB each, tens
+ * of milliseconds of host time once) and the per-stream tables of the batch (about 0.45 MB of device memory per stream: the models,
+ * inlier counts and inlier sets of all iterations; a few tens of KB before the two calls were one).  Limits: n_cams == 1,
+ * max_points <= 2048, rejectWithF on at most 1024 tracking survivors. */
 typedef struct vg_fe_frame_out {
     int n1;                      /* survivors of tracking + border test                                           (:115-124) */
     int n2;                      /* survivors of rejectWithF (== n1 when it did not run)                          (:193-198) */
@@ -619,11 +624,12 @@ int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* ou
 
 /* ---- The same for EVERY stream of a handle in one call (added within ABI 12): readImage of in[c] for stream c of a handle configured
  * with n_cams == n_streams (any other n_streams: VG_ERR_BAD_ARG; the batched streams advance together), out[c] with exactly the
- * meaning, the values and the lifetime of the single call's result for that stream.  One upload, one launch per step over all streams
- * (tracking, image build, stamping and detection are indexed by stream; the steps between them run one workgroup per stream; the
- * RANSAC of all streams runs in two parts around the iteration bookkeeping instead of 1000 iterations per stream), one download after
- * rejectWithF, one after the detection.  When to use which: one camera -> vg_fe_read_image (lowest latency); many cameras or many
- * sequences replayed together -> one handle with n_cams streams and this call.
+ * meaning, the values and the lifetime of the single call's result for that stream -- the single call is this one with n_streams == 1.
+ * One upload, one launch per step over all streams (tracking, image build, stamping and detection are indexed by stream; the steps
+ * between them run one workgroup per stream; with more than one stream the RANSAC runs in two parts around the iteration bookkeeping
+ * instead of 1000 iterations per stream), one download after rejectWithF, one after the detection.  When to use which: one camera ->
+ * vg_fe_read_image (lowest latency: one launch per RANSAC step); many cameras or many sequences replayed together -> one handle with
+ * n_cams streams and this call.
  *   per stream  (from in[c]):  img / stride, cur_xy / n, publish, max_cnt, intr, focal_length, f_threshold, base_mask, order / user.
  *               Streams that publish and streams that do not may be mixed; one that does not costs the detection an early exit.
  *               The camera is per stream too (vg_fe_set_camera, else the pinhole of in[c].intr): streams of different models may
@@ -634,7 +640,7 @@ int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* ou
  *               uploaded; benchmarks time the device work this way).  Some NULL, some not: VG_ERR_BAD_ARG.
  *   walk order  after rejectWithF of all streams ONE download, then the `order` callbacks on the calling thread in ascending stream
  *               order (streams that publish, have n2 > 0 and a callback), then ONE upload of all orders.
- *   host cases  8 <= survivors < 15 (LMedS) and a sample OpenCV would have redrawn go back to the host per stream, as in the single call.
+ *   host cases  8 <= survivors < 15 (LMedS) and a sample OpenCV would have redrawn go back to the host per stream.
  * Failure semantics as for the single call: everything that follows from the arguments alone (sizes, a point list on a handle without
  * a previous frame, mixed uniform fields, n_streams, frames for some streams only) is refused BEFORE any frame is uploaded and no stream
  * has moved; an error after that (a callback's, a detection overflow, a HIP error) leaves ALL streams one frame ahead of the caller,

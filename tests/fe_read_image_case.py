@@ -11,6 +11,9 @@ and lifted points are required, on streams chosen to reach every branch of the c
   no-callback  order == NULL walks the list as it stands = the callback returning the identity
   fisheye      a base mask under setMask
 
+run_alternating(): vg_fe_read_image and vg_fe_read_image_batch(n_streams = 1) share one implementation and one resident state; a handle
+that is driven by both in turn must give what a handle driven by vg_fe_read_image alone gives.
+
 Used by tests/test_fe_read_image.py under the emulator (`not gpu`) and on the device (`gpu`)."""
 import numpy as np
 
@@ -155,4 +158,43 @@ def run(handle_a, handle_b, W=320, H=240, n_frames=7):
     stream("collinear", frames[:3], plain, 70, md(10), False, first_pts=grid, pub=lambda k: True)
     # points that all leave the image / fail: nothing survives the tracking on a published frame
     stream("none", frames[:2], intr, 30, md(20), False, first_pts=np.array([[0.2, 0.3], [W - 0.6, H - 0.7], [0.4, H - 0.8]], np.float32), pub=lambda k: True)
+    return seen
+
+
+def run_alternating(handle_a, handle_b, W=320, H=240):
+    """One n_cams == 1 handle on which vg_fe_read_image and vg_fe_read_image_batch(n_streams = 1) take turns frame by frame -- both work on
+    the one resident state of the handle -- against a second handle driven by vg_fe_read_image alone: every field of every output, bit for
+    bit (fe_read_image_batch_case.same_all).  Five frames, published on 0, 2 and 4, an order callback on the stream.  With strict turns a
+    pass has all its published frames under one entry point, so there are two passes: the single call first (it publishes), then the
+    batched call first.  Returns what was seen; the preconditions that keep the comparison from being vacuous are asserted here."""
+    import fe_read_image_batch_case as B
+    cap, n_frames, max_cnt, min_dist = 64, 5, 50, 14
+    frames = fe_scene.moving_scene(n_frames, seed=4, width=W, height=H, velocity=(3.1, -1.4))
+    pub = lambda k: k % 2 == 0
+    kw = dict(max_cnt=max_cnt, min_dist=min_dist, equalize=True)
+    # the reference: vg_fe_read_image alone (computed once, both passes are held to it)
+    alone = B.Stream("alone", frames, INTR, max_cnt, pub)
+    want = B.run_single(handle_b, W, H, cap, alone, min_dist, n_frames)
+    seen = dict(published_device_ransac={}, unpublished_tracked=0)
+    for first in ("single", "batch"):
+        tr = fe.FrontEnd(handle_a, W, H, 1, cap)
+        mixed = B.Stream("mixed", frames, INTR, max_cnt, pub)
+        for k in range(n_frames):
+            img, pts, publish = mixed.begin(k)
+            call = ("single", "batch")[(k + (first == "batch")) % 2]
+            if call == "single":
+                got = tr.read_image(img, pts, publish, INTR, order=mixed.order(), **kw)
+            else:
+                got = tr.read_image_batch([img], [pts], [publish], [INTR], orders=[mixed.order()], **kw)[0]
+            wpts, wpub, w = want[k]
+            assert wpub == publish and np.array_equal(wpts.view(np.uint32), pts.view(np.uint32)), (first, k, "inputs")
+            B.same_all(got, w, ("alternating", first, k, call))
+            mixed.advance(got, publish)
+            if publish and got["ransac_ran"] and got["fallback"] == 0:
+                seen["published_device_ransac"][call] = seen["published_device_ransac"].get(call, 0) + 1
+            if not publish and got["n1"] > 0:
+                seen["unpublished_tracked"] += 1
+    # the device estimate ran, to its end, under either entry point; a frame that ends after the tracking had points to lift
+    assert seen["published_device_ransac"].get("single", 0) >= 1 and seen["published_device_ransac"].get("batch", 0) >= 1, seen
+    assert seen["unpublished_tracked"] >= 1, seen
     return seen

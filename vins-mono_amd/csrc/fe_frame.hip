@@ -1,17 +1,17 @@
 // fe_frame.hip — what FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:81-167) does BETWEEN its OpenCV calls, on
-// the device, so that vg_fe_read_image (fe_host.hip) runs a frame without handing intermediate results to the host:
-//   :115-124  status[i] && inBorder(forw_pts[i]) + reduceVector        -> fe_ri_after_lk_kernel (ordered compaction = reduceVector)
-//   :175-188  liftProjective of cur_pts / forw_pts for findFundamentalMat -> the same kernel (the stream's camera, double, reference order)
-//   :191-198  the registrator's sequential bookkeeping over the RANSAC iterations + reduceVector by its mask -> fe_ri_pick_kernel
-//   :36-69    setMask's walk in the order the host's sort produced     -> fe_ri_setmask_kernel (+ fe_stamp_kernel of fe_kernels.hip)
-//   :144      n_max_cnt = MAX_CNT - forw_pts.size()                    -> written by the same kernel where fe_select_kernel reads it
-//   :71-79, :258-268  addPoints + undistortedPoints (liftProjective of the final list) -> fe_ri_finish_kernel
-// All of them are single-workgroup kernels on <= a few hundred points: what matters is that they need no round trip, not their
-// arithmetic.  Compiled with -ffp-contract=off: the lifting (fe_camera.h) evaluates the reference's double expressions as written.
+// the device, so that vg_fe_read_image / vg_fe_read_image_batch (fe_host.hip) run a frame without handing intermediate results to the
+// host.  The work on ONE stream is a body (ri_*_body) over the stream's view RiDev:
+//   :115-124  status[i] && inBorder(forw_pts[i]) + reduceVector        -> ri_after_lk_body (ordered compaction = reduceVector)
+//   :175-188  liftProjective of cur_pts / forw_pts for findFundamentalMat -> the same body (the stream's camera, double, reference order)
+//   :191-198  the registrator's sequential bookkeeping over the RANSAC iterations + reduceVector by its mask -> ri_pick_body
+//   :36-69    setMask's walk in the order the host's sort produced     -> ri_setmask_body (+ fe_stamp_kernel of fe_kernels.hip)
+//   :144      n_max_cnt = MAX_CNT - forw_pts.size()                    -> written by the same body where fe_select_kernel reads it
+//   :71-79, :258-268  addPoints + undistortedPoints (liftProjective of the final list) -> ri_finish_body
+// All of them work on <= a few hundred points: what matters is that they need no round trip, not their arithmetic.  Compiled with
+// -ffp-contract=off: the lifting (fe_camera.h) evaluates the reference's double expressions as written.
 //
-// vg_fe_read_image_batch runs the same frame for every stream of a handle: the fe_rb_* kernels at the end of this file have one
-// workgroup (the walk: one wavefront) PER STREAM, rebuild the stream's RiDev from the device tables of RbDev and run the very bodies
-// (ri_*_body) the single-stream kernels run.
+// The kernels (fe_rb_*, at the end of this file) run the frame for the S streams of a handle -- S = 1 is vg_fe_read_image: one
+// workgroup (the walk: one wavefront) PER STREAM, which rebuilds the stream's RiDev from the device tables of RbDev and runs the body.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vg_target.h"
@@ -96,24 +96,20 @@ FDEV void ri_after_lk_body(const FeDev& d, const RiDev& r, int* wsum) {
         }
     }
 }
-extern "C" __global__ __launch_bounds__(256) void fe_ri_after_lk_kernel(FeDev d, RiDev r) {
-    __shared__ int wsum[4];
-    ri_after_lk_body(d, r, wsum);
-}
 
-// After fe_ransac7_kernel / fe_ransac_count_kernel: the registrator's loop over the iterations (ptsetreg.cpp RANSACPointSetRegistrator::run
+// After fe_rb_ransac7_kernel / fe_rb_count_kernel: the registrator's loop over the iterations (ptsetreg.cpp RANSACPointSetRegistrator::run
 // as restated in fe_ransac.hip: a model replaces the best one if it has more inliers than max(best, 6); after every improvement the
 // iteration bound shrinks to RANSACUpdateNumIters(...), read from the host-made table; iterations at or beyond the bound do not
 // count), then the mask of the winning model and reduceVector by it.  One workgroup; the loop itself runs on one wavefront with the
 // counts of 64 iterations in a register each (v_readlane in sequence: the bound usually ends the loop inside the first chunk).
-// The batched call runs the loop in two parts with RANSAC work between them: iterations [it0, stop) per part, the state (bound, best
-// count, best iteration) carried in ctl; `final`: the last part, which also makes the mask.  The single call: (0, FE_RANSAC_MAXIT, true).
+// More than one stream: the loop runs in two parts with RANSAC work between them, iterations [it0, stop) per part, the state (bound,
+// best count, best iteration) carried in ctl; `final`: the last part, which also makes the mask.  One stream: (0, FE_RANSAC_MAXIT, true).
 FDEV void ri_pick_body(const RiDev& r, const int it0, const int stop, const bool final, int* wsum, int& sbest) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int n1 = r.ctl[RI_N1];
     if (r.ctl[RI_PUBLISH] == 0 || r.ctl[RI_RANSAC] == 0) return;
     int fb = r.ctl[RI_FALLBACK];
-    if (fb & (RI_FB_LMEDS | RI_FB_RANGE)) return;                   // (header already written by fe_ri_after_lk_kernel)
+    if (fb & (RI_FB_LMEDS | RI_FB_RANGE)) return;                   // (header already written by ri_after_lk_body)
     if (tid < 64) {
         int niters = FE_RANSAC_MAXIT, max_good = 0, best = -1;
         if (it0 > 0) { niters = r.ctl[RI_NITERS]; max_good = r.ctl[RI_MAXGOOD]; best = r.ctl[RI_BEST]; }
@@ -147,11 +143,6 @@ FDEV void ri_pick_body(const RiDev& r, const int it0, const int stop, const bool
         r.a_hdr[RI_N] = r.ctl[RI_N]; r.a_hdr[RI_PUBLISH] = 1; r.a_hdr[RI_N1] = n1; r.a_hdr[RI_N2] = n2; r.a_hdr[RI_FALLBACK] = fb;
         r.a_hdr[RI_RANSAC] = 1; r.a_hdr[RI_BEST] = best; r.a_hdr[RI_NITERS] = r.ctl[RI_NITERS];
     }
-}
-extern "C" __global__ __launch_bounds__(256) void fe_ri_pick_kernel(RiDev r) {
-    __shared__ int wsum[4];
-    __shared__ int sbest;
-    ri_pick_body(r, 0, FE_RANSAC_MAXIT, true, wsum, sbest);
 }
 
 // setMask (:36-69) in a given order: position q of the walk is survivor order[q] (order == nullptr: the list as it stands).  A point is
@@ -208,10 +199,6 @@ FDEV void ri_setmask_body(const FeDev& d, const RiDev& r, short* kx, short* ky) 
         const_cast<int*>(d.max_corners)[0] = room > 0 ? (room < d.max_pts ? room : d.max_pts) : 0;
     }
 }
-extern "C" __global__ __launch_bounds__(64) void fe_ri_setmask_kernel(FeDev d, RiDev r) {
-    __shared__ short kx[RI_SETMASK_MAX], ky[RI_SETMASK_MAX];
-    ri_setmask_body(d, r, kx, ky);
-}
 
 // addPoints (:71-79) + undistortedPoints (:262-267): the list the frame ends with = the kept points in the walk's order, then the new
 // corners; every point lifted.
@@ -237,13 +224,10 @@ FDEV void ri_finish_body(const FeDev& d, const RiDev& r) {
         r.b_hdr[RI_NK] = nk; r.b_hdr[RI_NNEW] = nc; r.b_hdr[RI_N2] = r.ctl[RI_N2];
     }
 }
-extern "C" __global__ __launch_bounds__(256) void fe_ri_finish_kernel(FeDev d, RiDev r) {
-    ri_finish_body(d, r);
-}
 
-// ================================================================================================ vg_fe_read_image_batch
-// Stream c of the batch as the single call sees a stream: its slices of the per-stream arrays of FeDev (next_xy, status, corners, the
-// detection's counters) and an RiDev made from the tables.  Everything here is uniform over the workgroup.
+// ================================================================================================ the kernels: a workgroup per stream
+// Stream c as the bodies see a stream: its slices of the per-stream arrays of FeDev (next_xy, status, corners, the detection's
+// counters) and an RiDev made from the tables.  Everything here is uniform over the workgroup.
 FDEV void rb_stream(const RbDev& b, const int c, FeDev& d, RiDev& r) {
     const size_t cap = (size_t)b.cap, mp = (size_t)d.max_pts;
     d.next_xy += c * mp * 2; d.status += c * mp; d.corners += c * mp * 2; d.max_corners += c; d.ncorners += c;
@@ -265,7 +249,7 @@ FDEV void rb_stream(const RbDev& b, const int c, FeDev& d, RiDev& r) {
     r.base_mask = (b.base && k.has_base) ? b.base + (size_t)c * d.W * d.H : nullptr;
 }
 
-// grid (S), 256 threads.  Besides the single call's work: every stream starts the frame with no kept point and NO detection (a
+// grid (S), 256 threads.  Besides the body: every stream starts the frame with no kept point and NO detection (a
 // negative corner budget: fe_mineig_kernel / fe_select_kernel leave at once); fe_rb_setmask_kernel sets both for the streams that publish.
 extern "C" __global__ __launch_bounds__(256) void fe_rb_after_lk_kernel(FeDev d, RbDev b) {
     __shared__ int wsum[4];
@@ -275,14 +259,13 @@ extern "C" __global__ __launch_bounds__(256) void fe_rb_after_lk_kernel(FeDev d,
     if (threadIdx.x == 0) { b.nk[c] = 0; const_cast<int*>(d.max_corners)[0] = -1; }
     ri_after_lk_body(d, r, wsum);
 }
-// grid (S), 256 threads; part 0: iterations [0, RB_CHUNK0), part 1: the rest and the mask
-extern "C" __global__ __launch_bounds__(256) void fe_rb_pick_kernel(FeDev d, RbDev b, int part) {
+// grid (S), 256 threads; the bookkeeping over iterations [first, end) (fe_ransac.hip); the part that ends at FE_RANSAC_MAXIT makes the mask
+extern "C" __global__ __launch_bounds__(256) void fe_rb_pick_kernel(FeDev d, RbDev b, int first, int end) {
     __shared__ int wsum[4];
     __shared__ int sbest;
     RiDev r;
     rb_stream(b, blockIdx.x, d, r);
-    if (part == 0) ri_pick_body(r, 0, RB_CHUNK0, false, wsum, sbest);
-    else ri_pick_body(r, RB_CHUNK0, FE_RANSAC_MAXIT, true, wsum, sbest);
+    ri_pick_body(r, first, end, end >= FE_RANSAC_MAXIT, wsum, sbest);
 }
 // grid (S), one wavefront
 extern "C" __global__ __launch_bounds__(64) void fe_rb_setmask_kernel(FeDev d, RbDev b) {

@@ -34,46 +34,18 @@ __global__ void fe_setmask_kernel(FeDev d, const float* pts_xy, const int* track
                                   int radius, int* kept_index, int* n_kept, int* kept_xy);
 __global__ void fe_stamp_kernel(FeDev d, const int* n_kept, const int* kept_xy, int radius);
 __global__ void fe_lift_kernel(const float* pts_xy, int n, FeCamera cam, float* out_xy);
-// vg_fe_read_image (fe_frame.hip, fe_ransac.hip)
-__global__ void fe_ri_after_lk_kernel(FeDev d, RiDev r);
-__global__ void fe_ri_pick_kernel(RiDev r);
-__global__ void fe_ri_setmask_kernel(FeDev d, RiDev r);
-__global__ void fe_ri_finish_kernel(FeDev d, RiDev r);
-__global__ void fe_ransac7_kernel(const float* p1, const float* p2, int n, const int* sched, int nsched, double* models, int* ctl);
-__global__ void fe_ransac_count_kernel(const float* p1, const float* p2, int n, float thresh2, int lmeds, const double* models, int nsched,
-                                       double* Fout, int* count, double* median, unsigned long long* inl_words, const int* ctl);
-// vg_fe_read_image_batch (fe_frame.hip, fe_ransac.hip)
+// vg_fe_read_image / vg_fe_read_image_batch (fe_frame.hip, fe_ransac.hip)
 __global__ void fe_rb_after_lk_kernel(FeDev d, RbDev b);
-__global__ void fe_rb_pick_kernel(FeDev d, RbDev b, int part);
+__global__ void fe_rb_pick_kernel(FeDev d, RbDev b, int first, int end);
 __global__ void fe_rb_setmask_kernel(FeDev d, RbDev b);
 __global__ void fe_rb_finish_kernel(FeDev d, RbDev b);
-__global__ void fe_rb_ransac7_kernel(RbDev b, const int* sched, int part);
-__global__ void fe_rb_count_kernel(RbDev b, int part);
+__global__ void fe_rb_ransac7_kernel(RbDev b, const int* sched, int first, int end);
+__global__ void fe_rb_count_kernel(RbDev b, int first, int end);
 }
-hipError_t fe_ransac_buffers(vg_handle* h, FeRansacBufs* b);
 void fe_ransac_tables(int nmax, std::vector<int>& sched, std::vector<int>& niters, int stride);
 
-// resident state of vg_fe_read_image: device arrays (one allocation), their pinned host mirrors, the RANSAC tables
-struct RiState {
-    int cap = 0;
-    char* dev = nullptr;
-    char* host = nullptr;              // pinned: [input block | block A | block B | order]
-    size_t in_bytes = 0, a_bytes = 0, b_bytes = 0;
-    char *d_in = nullptr, *d_a = nullptr, *d_b = nullptr;
-    int *d_order = nullptr, *d_sched = nullptr, *d_tab = nullptr;
-    uint8_t* d_base = nullptr;         // copy of the caller's fisheye mask
-    const uint8_t* base_src = nullptr;
-    RiDev r;
-};
-static void ri_free(RiState* q) {
-    if (!q) return;
-    (void)hipFree(q->dev); (void)hipFree(q->d_sched); (void)hipFree(q->d_tab); (void)hipFree(q->d_base);
-    (void)hipHostFree(q->host);
-    delete q;
-}
-
-// resident state of vg_fe_read_image_batch: the tables of RbDev for every stream of the handle (one device allocation), the pinned
-// mirrors of what travels ([input | block A | lifted survivors | block B | orders]), the RANSAC tables
+// resident state of vg_fe_read_image / vg_fe_read_image_batch: the tables of RbDev for every stream of the handle (one device
+// allocation), the pinned mirrors of what travels ([input | block A | lifted survivors | block B | orders]), the RANSAC tables
 struct RbState {
     char* dev = nullptr;
     char* host = nullptr;
@@ -83,6 +55,7 @@ struct RbState {
     int *d_sched = nullptr, *d_tab = nullptr;
     uint8_t* d_base = nullptr;                        // [S][H][W] copies of the callers' fisheye masks
     std::vector<const uint8_t*> base_src;
+    bool ord_flags_set = false;                       // a walk-order flag on the device is 1 (all zero: the next frame without orders uploads none)
     RbDev b;
 };
 static void rb_free(RbState* q) {
@@ -128,7 +101,6 @@ struct FeState {
     std::vector<char> pushed_once;
     std::vector<FeCamera> cam;       // [cams] vg_fe_set_camera; cam_set[c] == 0: the pinhole of vg_fe_frame_in::intr
     std::vector<char> cam_set;
-    RiState* ri = nullptr;
     RbState* rb = nullptr;
 };
 
@@ -141,7 +113,6 @@ extern "C" void fe_state_destroy(FeState* s) {
     (void)hipFree(s->ncorners); (void)hipFree(s->ncand); (void)hipFree(s->keys);
     (void)hipFree(s->sm_pts); (void)hipFree(s->sm_cnt); (void)hipFree(s->sm_n); (void)hipFree(s->sm_kidx); (void)hipFree(s->sm_nk);
     (void)hipFree(s->sm_kxy); (void)hipFree(s->sm_base); (void)hipFree((void*)s->sm_base_ptrs); (void)hipFree(s->lift_in); (void)hipFree(s->lift_out);
-    ri_free(s->ri);
     rb_free(s->rb);
     delete s;
 }
@@ -235,13 +206,16 @@ extern "C" int vg_fe_configure(vg_handle* h, int width, int height, int n_cams, 
     return VG_OK;
 }
 
-static int fe_upload_async(vg_handle* h, const uint8_t* const* imgs, int stride) {
+// the frames of all streams into the slot of the next build; `strides`: the row pitch per stream, or NULL = `stride` for every stream
+static int fe_upload_async(vg_handle* h, const uint8_t* const* imgs, int stride, const int* strides = nullptr) {
     if (!h || !h->fe || !imgs) return VG_ERR_BAD_ARG;
     FeState* s = h->fe;
     const size_t npix = (size_t)s->W * s->H;
+    auto pitch = [&](int c) { return strides ? strides[c] : stride; };
     for (int c = 0; c < s->cams; ++c)                 // validate before touching any state
         if (!imgs[c]) { h->err = "vg_fe_upload_frames: every stream needs a frame (batched streams advance together)"; return VG_ERR_BAD_ARG; }
-    if (stride < s->W) { h->err = "vg_fe_upload_frames: stride smaller than the frame width"; return VG_ERR_BAD_ARG; }
+    for (int c = 0; c < s->cams; ++c)
+        if (pitch(c) < s->W) { h->err = "vg_fe_upload_frames: stride smaller than the frame width"; return VG_ERR_BAD_ARG; }
     // into the frame slot of the pyramid set the next build fills (set k <-> slot k): never the slot the CURRENT pyramid may be
     // using as its level 0 -- that image is the "previous" one of the next tracking step
     s->raw_sel = s->flip ^ 1;
@@ -251,15 +225,15 @@ static int fe_upload_async(vg_handle* h, const uint8_t* const* imgs, int stride)
     // sets); upload -> track is refused until a build has run.
     s->prev_clobbered = s->have_prev && s->alias_on[s->flip ^ 1];
     // frames that follow each other in memory without padding (one buffer for all streams: a ring of a capture driver, the bench's
-    // staging area) travel as ONE copy; otherwise one copy per stream (2-D when the rows are padded)
-    bool contiguous = stride == s->W;
-    for (int c = 1; c < s->cams && contiguous; ++c) contiguous = imgs[c] == imgs[c - 1] + npix;
+    // staging area) travel as ONE copy; otherwise one copy per stream (2-D when its rows are padded)
+    bool contiguous = true;
+    for (int c = 0; c < s->cams && contiguous; ++c) contiguous = pitch(c) == s->W && (c == 0 || imgs[c] == imgs[c - 1] + npix);
     if (contiguous) {
         HIPCHK(h, hipMemcpyAsync(s->raw2[s->raw_sel], imgs[0], npix * s->cams, hipMemcpyHostToDevice, h->stream));
     } else {
         for (int c = 0; c < s->cams; ++c) {
-            if (stride == s->W) HIPCHK(h, hipMemcpyAsync(s->raw2[s->raw_sel] + (size_t)c * npix, imgs[c], npix, hipMemcpyHostToDevice, h->stream));
-            else HIPCHK(h, hipMemcpy2DAsync(s->raw2[s->raw_sel] + (size_t)c * npix, s->W, imgs[c], stride, s->W, s->H, hipMemcpyHostToDevice, h->stream));
+            if (pitch(c) == s->W) HIPCHK(h, hipMemcpyAsync(s->raw2[s->raw_sel] + (size_t)c * npix, imgs[c], npix, hipMemcpyHostToDevice, h->stream));
+            else HIPCHK(h, hipMemcpy2DAsync(s->raw2[s->raw_sel] + (size_t)c * npix, s->W, imgs[c], pitch(c), s->W, s->H, hipMemcpyHostToDevice, h->stream));
         }
     }
     return VG_OK;
@@ -284,13 +258,19 @@ extern "C" int vg_fe_select_frames(vg_handle* h, int slot) {
     return VG_OK;
 }
 
+// why the frames of this handle cannot be equalized, or nullptr
+static const char* fe_clahe_refusal(const FeDev& d) {
+    if (d.W % 8 || d.H % 8) return "CLAHE needs width and height divisible by 8";
+    // (fe_clahe_apply_kernel lays the interpolation cells of a row over the 256 threads of a workgroup: W / 8 / 4 + 3 of them)
+    if (d.W / 8 / 4 + 3 > 256) return "CLAHE: frame wider than the interpolation-cell tiling (W / 32 + 3 > 256)";
+    return nullptr;
+}
+
 extern "C" int vg_fe_build_async(vg_handle* h, int equalize) {
     VG_RANGE("vg_fe_build_async");
     if (!h || !h->fe) return VG_ERR_BAD_ARG;
     FeState* s = h->fe;
-    if (equalize && (s->d.W % 8 || s->d.H % 8)) { h->err = "CLAHE needs width and height divisible by 8"; return VG_ERR_UNSUPPORTED; }
-    // (fe_clahe_apply_kernel lays the interpolation cells of a row over the 256 threads of a workgroup: W / 8 / 4 + 3 of them)
-    if (equalize && s->d.W / 8 / 4 + 3 > 256) { h->err = "CLAHE: frame wider than the interpolation-cell tiling (W / 32 + 3 > 256)"; return VG_ERR_UNSUPPORTED; }
+    if (const char* why = equalize ? fe_clahe_refusal(s->d) : nullptr) { h->err = why; return VG_ERR_UNSUPPORTED; }
     const bool first = !s->have_prev;
     s->prev_clobbered = false;
     s->flip ^= 1;                                     // previous <- current (only after the arguments are known to be valid)
@@ -419,20 +399,32 @@ extern "C" int vg_fe_detect_upload(vg_handle* h, const uint8_t* const* masks, co
     return VG_OK;
 }
 
-extern "C" int vg_fe_detect_async(vg_handle* h, double quality, double min_dist) {
-    VG_RANGE("vg_fe_detect_async");
-    if (!h || !h->fe) return VG_ERR_BAD_ARG;
-    FeState* s = h->fe;
-    const FeDev& d = s->d;
+static const char* const FE_CAND_OVERFLOW = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)";
+
+// the min-distance cell grid of the detection holds FE_MAX_CELLS cells
+static int fe_cell_grid_check(vg_handle* h, const FeDev& d, double min_dist) {
     const int cell = (int)std::lrint(min_dist) < 1 ? 1 : (int)std::lrint(min_dist);
     if (((d.W + cell - 1) / cell) * ((d.H + cell - 1) / cell) > FE_MAX_CELLS) { h->err = "min_dist too small for the cell grid"; return VG_ERR_UNSUPPORTED; }
-    HIPCHK(h, hipMemsetAsync(s->ncand, 0, sizeof(unsigned) * FE_CNT_STRIDE * d.cams, h->stream));
+    return VG_OK;
+}
+
+// goodFeaturesToTrack of every stream of `d` (max_corners and the mask are on the device)
+static int fe_detect_launch(vg_handle* h, const FeDev& d, double quality, double min_dist) {
+    const int rc = fe_cell_grid_check(h, d, min_dist);
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(d.ncand, 0, sizeof(unsigned) * FE_CNT_STRIDE * d.cams, h->stream));
     // min-eigenvalue map + candidates in one kernel (64 x 16 tiles), then the exact threshold, the sort and the min-distance walk
     const dim3 g((d.W + 63) / 64, (d.H + 15) / 16, d.cams);
     hipLaunchKernelGGL(fe_mineig_kernel, g, dim3(256), 0, h->stream, d, quality);
     HIPCHK(h, fe_launch_select(d, quality, (float)min_dist, h->stream));
     HIPCHK(h, hipGetLastError());
     return VG_OK;
+}
+
+extern "C" int vg_fe_detect_async(vg_handle* h, double quality, double min_dist) {
+    VG_RANGE("vg_fe_detect_async");
+    if (!h || !h->fe) return VG_ERR_BAD_ARG;
+    return fe_detect_launch(h, h->fe->d, quality, min_dist);
 }
 
 extern "C" int vg_fe_detect_download(vg_handle* h, float* out_xy, int* out_n) {
@@ -442,7 +434,24 @@ extern "C" int vg_fe_detect_download(vg_handle* h, float* out_xy, int* out_n) {
     HIPCHK(h, hipMemcpyAsync(out_n, s->ncorners, sizeof(int) * s->cams, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int c = 0; c < s->cams; ++c)
-        if (out_n[c] < 0) { out_n[c] = 0; h->err = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)"; return VG_ERR_UNSUPPORTED; }
+        if (out_n[c] < 0) { out_n[c] = 0; h->err = FE_CAND_OVERFLOW; return VG_ERR_UNSUPPORTED; }
+    return VG_OK;
+}
+
+// stream `cam` alone, with the mask that is on the device: run, read its count, report overflow, copy its n corners
+static int fe_detect_stream(vg_handle* h, int cam, int max_corners, double quality, double min_dist, float* out_xy, int* out_n) {
+    FeState* s = h->fe;
+    std::vector<int> mc(s->cams, 0);
+    mc[cam] = max_corners;
+    HIPCHK(h, hipMemcpyAsync(s->max_corners, mc.data(), sizeof(int) * s->cams, hipMemcpyHostToDevice, h->stream));
+    int rc = vg_fe_detect_async(h, quality, min_dist);
+    if (rc) return rc;
+    int n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, s->ncorners + cam, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (n < 0) { h->err = FE_CAND_OVERFLOW; return VG_ERR_UNSUPPORTED; }
+    if (n > 0) HIPCHK(h, hipMemcpy(out_xy, s->corners + (size_t)cam * s->max_pts * 2, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+    *out_n = n;
     return VG_OK;
 }
 
@@ -455,20 +464,9 @@ extern "C" int vg_fe_detect(vg_handle* h, int cam, const uint8_t* mask, int max_
     *out_n = 0;
     if (max_corners == 0) return VG_OK;
     const size_t npix = (size_t)s->W * s->H;
-    std::vector<int> mc(s->cams, 0);
-    mc[cam] = max_corners;
     if (mask) HIPCHK(h, hipMemcpyAsync(s->mask + (size_t)cam * npix, mask, npix, hipMemcpyHostToDevice, h->stream));
     else HIPCHK(h, hipMemsetAsync(s->mask + (size_t)cam * npix, 255, npix, h->stream));
-    HIPCHK(h, hipMemcpyAsync(s->max_corners, mc.data(), sizeof(int) * s->cams, hipMemcpyHostToDevice, h->stream));
-    int rc = vg_fe_detect_async(h, quality, min_dist);
-    if (rc) return rc;
-    int n = 0;
-    HIPCHK(h, hipMemcpyAsync(&n, s->ncorners + cam, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (n < 0) { h->err = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)"; return VG_ERR_UNSUPPORTED; }
-    if (n > 0) HIPCHK(h, hipMemcpy(out_xy, s->corners + (size_t)cam * s->max_pts * 2, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
-    *out_n = n;
-    return VG_OK;
+    return fe_detect_stream(h, cam, max_corners, quality, min_dist, out_xy, out_n);
 }
 
 // ---- FeatureTracker::setMask on the device (feature_tracker.cpp:36-69)
@@ -526,18 +524,7 @@ extern "C" int vg_fe_detect_masked(vg_handle* h, int cam, int max_corners, doubl
     FeState* s = h->fe;
     *out_n = 0;
     if (max_corners == 0) return VG_OK;
-    std::vector<int> mc(s->cams, 0);
-    mc[cam] = max_corners;
-    HIPCHK(h, hipMemcpyAsync(s->max_corners, mc.data(), sizeof(int) * s->cams, hipMemcpyHostToDevice, h->stream));
-    int rc = vg_fe_detect_async(h, quality, min_dist);
-    if (rc) return rc;
-    int n = 0;
-    HIPCHK(h, hipMemcpyAsync(&n, s->ncorners + cam, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (n < 0) { h->err = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)"; return VG_ERR_UNSUPPORTED; }
-    if (n > 0) HIPCHK(h, hipMemcpy(out_xy, s->corners + (size_t)cam * s->max_pts * 2, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
-    *out_n = n;
-    return VG_OK;
+    return fe_detect_stream(h, cam, max_corners, quality, min_dist, out_xy, out_n);
 }
 
 extern "C" int vg_fe_get_mask(vg_handle* h, int cam, uint8_t* out) {
@@ -655,192 +642,9 @@ extern "C" int vg_fe_get_eig(vg_handle* h, int cam, float* out) {
     return VG_OK;
 }
 
-// ================================================================================================ one call per frame
+// ================================================================================================ one call per frame, every stream
 static size_t ri_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static int ri_build(vg_handle* h, FeState* s, RiState* q);
-
-// (the state is attached to the stream only when it is complete: a failed allocation leaves nothing half-made behind)
-static int ri_ensure(vg_handle* h, FeState* s) {
-    if (s->ri) return VG_OK;
-    RiState* q = new RiState();
-    const int rc = ri_build(h, s, q);
-    if (rc != VG_OK) { ri_free(q); return rc; }
-    s->ri = q;
-    return VG_OK;
-}
-
-static int ri_build(vg_handle* h, FeState* s, RiState* q) {
-    const size_t cap = (size_t)s->max_pts;
-    q->cap = (int)cap;
-    // input block: control ints | cur_pts;  block A: header | status_lk | status_f | forw_xy | un_xy;  block B: header | kept | new_xy | un_xy
-    q->in_bytes = ri_up(sizeof(int) * RI_CTL_INTS + sizeof(float) * 2 * cap, 256);
-    const size_t a_st = 64, a_sf = a_st + ri_up(cap, 16), a_fw = a_sf + ri_up(cap, 16), a_un = a_fw + sizeof(float) * 2 * cap;
-    q->a_bytes = ri_up(a_un + sizeof(float) * 2 * cap, 256);
-    const size_t b_k = 64, b_nw = b_k + sizeof(int) * cap, b_un = b_nw + sizeof(float) * 2 * cap;
-    q->b_bytes = ri_up(b_un + sizeof(float) * 2 * cap, 256);
-    const size_t o_idx1 = q->in_bytes + q->a_bytes + q->b_bytes, o_idx2 = o_idx1 + sizeof(int) * cap, o_p1 = o_idx2 + sizeof(int) * cap;
-    const size_t o_p2 = o_p1 + sizeof(float) * 2 * cap, o_ord = o_p2 + sizeof(float) * 2 * cap, o_kxy = o_ord + sizeof(int) * cap;
-    const size_t total = o_kxy + sizeof(int) * 2 * cap;
-    HIPCHK(h, hipMalloc((void**)&q->dev, total));
-    HIPCHK(h, hipMemset(q->dev, 0, total));
-    HIPCHK(h, hipHostMalloc((void**)&q->host, q->in_bytes + q->a_bytes + q->b_bytes + sizeof(int) * cap, 0));
-    memset(q->host, 0, q->in_bytes + q->a_bytes + q->b_bytes + sizeof(int) * cap);
-    q->d_in = q->dev; q->d_a = q->dev + q->in_bytes; q->d_b = q->d_a + q->a_bytes;
-    q->d_order = (int*)(q->dev + o_ord);
-    RiDev& r = q->r;
-    memset(&r, 0, sizeof(r));
-    r.ctl = (int*)q->d_in; r.xy_in = (const float*)(q->d_in + sizeof(int) * RI_CTL_INTS); r.cap = (int)cap;
-    r.idx1 = (int*)(q->dev + o_idx1); r.idx2 = (int*)(q->dev + o_idx2); r.p1 = (float*)(q->dev + o_p1); r.p2 = (float*)(q->dev + o_p2);
-    r.kept_xy = (int*)(q->dev + o_kxy);
-    r.a_hdr = (int*)q->d_a; r.a_status_lk = (uint8_t*)(q->d_a + a_st); r.a_status_f = (uint8_t*)(q->d_a + a_sf);
-    r.a_forw_xy = (float*)(q->d_a + a_fw); r.a_un_xy = (float*)(q->d_a + a_un);
-    r.b_hdr = (int*)q->d_b; r.b_kept = (int*)(q->d_b + b_k); r.b_new_xy = (float*)(q->d_b + b_nw); r.b_un_xy = (float*)(q->d_b + b_un);
-    // the point-independent part of OpenCV's sample schedule and the iteration bounds, for every point count the stream can have
-    const int nmax = (int)std::min<size_t>(cap, FE_RANSAC_MAXPTS);
-    std::vector<int> sched, tab;
-    r.tab_stride = nmax + 1;
-    fe_ransac_tables(nmax, sched, tab, r.tab_stride);
-    HIPCHK(h, hipMalloc((void**)&q->d_sched, sizeof(int) * std::max<size_t>(sched.size(), 1)));
-    HIPCHK(h, hipMalloc((void**)&q->d_tab, sizeof(int) * tab.size()));
-    if (!sched.empty()) HIPCHK(h, hipMemcpy(q->d_sched, sched.data(), sizeof(int) * sched.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(q->d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    r.niters_tab = q->d_tab;
-    return VG_OK;
-}
-
-extern "C" int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
-    VG_RANGE("vg_fe_read_image");
-    if (!h || !h->fe || !in || !out || in->struct_size != (int)sizeof(vg_fe_frame_in) || !in->img || in->n < 0 || (in->n && !in->cur_xy))
-        return VG_ERR_BAD_ARG;
-    FeState* s = h->fe;
-    if (s->cams != 1) { h->err = "vg_fe_read_image: one stream per handle (vg_fe_configure with n_cams == 1)"; return VG_ERR_UNSUPPORTED; }
-    if (s->max_pts > 2048) { h->err = "vg_fe_read_image: max_points > 2048"; return VG_ERR_UNSUPPORTED; }
-    if (in->n > s->max_pts || in->max_cnt < 0 || in->max_cnt > s->max_pts) { h->err = "vg_fe_read_image: n / max_cnt beyond max_points of vg_fe_configure"; return VG_ERR_BAD_ARG; }
-    if (in->publish && (in->min_dist < 0 || !(in->f_threshold > 0) || !(in->quality > 0))) { h->err = "vg_fe_read_image: min_dist / f_threshold / quality"; return VG_ERR_BAD_ARG; }
-    // (everything that can be refused from the arguments is refused before the frame goes up and the pyramid ring turns)
-    if (in->n > 0 && !s->have_prev) { h->err = "vg_fe_read_image: points to track but no previous frame"; return VG_ERR_BAD_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = ri_ensure(h, s);
-    if (rc) return rc;
-    RiState* q = s->ri;
-    const size_t npix = (size_t)s->W * s->H, cap = (size_t)q->cap;
-    memset(out, 0, sizeof(*out));
-    RiDev r = q->r;
-    r.focal = in->focal_length; r.half_w = s->W / 2.0; r.half_h = s->H / 2.0;
-    r.cam = fe_stream_camera(s, 0, in->intr);
-    r.max_cnt = in->max_cnt; r.radius = in->min_dist;
-    FeRansacBufs rb;
-    { const hipError_t e = fe_ransac_buffers(h, &rb); if (e != hipSuccess) { h->err = std::string("vg_fe_read_image: ") + hipGetErrorString(e); return VG_ERR_HIP; } }
-    r.count = rb.cnt; r.words = rb.words;
-    // the fisheye mask travels once (the reference loads it at start-up, feature_tracker_node.cpp)
-    if (in->publish && in->base_mask && in->base_mask != q->base_src) {
-        if (!q->d_base) HIPCHK(h, hipMalloc((void**)&q->d_base, npix));
-        HIPCHK(h, hipMemcpyAsync(q->d_base, in->base_mask, npix, hipMemcpyHostToDevice, h->stream));
-        q->base_src = in->base_mask;
-    }
-    r.base_mask = (in->publish && in->base_mask) ? q->d_base : nullptr;
-    // ---- upload: the frame, then ONE block with the control ints and cur_pts
-    const uint8_t* planes[1] = {in->img};
-    rc = fe_upload_async(h, planes, in->stride);
-    if (rc) return rc;
-    int* hctl = (int*)q->host;
-    memset(hctl, 0, sizeof(int) * RI_CTL_INTS);
-    hctl[RI_N] = in->n; hctl[RI_PUBLISH] = in->publish ? 1 : 0; hctl[RI_BEST] = -1;
-    if (in->n) memcpy(q->host + sizeof(int) * RI_CTL_INTS, in->cur_xy, sizeof(float) * 2 * in->n);
-    HIPCHK(h, hipMemcpyAsync(q->d_in, q->host, sizeof(int) * RI_CTL_INTS + sizeof(float) * 2 * in->n, hipMemcpyHostToDevice, h->stream));
-    rc = vg_fe_build_async(h, in->equalize);
-    if (rc) return rc;
-    FeDev d = s->d;
-    d.npts = r.ctl + RI_N; d.prev_xy = r.xy_in;
-    const bool track = in->n > 0;
-    if (track) hipLaunchKernelGGL(fe_lk_kernel, dim3(in->n, 1), dim3(64), 0, h->stream, d);
-    hipLaunchKernelGGL(fe_ri_after_lk_kernel, dim3(1), dim3(256), 0, h->stream, d, r);
-    char* hA = q->host + q->in_bytes;
-    char* hB = hA + q->a_bytes;
-    int* horder = (int*)(hB + q->b_bytes);
-    const int* ahdr = (const int*)hA;
-    out->status_lk = (const uint8_t*)(hA + ((const char*)r.a_status_lk - q->d_a));
-    out->status_f = (const uint8_t*)(hA + ((const char*)r.a_status_f - q->d_a));
-    out->forw_xy = (const float*)(hA + ((const char*)r.a_forw_xy - q->d_a));
-    if (!in->publish) {
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        out->n1 = out->n2 = out->n_final = ahdr[RI_N1];
-        out->un_xy = (const float*)(hA + ((const char*)r.a_un_xy - q->d_a));
-        out->ransac_best = -1;
-        return VG_OK;
-    }
-    // ---- rejectWithF (:169-202); the kernels leave at once when fewer than 15 points survived the tracking
-    if (in->n >= 15) {
-        const float thresh2 = (float)(in->f_threshold * in->f_threshold);
-        hipLaunchKernelGGL(fe_ransac7_kernel, dim3((FE_RANSAC_MAXIT + 6) / 7), dim3(64), 0, h->stream, (const float*)r.p1, (const float*)r.p2, 0,
-                           (const int*)q->d_sched, FE_RANSAC_MAXIT, rb.models, r.ctl);
-        hipLaunchKernelGGL(fe_ransac_count_kernel, dim3(FE_RANSAC_MAXIT), dim3(64), 0, h->stream, (const float*)r.p1, (const float*)r.p2, 0, thresh2, 0,
-                           (const double*)rb.models, FE_RANSAC_MAXIT, rb.F, rb.cnt, rb.med, rb.words, (const int*)r.ctl);
-        hipLaunchKernelGGL(fe_ri_pick_kernel, dim3(1), dim3(256), 0, h->stream, r);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(hA, q->d_a, (size_t)((const char*)r.a_un_xy - q->d_a), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    out->n1 = ahdr[RI_N1]; out->n2 = ahdr[RI_N2]; out->ransac_ran = ahdr[RI_RANSAC]; out->fallback = ahdr[RI_FALLBACK];
-    out->ransac_best = ahdr[RI_BEST]; out->ransac_niters = ahdr[RI_NITERS];
-    if (out->n1 < 0 || out->n1 > in->n || out->n2 < 0 || out->n2 > out->n1) { h->err = "vg_fe_read_image: inconsistent counts from the device"; return VG_ERR_NUMERIC; }
-    if (out->fallback) {
-        // The device could not finish the estimate by itself (LMedS range, or a sample OpenCV would have redrawn): the lifted point
-        // sets come back, vg_fe_reject_with_f runs the exact schedule, and the survivor list goes up again.
-        const int n1 = out->n1;
-        std::vector<float> pp((size_t)4 * n1);
-        HIPCHK(h, hipMemcpyAsync(pp.data(), r.p1, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(pp.data() + 2 * n1, r.p2, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        uint8_t* sf = (uint8_t*)(hA + ((const char*)r.a_status_f - q->d_a));
-        rc = vg_fe_reject_with_f(h, pp.data(), pp.data() + 2 * n1, n1, in->f_threshold, sf, nullptr, nullptr);
-        if (rc) return rc;
-        std::vector<int> idx2;
-        for (int i = 0, k = 0; i < in->n; ++i)
-            if (out->status_lk[i]) { if (sf[k]) idx2.push_back(i); ++k; }
-        out->n2 = (int)idx2.size();
-        if (out->n2) HIPCHK(h, hipMemcpy(r.idx2, idx2.data(), sizeof(int) * idx2.size(), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(r.ctl + RI_N2, &out->n2, sizeof(int), hipMemcpyHostToDevice));
-        out->ransac_best = -1; out->ransac_niters = 0;
-    }
-    // ---- setMask (:36-69): the order of the walk is the caller's (see include/vinsgpu.h)
-    const int n2 = out->n2;
-    if (in->order && n2 > 0) {
-        for (int k = 0; k < n2; ++k) horder[k] = -1;
-        if (in->order(in->user, out, horder) != 0) { h->err = "vg_fe_read_image: the order callback failed"; return VG_ERR_BAD_ARG; }
-        std::vector<char> seen((size_t)n2, 0);
-        for (int k = 0; k < n2; ++k) {
-            if (horder[k] < 0 || horder[k] >= n2 || seen[horder[k]]) { h->err = "vg_fe_read_image: the order callback did not return a permutation"; return VG_ERR_BAD_ARG; }
-            seen[horder[k]] = 1;
-        }
-        HIPCHK(h, hipMemcpyAsync(q->d_order, horder, sizeof(int) * n2, hipMemcpyHostToDevice, h->stream));
-        r.order = q->d_order;
-    } else
-        r.order = nullptr;
-    if (r.base_mask) HIPCHK(h, hipMemcpyAsync(s->mask, q->d_base, npix, hipMemcpyDeviceToDevice, h->stream));
-    else HIPCHK(h, hipMemsetAsync(s->mask, 255, npix, h->stream));
-    hipLaunchKernelGGL(fe_ri_setmask_kernel, dim3(1), dim3(64), 0, h->stream, d, r);
-    if (n2 > 0) hipLaunchKernelGGL(fe_stamp_kernel, dim3(n2, 1), dim3(256), 0, h->stream, d, (const int*)(r.ctl + RI_NK), (const int*)r.kept_xy, in->min_dist);
-    // ---- goodFeaturesToTrack(forw_img, n_pts, MAX_CNT - forw_pts.size(), 0.01, MIN_DIST, mask) (:144-149) + addPoints + undistortedPoints
-    rc = vg_fe_detect_async(h, in->quality, (double)in->min_dist);
-    if (rc) return rc;
-    hipLaunchKernelGGL(fe_ri_finish_kernel, dim3(1), dim3(256), 0, h->stream, d, r);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(hB, q->d_b, q->b_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int* bhdr = (const int*)hB;
-    if (bhdr[RI_NNEW] < 0) { h->err = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)"; return VG_ERR_UNSUPPORTED; }
-    out->n_kept = bhdr[RI_NK]; out->n_new = bhdr[RI_NNEW]; out->n_final = out->n_kept + out->n_new;
-    out->kept = (const int*)(hB + ((const char*)r.b_kept - q->d_b));
-    out->new_xy = (const float*)(hB + ((const char*)r.b_new_xy - q->d_b));
-    out->un_xy = (const float*)(hB + ((const char*)r.b_un_xy - q->d_b));
-    return VG_OK;
-}
-
-// ================================================================================================ one call per frame, every stream
 static int rb_build(vg_handle* h, FeState* s, RbState* q) {
     const size_t cap = (size_t)s->max_pts, S = (size_t)s->cams;
     RbDev& b = q->b;
@@ -893,6 +697,7 @@ static int rb_build(vg_handle* h, FeState* s, RbState* q) {
     return VG_OK;
 }
 
+// (the state is attached to the handle only when it is complete: a failed allocation leaves nothing half-made behind)
 static int rb_ensure(vg_handle* h, FeState* s) {
     if (s->rb) return VG_OK;
     RbState* q = new RbState();
@@ -902,70 +707,49 @@ static int rb_ensure(vg_handle* h, FeState* s) {
     return VG_OK;
 }
 
-// the frames of all streams into the slot of the next build; rows may be padded differently per stream
-static int rb_upload_frames(vg_handle* h, FeState* s, const vg_fe_frame_in* in) {
-    std::vector<const uint8_t*> imgs((size_t)s->cams);
-    bool same = true;
-    for (int c = 0; c < s->cams; ++c) { imgs[c] = in[c].img; same = same && in[c].stride == in[0].stride; }
-    if (same) return fe_upload_async(h, imgs.data(), in[0].stride);
-    const size_t npix = (size_t)s->W * s->H;
-    s->raw_sel = s->flip ^ 1;                             // (as fe_upload_async)
-    s->d.raw = s->raw2[s->raw_sel];
-    s->prev_clobbered = s->have_prev && s->alias_on[s->flip ^ 1];
-    for (int c = 0; c < s->cams; ++c)
-        HIPCHK(h, hipMemcpy2DAsync(s->raw2[s->raw_sel] + (size_t)c * npix, s->W, imgs[c], in[c].stride, s->W, s->H, hipMemcpyHostToDevice, h->stream));
-    return VG_OK;
-}
-
-extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
-    VG_RANGE("vg_fe_read_image_batch");
-    if (!h || !h->fe || !in || !out || n_streams < 1) return VG_ERR_BAD_ARG;
+// FeatureTracker::readImage for the S streams of the handle, the body of vg_fe_read_image (S == 1) and vg_fe_read_image_batch, which
+// have checked h, in, out and S == n_cams; `who` is the entry point the caller used, for the messages.
+static int fe_read_image_streams(vg_handle* h, const char* who, const int S, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
     FeState* s = h->fe;
-    if (n_streams != s->cams) { h->err = "vg_fe_read_image_batch: n_streams differs from n_cams of vg_fe_configure (the batched streams advance together)"; return VG_ERR_BAD_ARG; }
-    if (s->max_pts > 2048) { h->err = "vg_fe_read_image_batch: max_points > 2048"; return VG_ERR_UNSUPPORTED; }
-    // ---- everything that follows from the arguments alone is refused here: no frame has gone up, no stream has moved
-    const int S = s->cams;
+    auto refuse = [&](int code, const char* why) { h->err = std::string(who) + ": " + why; return code; };
+    if (s->max_pts > 2048) return refuse(VG_ERR_UNSUPPORTED, "max_points > 2048");
+    // ---- everything that follows from the arguments alone is refused here: no frame has gone up, no stream has moved (ADVICE r5)
     int n_img = 0, n_pub = 0, first_pub = -1, nmax = 0;
     bool any_ransac = false, any_base = false;
     for (int c = 0; c < S; ++c) {
         const vg_fe_frame_in& f = in[c];
-        if (f.struct_size != (int)sizeof(vg_fe_frame_in) || f.n < 0 || (f.n && !f.cur_xy)) { h->err = "vg_fe_read_image_batch: struct_size / n / cur_xy of a stream"; return VG_ERR_BAD_ARG; }
-        if (f.n > s->max_pts || f.max_cnt < 0 || f.max_cnt > s->max_pts) { h->err = "vg_fe_read_image_batch: n / max_cnt beyond max_points of vg_fe_configure"; return VG_ERR_BAD_ARG; }
-        if (f.publish && (f.min_dist < 0 || !(f.f_threshold > 0) || !(f.quality > 0))) { h->err = "vg_fe_read_image_batch: min_dist / f_threshold / quality"; return VG_ERR_BAD_ARG; }
-        if (f.n > 0 && !s->have_prev) { h->err = "vg_fe_read_image_batch: points to track but no previous frame"; return VG_ERR_BAD_ARG; }
-        if (f.img && f.stride < s->W) { h->err = "vg_fe_read_image_batch: stride smaller than the frame width"; return VG_ERR_BAD_ARG; }
-        if ((f.equalize != 0) != (in[0].equalize != 0)) { h->err = "vg_fe_read_image_batch: equalize differs between the streams (the image build takes one value)"; return VG_ERR_BAD_ARG; }
+        if (f.struct_size != (int)sizeof(vg_fe_frame_in) || f.n < 0 || (f.n && !f.cur_xy)) return refuse(VG_ERR_BAD_ARG, "struct_size / n / cur_xy of a stream");
+        if (f.n > s->max_pts || f.max_cnt < 0 || f.max_cnt > s->max_pts) return refuse(VG_ERR_BAD_ARG, "n / max_cnt beyond max_points of vg_fe_configure");
+        if (f.publish && (f.min_dist < 0 || !(f.f_threshold > 0) || !(f.quality > 0))) return refuse(VG_ERR_BAD_ARG, "min_dist / f_threshold / quality");
+        if (f.n > 0 && !s->have_prev) return refuse(VG_ERR_BAD_ARG, "points to track but no previous frame");
+        if (f.img && f.stride < s->W) return refuse(VG_ERR_BAD_ARG, "stride smaller than the frame width");
+        if ((f.equalize != 0) != (in[0].equalize != 0)) return refuse(VG_ERR_BAD_ARG, "equalize differs between the streams (the image build takes one value)");
         n_img += f.img ? 1 : 0;
         nmax = std::max(nmax, f.n);
         if (f.publish) {
             if (first_pub < 0) first_pub = c;
-            else if (f.quality != in[first_pub].quality || f.min_dist != in[first_pub].min_dist) {
-                h->err = "vg_fe_read_image_batch: quality / min_dist differ between the streams that publish (the detection takes one value)";
-                return VG_ERR_BAD_ARG;
-            }
+            else if (f.quality != in[first_pub].quality || f.min_dist != in[first_pub].min_dist)
+                return refuse(VG_ERR_BAD_ARG, "quality / min_dist differ between the streams that publish (the detection takes one value)");
             ++n_pub;
             any_ransac = any_ransac || f.n >= 15;
             any_base = any_base || f.base_mask;
         }
     }
-    if (n_img != 0 && n_img != S) { h->err = "vg_fe_read_image_batch: frames for some streams only (all, or none = the resident frames)"; return VG_ERR_BAD_ARG; }
+    if (n_img != 0 && n_img != S) return refuse(VG_ERR_BAD_ARG, "frames for some streams only (all, or none = the resident frames)");
     const int equalize = in[0].equalize;
-    if (equalize && (s->d.W % 8 || s->d.H % 8)) { h->err = "CLAHE needs width and height divisible by 8"; return VG_ERR_UNSUPPORTED; }
-    if (equalize && s->d.W / 8 / 4 + 3 > 256) { h->err = "CLAHE: frame wider than the interpolation-cell tiling (W / 32 + 3 > 256)"; return VG_ERR_UNSUPPORTED; }
+    if (const char* why = equalize ? fe_clahe_refusal(s->d) : nullptr) { h->err = why; return VG_ERR_UNSUPPORTED; }
     const int radius = n_pub ? in[first_pub].min_dist : 0;
     const double quality = n_pub ? in[first_pub].quality : 0.01;
-    if (n_pub) {
-        const int cell = radius < 1 ? 1 : radius;
-        if (((s->d.W + cell - 1) / cell) * ((s->d.H + cell - 1) / cell) > FE_MAX_CELLS) { h->err = "min_dist too small for the cell grid"; return VG_ERR_UNSUPPORTED; }
-    }
+    int rc = n_pub ? fe_cell_grid_check(h, s->d, radius) : VG_OK;
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = rb_ensure(h, s);
+    rc = rb_ensure(h, s);
     if (rc) return rc;
     RbState* q = s->rb;
     const RbDev& b = q->b;
     const size_t npix = (size_t)s->W * s->H, cap = (size_t)b.cap;
     for (int c = 0; c < S; ++c) memset(&out[c], 0, sizeof(out[c]));
-    // the fisheye masks travel once per stream (the reference loads them at start-up)
+    // the fisheye masks travel once per stream (the reference loads them at start-up, feature_tracker_node.cpp)
     if (any_base && !q->d_base) HIPCHK(h, hipMalloc((void**)&q->d_base, npix * S));
     RbDev bd = b;
     bd.base = q->d_base;
@@ -976,7 +760,10 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
         }
     // ---- upload: the frames (unless they are resident), then ONE block with the point counts, control ints, cameras and cur_pts
     if (n_img) {
-        rc = rb_upload_frames(h, s, in);
+        std::vector<const uint8_t*> imgs((size_t)S);
+        std::vector<int> strides((size_t)S);
+        for (int c = 0; c < S; ++c) { imgs[c] = in[c].img; strides[c] = in[c].stride; }
+        rc = fe_upload_async(h, imgs.data(), 0, strides.data());
         if (rc) return rc;
     }
     {
@@ -1006,14 +793,19 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
     d.npts = b.npts; d.prev_xy = b.xy_in; d.skip_idle = 1;
     if (nmax > 0) hipLaunchKernelGGL(fe_lk_kernel, dim3(nmax, S), dim3(64), 0, h->stream, d);
     hipLaunchKernelGGL(fe_rb_after_lk_kernel, dim3(S), dim3(256), 0, h->stream, d, bd);
-    // ---- rejectWithF (:169-202) of every stream that publishes; the kernels leave at once for a stream with fewer than 15 survivors
+    // ---- rejectWithF (:169-202) of every stream that publishes; the kernels leave at once for a stream with fewer than 15 survivors.
+    // One stream evaluates all iterations in one part (a launch per step); more streams RB_CHUNK0 of them, then what the bookkeeping
+    // left to do (fe_ransac.hip).  The only place that asks how many streams there are.
     if (any_ransac) {
-        hipLaunchKernelGGL(fe_rb_ransac7_kernel, dim3((RB_CHUNK0 + 6) / 7, S), dim3(64), 0, h->stream, bd, (const int*)q->d_sched, 0);
-        hipLaunchKernelGGL(fe_rb_count_kernel, dim3(RB_CHUNK0, S), dim3(64), 0, h->stream, bd, 0);
-        hipLaunchKernelGGL(fe_rb_pick_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, 0);
-        hipLaunchKernelGGL(fe_rb_ransac7_kernel, dim3(8, S), dim3(64), 0, h->stream, bd, (const int*)q->d_sched, 1);
-        hipLaunchKernelGGL(fe_rb_count_kernel, dim3(56, S), dim3(64), 0, h->stream, bd, 1);
-        hipLaunchKernelGGL(fe_rb_pick_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, 1);
+        const int chunk = S == 1 ? FE_RANSAC_MAXIT : RB_CHUNK0;
+        hipLaunchKernelGGL(fe_rb_ransac7_kernel, dim3((chunk + 6) / 7, S), dim3(64), 0, h->stream, bd, (const int*)q->d_sched, 0, chunk);
+        hipLaunchKernelGGL(fe_rb_count_kernel, dim3(chunk, S), dim3(64), 0, h->stream, bd, 0, chunk);
+        hipLaunchKernelGGL(fe_rb_pick_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, 0, chunk);
+        if (chunk < FE_RANSAC_MAXIT) {
+            hipLaunchKernelGGL(fe_rb_ransac7_kernel, dim3(8, S), dim3(64), 0, h->stream, bd, (const int*)q->d_sched, chunk, FE_RANSAC_MAXIT);
+            hipLaunchKernelGGL(fe_rb_count_kernel, dim3(56, S), dim3(64), 0, h->stream, bd, chunk, FE_RANSAC_MAXIT);
+            hipLaunchKernelGGL(fe_rb_pick_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, chunk, FE_RANSAC_MAXIT);
+        }
     }
     HIPCHK(h, hipGetLastError());
     char* hA = q->host + q->in_bytes;
@@ -1023,25 +815,25 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
     // ONE download: block A of every stream, and the lifted survivors when a stream ends its frame here
     HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes + (n_pub < S ? q->un_bytes : 0), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    int max_n2 = 0;
     for (int c = 0; c < S; ++c) {
         vg_fe_frame_out& o = out[c];
         char* a = hA + (size_t)c * b.a_stride;
         const int* ahdr = (const int*)a;
         o.status_lk = (const uint8_t*)(a + b.a_st); o.status_f = (const uint8_t*)(a + b.a_sf); o.forw_xy = (const float*)(a + b.a_fw);
+        o.n1 = ahdr[RI_N1];
         if (!in[c].publish) {
-            o.n1 = o.n2 = o.n_final = ahdr[RI_N1];
+            o.n2 = o.n_final = o.n1;
             o.un_xy = (const float*)hUn + (size_t)c * cap * 2;
             o.ransac_best = -1;
-            if (o.n1 < 0 || o.n1 > in[c].n) { h->err = "vg_fe_read_image_batch: inconsistent counts from the device"; return VG_ERR_NUMERIC; }
-            continue;
+        } else {
+            o.n2 = ahdr[RI_N2]; o.ransac_ran = ahdr[RI_RANSAC]; o.fallback = ahdr[RI_FALLBACK];
+            o.ransac_best = ahdr[RI_BEST]; o.ransac_niters = ahdr[RI_NITERS];
         }
-        o.n1 = ahdr[RI_N1]; o.n2 = ahdr[RI_N2]; o.ransac_ran = ahdr[RI_RANSAC]; o.fallback = ahdr[RI_FALLBACK];
-        o.ransac_best = ahdr[RI_BEST]; o.ransac_niters = ahdr[RI_NITERS];
-        if (o.n1 < 0 || o.n1 > in[c].n || o.n2 < 0 || o.n2 > o.n1) { h->err = "vg_fe_read_image_batch: inconsistent counts from the device"; return VG_ERR_NUMERIC; }
+        if (o.n1 < 0 || o.n1 > in[c].n || o.n2 < 0 || o.n2 > o.n1) return refuse(VG_ERR_NUMERIC, "inconsistent counts from the device");
     }
     if (n_pub == 0) return VG_OK;
-    // ---- the streams whose estimate the device could not finish (LMedS range, a sample OpenCV would have redrawn): as in the single call
+    // ---- the streams whose estimate the device could not finish (LMedS range, a sample OpenCV would have redrawn): the lifted point
+    // sets come back, vg_fe_reject_with_f runs the exact schedule, and the survivor list goes up again
     for (int c = 0; c < S; ++c) {
         vg_fe_frame_out& o = out[c];
         if (!in[c].publish || !o.fallback) continue;
@@ -1061,10 +853,12 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
         HIPCHK(h, hipMemcpy(b.ctl + (size_t)c * RI_CTL_INTS + RI_N2, &o.n2, sizeof(int), hipMemcpyHostToDevice));
         o.ransac_best = -1; o.ransac_niters = 0;
     }
-    // ---- setMask (:36-69): the callbacks in ascending stream order on this thread, then ONE upload of all orders
+    // ---- setMask (:36-69): the order of the walk is the caller's (include/vinsgpu.h): the callbacks in ascending stream order on this
+    // thread, then ONE upload of all orders
     int* hflag = (int*)hOrd;
     int* horder = (int*)(hOrd + q->ord_flags_bytes);
     bool any_order = false;
+    int max_n2 = 0;
     for (int c = 0; c < S; ++c) {
         hflag[c] = 0;
         if (!in[c].publish) continue;
@@ -1073,16 +867,17 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
         if (!in[c].order || n2 <= 0) continue;
         int* ord = horder + (size_t)c * cap;
         for (int k = 0; k < n2; ++k) ord[k] = -1;
-        if (in[c].order(in[c].user, &out[c], ord) != 0) { h->err = "vg_fe_read_image_batch: the order callback of a stream failed"; return VG_ERR_BAD_ARG; }
+        if (in[c].order(in[c].user, &out[c], ord) != 0) return refuse(VG_ERR_BAD_ARG, "the order callback of a stream failed");
         std::vector<char> seen((size_t)n2, 0);
         for (int k = 0; k < n2; ++k) {
-            if (ord[k] < 0 || ord[k] >= n2 || seen[ord[k]]) { h->err = "vg_fe_read_image_batch: an order callback did not return a permutation"; return VG_ERR_BAD_ARG; }
+            if (ord[k] < 0 || ord[k] >= n2 || seen[ord[k]]) return refuse(VG_ERR_BAD_ARG, "an order callback did not return a permutation");
             seen[ord[k]] = 1;
         }
         hflag[c] = 1;
         any_order = true;
     }
-    HIPCHK(h, hipMemcpyAsync(q->d_ord, hOrd, any_order ? q->ord_bytes : sizeof(int) * S, hipMemcpyHostToDevice, h->stream));
+    if (any_order || q->ord_flags_set) HIPCHK(h, hipMemcpyAsync(q->d_ord, hOrd, any_order ? q->ord_bytes : sizeof(int) * S, hipMemcpyHostToDevice, h->stream));
+    q->ord_flags_set = any_order;
     // the masks of the streams that publish: the fisheye mask or 255 (runs of streams without one: one fill)
     for (int c = 0; c < S;) {
         if (!in[c].publish) { ++c; continue; }
@@ -1098,10 +893,10 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
     }
     hipLaunchKernelGGL(fe_rb_setmask_kernel, dim3(S), dim3(64), 0, h->stream, d, bd);
     if (max_n2 > 0) hipLaunchKernelGGL(fe_stamp_kernel, dim3(max_n2, S), dim3(256), 0, h->stream, d, (const int*)b.nk, (const int*)b.kept_xy, radius);
-    // ---- goodFeaturesToTrack (:144-149) of the streams that publish (the others leave the kernels at once) + addPoints + undistortedPoints
-    HIPCHK(h, hipMemsetAsync(s->ncand, 0, sizeof(unsigned) * FE_CNT_STRIDE * S, h->stream));
-    hipLaunchKernelGGL(fe_mineig_kernel, dim3((d.W + 63) / 64, (d.H + 15) / 16, S), dim3(256), 0, h->stream, d, quality);
-    HIPCHK(h, fe_launch_select(d, quality, (float)(double)radius, h->stream));
+    // ---- goodFeaturesToTrack(forw_img, n_pts, MAX_CNT - forw_pts.size(), 0.01, MIN_DIST, mask) (:144-149) of the streams that publish
+    // (the others leave the kernels at once) + addPoints + undistortedPoints
+    rc = fe_detect_launch(h, d, quality, (double)radius);
+    if (rc) return rc;
     hipLaunchKernelGGL(fe_rb_finish_kernel, dim3(S), dim3(256), 0, h->stream, d, bd);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(hB, q->d_b, q->b_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1111,9 +906,23 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
         vg_fe_frame_out& o = out[c];
         char* q2 = hB + (size_t)c * b.b_stride;
         const int* bhdr = (const int*)q2;
-        if (bhdr[RI_NNEW] < 0) { h->err = "goodFeaturesToTrack: candidate list overflow (more 3x3 maxima than the key buffer holds)"; return VG_ERR_UNSUPPORTED; }
+        if (bhdr[RI_NNEW] < 0) { h->err = FE_CAND_OVERFLOW; return VG_ERR_UNSUPPORTED; }
         o.n_kept = bhdr[RI_NK]; o.n_new = bhdr[RI_NNEW]; o.n_final = o.n_kept + o.n_new;
         o.kept = (const int*)(q2 + b.b_k); o.new_xy = (const float*)(q2 + b.b_nw); o.un_xy = (const float*)(q2 + b.b_un);
     }
     return VG_OK;
+}
+
+extern "C" int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
+    VG_RANGE("vg_fe_read_image");
+    if (!h || !h->fe || !in || !out || in->struct_size != (int)sizeof(vg_fe_frame_in) || !in->img) return VG_ERR_BAD_ARG;
+    if (h->fe->cams != 1) { h->err = "vg_fe_read_image: one stream per handle (vg_fe_configure with n_cams == 1)"; return VG_ERR_UNSUPPORTED; }
+    return fe_read_image_streams(h, "vg_fe_read_image", 1, in, out);
+}
+
+extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
+    VG_RANGE("vg_fe_read_image_batch");
+    if (!h || !h->fe || !in || !out || n_streams < 1) return VG_ERR_BAD_ARG;
+    if (n_streams != h->fe->cams) { h->err = "vg_fe_read_image_batch: n_streams differs from n_cams of vg_fe_configure (the batched streams advance together)"; return VG_ERR_BAD_ARG; }
+    return fe_read_image_streams(h, "vg_fe_read_image_batch", n_streams, in, out);
 }

@@ -1,4 +1,5 @@
-// fe_layout.h — device-side descriptor of the front-end state (shared by fe_host.hip and fe_kernels.hip).
+// fe_layout.h — device-side descriptors of the front-end state, shared by fe_host.hip and the kernel files: FeDev (images, points,
+// detection), RbDev / RiDev (one readImage call per frame: the tables of all streams / the view of one stream), FeRansacBufs.
 #pragma once
 #include <stdint.h>
 #include "fe_camera.h"
@@ -32,13 +33,14 @@ struct FeDev {
     const int* max_corners;         // [cams]
     float* corners;                 // [cams][max_pts][2]
     int* ncorners;                  // [cams]
-    int skip_idle;                  // vg_fe_read_image_batch: a stream whose max_corners is negative (it does not publish) leaves the
+    int skip_idle;                  // vg_fe_read_image[_batch]: a stream whose max_corners is negative (it does not publish) leaves the
                                     // detection kernels at once with 0 corners; 0 everywhere else
 };
 
 #define FE_RANSAC_MAXIT 1000        // maxIters of cv::findFundamentalMat's RANSAC
 #define FE_RANSAC_MAXPTS 1024
-// ---- vg_fe_read_image: one call per frame (fe_frame.hip).  Device control block (ints), the head of the uploaded input block:
+// ---- vg_fe_read_image / vg_fe_read_image_batch: one call per frame (fe_frame.hip).  Device control block of a stream (ints), part of
+// the uploaded input block:
 enum {
     RI_N = 0,          // points handed in (cur_pts)
     RI_PUBLISH,        // PUB_THIS_FRAME
@@ -50,12 +52,13 @@ enum {
     RI_NK,             // points setMask kept
     RI_NNEW,           // corners detected (-1: candidate list overflow)
     RI_NITERS,         // iterations that counted
-    RI_MAXGOOD,        // (batched call) inliers of the best model so far, carried between the two parts of the bookkeeping
+    RI_MAXGOOD,        // inliers of the best model so far, carried between the two parts of the bookkeeping (more than one stream)
     RI_CTL_INTS = 16
 };
 #define RI_FB_COLLINEAR 1           // a sample of the point-independent schedule would have been redrawn by OpenCV
 #define RI_FB_LMEDS 2               // 8 <= n1 < 15: findFundamentalMat switches to LMedS
 #define RI_FB_RANGE 4               // n1 beyond the resident schedule table
+// One stream as the bodies of fe_frame.hip see it.  Never passed to a kernel: a kernel rebuilds it from RbDev for its stream (scalar loads).
 struct RiDev {
     int* ctl;                       // [RI_CTL_INTS]
     const float* xy_in;             // [cap][2] cur_pts
@@ -86,10 +89,9 @@ struct RiDev {
     int* kept_xy;                   // [cap][2] rounded positions of the kept points (fe_stamp_kernel)
     const uint8_t* base_mask;       // fisheye mask or nullptr
 };
-// ---- vg_fe_read_image_batch: the same frame for every stream of the handle.  What the single call passes by value in RiDev comes from
-// device tables indexed by stream; a kernel of the batch rebuilds the stream's RiDev from them (scalar loads) and runs the single
-// call's body on it.
-#define RB_CHUNK0 63                // RANSAC iterations every stream evaluates before the bookkeeping first looks (9 wavefronts of 7 samples)
+// ---- the frame for the S streams of the handle (vg_fe_read_image: S = 1): device tables indexed by stream, what the kernels take.
+#define RB_CHUNK0 63                // S > 1: RANSAC iterations every stream evaluates before the bookkeeping first looks (9 wavefronts of 7
+                                    // samples); one stream evaluates all FE_RANSAC_MAXIT in one part
 struct RiCam {                      // per stream, uploaded with the points
     double focal, half_w, half_h;
     FeCamera cam;

@@ -113,21 +113,10 @@ DEV bool fr_last_collinear(const float* __restrict__ p, const int* idx) {
 // wavefront per SIMD at most: what it costs is the LENGTH of the dependent instruction sequence, and that is a quarter of the
 // one-thread form's (165 -> see DESIGN.md section 2 for 1000 samples).  Any basis of the two-dimensional null space gives the same
 // pencil of models; the inlier masks are held to the oracle's two-sided Jacobi as before.
-//
-// `ctl` (vg_fe_read_image: the call runs without the host in between): the number of correspondences is ctl[RI_N1], the schedule
-// is row n - 15 of the resident table of point-independent schedules, and a sample OpenCV would have REDRAWN (its last point
-// collinear with two earlier ones, which depends on the points) raises ctl[RI_FALLBACK] -- the host then repeats the estimate
-// with the exact schedule.  ctl == nullptr: the arguments are what they say (vg_fe_reject_with_f).
 #define FR_GROUP 9                       // lanes per sample
 #define FR_PER_WAVE (64 / FR_GROUP)      // 7 samples per wavefront; lane 63 idles
-extern "C" __global__ __launch_bounds__(64) void fe_ransac7_kernel(const float* __restrict__ p1, const float* __restrict__ p2, int n,
-                                                                   const int* __restrict__ sched, int nsched, double* __restrict__ models,
-                                                                   int* __restrict__ ctl) {
-    if (ctl) {
-        n = ctl[RI_N1];
-        if (n < 15 || n > FE_RANSAC_MAXPTS || ctl[RI_PUBLISH] == 0) return;
-        sched += (size_t)(n - 15) * 7 * FE_RANSAC_MAXIT;
-    }
+extern "C" __global__ __launch_bounds__(64) void fe_ransac7_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                                   const int* __restrict__ sched, int nsched, double* __restrict__ models) {
 #define FR_FIRST_SAMPLE (blockIdx.x * FR_PER_WAVE)
 #include "fe_ransac7_body.h"
 #undef FR_FIRST_SAMPLE
@@ -141,30 +130,38 @@ extern "C" __global__ __launch_bounds__(64) void fe_ransac7_kernel(const float* 
 extern "C" __global__ __launch_bounds__(64) void fe_ransac_count_kernel(const float* __restrict__ p1, const float* __restrict__ p2, int n, float thresh2,
                                                                         int lmeds, const double* __restrict__ models, int nsched,
                                                                         double* __restrict__ Fout, int* __restrict__ count, double* __restrict__ median,
-                                                                        unsigned long long* __restrict__ inl_words, const int* __restrict__ ctl) {
+                                                                        unsigned long long* __restrict__ inl_words) {
     const int k = blockIdx.x, lane = threadIdx.x;
-    if (ctl) {
-        n = ctl[RI_N1];
-        if (n < 15 || n > FE_RANSAC_MAXPTS || ctl[RI_PUBLISH] == 0) return;
-    }
     if (k >= nsched) return;
 #include "fe_ransac_count_body.h"
 }
 
-// ---- vg_fe_read_image_batch: the two kernels above with a stream dimension (blockIdx.y) and per-stream scratch, RANSAC only (a stream in
-// the LMedS range goes back to the host as in the single call).  The registrator's loop never looks at an iteration at or beyond its
-// bound, and the bound only shrinks; at 256 streams the 1000 iterations of the single call would be 256K wavefronts of which the
-// bookkeeping reads a few dozen per stream.  So the iterations run in two parts with the bookkeeping (fe_rb_pick_kernel) between them:
-//   part 0   iterations [0, RB_CHUNK0) of every stream, and the collinearity test of ALL 1000 samples of its schedule (the fall-back
-//            flag of the single call does not depend on where the loop ends; neither does this one);
-//   part 1   iterations [RB_CHUNK0, bound after part 0) -- nothing for most streams; a wavefront takes several iterations in turn.
-// Every iteration below the final bound has been evaluated when the bookkeeping reaches it: the outputs are those of the single call.
+// ---- vg_fe_read_image / vg_fe_read_image_batch: the two kernels above with a stream dimension (blockIdx.y) and per-stream scratch, for a
+// frame that runs without the host in between.  The number of correspondences is ctl[RI_N1], the schedule is row n - 15 of the resident
+// table of point-independent schedules, and a sample OpenCV would have REDRAWN (its last point collinear with two earlier ones, which
+// depends on the points) raises ctl[RI_FALLBACK] -- the host then repeats the estimate with the exact schedule.  RANSAC only (a stream
+// in the LMedS range goes back to the host as well).
+// The registrator's loop never looks at an iteration at or beyond its bound, and the bound only shrinks; at 256 streams all 1000
+// iterations would be 256K wavefronts of which the bookkeeping reads a few dozen per stream.  So a launch evaluates the iterations
+// [first, end), and the host runs them in one part (a single stream: first = 0, end = FE_RANSAC_MAXIT) or in two with the bookkeeping
+// (fe_rb_pick_kernel) between them:
+//   first == 0   iterations [0, end) of every stream, and the collinearity test of ALL 1000 samples of its schedule (the fall-back flag
+//                does not depend on where the loop ends);
+//   first > 0    iterations [first, min(end, bound after the earlier part)) -- nothing for most streams; a wavefront takes several
+//                iterations in turn.
+// Every iteration below the final bound has been evaluated when the bookkeeping reaches it: two parts give the outputs of one.
 DEV bool rb_ransac_stream(const RbDev& b, const int c, int& n) {
     const int* ctl = b.ctl + (size_t)c * RI_CTL_INTS;
     n = ctl[RI_N1];
     return !(n < 15 || n > FE_RANSAC_MAXPTS || ctl[RI_PUBLISH] == 0);
 }
-extern "C" __global__ __launch_bounds__(64) void fe_rb_ransac7_kernel(RbDev b, const int* __restrict__ sched, int part) {
+// end of the iterations of a launch: `end`, cut to the bound the earlier part's bookkeeping left when there was one
+DEV int rb_ransac_end(const RbDev& b, const int c, const int first, const int end) {
+    if (first == 0) return end;
+    const int bound = b.ctl[(size_t)c * RI_CTL_INTS + RI_NITERS];
+    return bound < end ? bound : end;
+}
+extern "C" __global__ __launch_bounds__(64) void fe_rb_ransac7_kernel(RbDev b, const int* __restrict__ sched, int first, int end) {
     const int cam = blockIdx.y;
     int n;
     if (!rb_ransac_stream(b, cam, n)) return;
@@ -173,28 +170,22 @@ extern "C" __global__ __launch_bounds__(64) void fe_rb_ransac7_kernel(RbDev b, c
     const float* __restrict__ p1 = b.p1 + (size_t)cam * b.cap * 2;
     const float* __restrict__ p2 = b.p2 + (size_t)cam * b.cap * 2;
     double* __restrict__ models = b.models + (size_t)cam * FE_RANSAC_MAXIT * 27;
-    int first = blockIdx.x * FR_PER_WAVE, nsched = RB_CHUNK0;
-    if (part == 0) {
+    if (first == 0)
         for (int q = blockIdx.x * 64 + threadIdx.x; q < FE_RANSAC_MAXIT; q += gridDim.x * 64) {
             int idx[7];
 #pragma unroll
             for (int i = 0; i < 7; ++i) idx[i] = sched[(size_t)q * 7 + i];
             if (fr_last_collinear(p1, idx) || fr_last_collinear(p2, idx)) atomicOr(&sctl[RI_FALLBACK], RI_FB_COLLINEAR);
         }
-    } else {
-        const int bound = sctl[RI_NITERS];
-        nsched = bound < FE_RANSAC_MAXIT ? bound : FE_RANSAC_MAXIT;
-        first += RB_CHUNK0;
-    }
-    int* const ctl = nullptr;                              // (the collinearity test above covers the whole schedule)
+    const int nsched = rb_ransac_end(b, cam, first, end);
 #pragma unroll 1
-    for (int k0 = first; k0 < nsched; k0 += gridDim.x * FR_PER_WAVE) {
+    for (int k0 = first + blockIdx.x * FR_PER_WAVE; k0 < nsched; k0 += gridDim.x * FR_PER_WAVE) {
 #define FR_FIRST_SAMPLE k0
 #include "fe_ransac7_body.h"
 #undef FR_FIRST_SAMPLE
     }
 }
-extern "C" __global__ __launch_bounds__(64) void fe_rb_count_kernel(RbDev b, int part) {
+extern "C" __global__ __launch_bounds__(64) void fe_rb_count_kernel(RbDev b, int first, int end) {
     const int cam = blockIdx.y, lane = threadIdx.x;
     int n;
     if (!rb_ransac_stream(b, cam, n)) return;
@@ -205,14 +196,9 @@ extern "C" __global__ __launch_bounds__(64) void fe_rb_count_kernel(RbDev b, int
     unsigned long long* __restrict__ inl_words = b.words + (size_t)cam * FE_RANSAC_MAXIT * b.words_n;
     const float thresh2 = b.cam[cam].thresh2;
     const int lmeds = 0;
-    int k0 = blockIdx.x, end = RB_CHUNK0;
-    if (part != 0) {
-        const int bound = b.ctl[(size_t)cam * RI_CTL_INTS + RI_NITERS];
-        end = bound < FE_RANSAC_MAXIT ? bound : FE_RANSAC_MAXIT;
-        k0 += RB_CHUNK0;
-    }
+    end = rb_ransac_end(b, cam, first, end);
 #pragma unroll 1
-    for (; k0 < end; k0 += gridDim.x) {
+    for (int k0 = first + blockIdx.x; k0 < end; k0 += gridDim.x) {
         const int k = k0;
 #define FR_COUNT_ONLY
 #include "fe_ransac_count_body.h"
@@ -353,9 +339,9 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
         if ((e = hipMemcpyAsync(d_p + 2 * n, forw_un_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail(e);
         if ((e = hipMemcpyAsync(d_sched, sched.data(), sizeof(int) * 7 * nsched, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail(e);
         const float thresh2 = (float)(threshold * threshold);
-        hipLaunchKernelGGL(fe_ransac7_kernel, dim3((nsched + 6) / 7), dim3(64), 0, h->stream, d_p, d_p + 2 * n, n, d_sched, nsched, d_models, (int*)nullptr);      // 7 samples per wavefront
+        hipLaunchKernelGGL(fe_ransac7_kernel, dim3((nsched + 6) / 7), dim3(64), 0, h->stream, d_p, d_p + 2 * n, d_sched, nsched, d_models);      // 7 samples per wavefront
         hipLaunchKernelGGL(fe_ransac_count_kernel, dim3(nsched), dim3(64), 0, h->stream, d_p, d_p + 2 * n, n, thresh2, lmeds ? 1 : 0, d_models, nsched,
-                           d_F, d_cnt, d_med, d_words, (const int*)nullptr);
+                           d_F, d_cnt, d_med, d_words);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e);
         const int nw = (n + 63) / 64;
         std::vector<int> cnt(nsched);

@@ -1,6 +1,6 @@
 // fe_ransac7_body.h — the body of fe_ransac7_kernel (fe_ransac.hip has the description), included once per kernel that runs it: the
-// single-stream kernel and the batched one compile the SAME text.  The including function provides p1, p2, sched, nsched, models, ctl
-// and FR_FIRST_SAMPLE (the first of the 7 samples of this wavefront).
+// stand-alone kernel and the per-stream one compile the SAME text.  The including function provides p1, p2, sched, nsched, models and
+// FR_FIRST_SAMPLE (the first of the 7 samples of this wavefront).
     const int lane = threadIdx.x, g = lane / FR_GROUP, c = lane - FR_GROUP * g;
     const int k = FR_FIRST_SAMPLE + g;
     const bool live = g < FR_PER_WAVE && k < nsched;
@@ -8,7 +8,6 @@
     int idx[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) idx[i] = live ? sched[(size_t)k * 7 + i] : i;
-    if (ctl && live && c == 0 && (fr_last_collinear(p1, idx) || fr_last_collinear(p2, idx))) atomicOr(&ctl[RI_FALLBACK], RI_FB_COLLINEAR);
     // column c of the design matrix (row i = [x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1]) and of the identity
     double a[7], v[9];
 #pragma unroll

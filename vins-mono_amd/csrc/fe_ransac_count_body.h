@@ -1,5 +1,5 @@
 // fe_ransac_count_body.h — the body of fe_ransac_count_kernel for iteration k (fe_ransac.hip has the description), included once per
-// kernel that runs it: the single-stream kernel and the batched one compile the SAME text.  The including function provides p1, p2, n,
+// kernel that runs it: the stand-alone kernel and the per-stream one compile the SAME text.  The including function provides p1, p2, n,
 // thresh2, lmeds, models, k, lane, count, inl_words and -- unless FR_COUNT_ONLY is defined -- Fout and median.
     const int nw = (n + 63) >> 6;
     double bestF[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
