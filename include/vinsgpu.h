@@ -29,7 +29,8 @@ extern "C" {
                              * 9: vg_fe_keep_eig (the min-eigenvalue map is no longer written unless asked for);
                              * 10: vg_config / vg_create_config; vg_ba_batch_is_fused no longer returns 2; 11: vg_fe_read_image;
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
-                             * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift) */
+                             * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
+                             * vg_fe_tracks_begin / _step / _get / _set) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -647,6 +648,97 @@ int vg_fe_read_image(vg_handle* h, const vg_fe_frame_in* in, vg_fe_frame_out* ou
  * who re-starts them with vg_fe_configure.  Limits: max_points <= 2048, rejectWithF on at most 1024 tracking survivors per stream;
  * the first call allocates the per-stream tables (about 0.45 MB of device memory per stream). */
 int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_frame_in* in /* [n_streams] */, vg_fe_frame_out* out /* [n_streams] */);
+
+/* ---- Track lists resident on the device (added within ABI 12, nothing existing changed).  vg_fe_read_image_batch takes cur_pts from
+ * the host every frame and leaves the bookkeeping of FeatureTracker to every caller: ids / track_cnt and reduceVector over them
+ * (feature_tracker.cpp:118-128, :193-198), setMask's re-ordering (:55-68), addPoints (:71-79), updateID (:204-214, driven from
+ * feature_tracker_node.cpp:103-111), prev_un_pts_map / pts_velocity (:272-305) and the message filter track_cnt > 1
+ * (feature_tracker_node.cpp:133-150).  These calls keep all of that on the device, per stream:
+ *   n, cur_xy[n] (cur_pts), ids[n] (all >= 0 between two frames), track_cnt[n], un_xy[n] (cur_un_pts), in_map[n] (the point is in
+ *   prev_un_pts_map under its own id), n_id, prev_time
+ * and a frame returns what the estimator consumes: per feature  id, x, y, z, u, v, vx, vy.
+ * IDS ARE PER STREAM: every stream counts its own n_id from 0, as a node with NUM_OF_CAM == 1 does.  The reference's process-wide static
+ * FeatureTracker::n_id, interleaved over the cameras of one node, is NOT reproduced.
+ * The state is allocated by the first vg_fe_tracks_begin (capacity max_points per stream); vg_fe_configure drops it.
+ *
+ * vg_fe_tracks_begin   every stream: an empty list, n_id = 0, no previous map.  Also the restart after a failed step.
+ * vg_fe_tracks_step    one frame for every stream: the frame of vg_fe_read_image_batch (image build, calcOpticalFlowPyrLK, rejectWithF,
+ *                      setMask, goodFeaturesToTrack, liftProjective -- the same kernels) with cur_pts read from the resident list, then
+ *                      ONE kernel that commits the frame: reduceVector / the walk order / addPoints over ids and counts, track_cnt + 1,
+ *                      pts_velocity, updateID, and the message.  The upload carries the control block and the cameras only.
+ *     velocity (:272-305)  a carried point whose in_map was set: v = (float)((double)(un - prev_un) / (stamp - prev_time)) per
+ *                      component (float difference, double division, as the reference's Point2f arithmetic); every other point (0, 0).
+ *                      Points detected in a frame enter the reference's map under the key -1 (the map is built BEFORE updateID), so
+ *                      they are not found one frame later: in_map = (id != -1) before this frame's ids are assigned.  stamp ==
+ *                      prev_time gives what IEEE gives.
+ *     message          entries with track_cnt > 1, ascending by id: msg_id[n_msg], msg_obs[n_msg][7] = x y 1.0 u v vx vy (the floats
+ *                      widened to double as estimator_node.cpp widens them): vg_ba_frame::feature_id / obs may point straight at them.
+ *   The rules of vg_fe_read_image_batch carry over: equalize uniform; quality / min_dist uniform over the streams that publish; img of
+ *   all streams or of none (the resident frames); n_streams == n_cams; cameras per stream (vg_fe_set_camera, else the pinhole of
+ *   intr); the LMedS range and a redrawn sample finish on the host.
+ *   walk order  `order` (optional) receives the incremented counts of the n2 survivors of rejectWithF in list order -- the keys setMask
+ *               sorts by -- and writes a permutation of [0, n2); it runs on the calling thread, streams in ascending order; anything
+ *               but 0 aborts the step with VG_ERR_BAD_ARG, as does an order that is no permutation.  NULL walks the list as it stands:
+ *               the counts of a resident list are non-increasing along the list between two frames (kept points in walk order, then
+ *               new ones with count 1), so that IS the stable order by count.  The reference's std::sort is not stable: a caller
+ *               that must reproduce one platform's order among equal counts passes its own sort here.
+ *   failure     VG_ERR_BAD_ARG before anything is uploaded, no stream moved: a step without vg_fe_tracks_begin, a wrong struct_size,
+ *               mixed uniform fields, frames for some streams only, n_streams != n_cams, max_cnt > max_points, a non-empty list on a
+ *               handle without a previous frame.  An error after the upload (a callback's, a detection overflow, a HIP error) leaves
+ *               every LIST exactly as it was (the commit kernel runs last and writes a second copy) but the FRAMES one ahead: restart
+ *               with vg_fe_tracks_begin or vg_fe_configure.
+ *   do not mix  a vg_fe_read_image* / vg_fe_push_frames call between two steps moves the frames but not the lists.
+ *   All pointers of vg_fe_tracks_out point into pinned buffers of the handle and stay valid until the next vg_fe_* call on it.
+ * vg_fe_tracks_get / vg_fe_tracks_set   export and re-seed of ONE stream between two frames; the other streams stay where they are.
+ *   get: arrays of capacity max_points, any of them may be NULL.  set: n <= max_points; ids distinct and >= 0 and n_id greater than
+ *   every id, else VG_ERR_BAD_ARG; un_xy == NULL: no previous map (in_map is ignored, the next frame's velocities are 0); with un_xy,
+ *   in_map is required. */
+typedef int (*vg_fe_tracks_order_fn)(void* user, int stream, int n2, const int* track_cnt /* [n2] */, int* order /* [n2] */);
+typedef struct vg_fe_tracks_in {
+    int struct_size;             /* sizeof(vg_fe_tracks_in) */
+    const uint8_t* img;          /* as vg_fe_frame_in, without cur_xy / n */
+    int stride;
+    int equalize;
+    int publish;
+    int max_cnt;
+    int min_dist;
+    double quality;
+    double f_threshold;
+    double focal_length;
+    double intr[8];
+    const uint8_t* base_mask;
+    vg_fe_tracks_order_fn order; /* or NULL */
+    void* user;
+    double stamp;                /* _cur_time of readImage */
+} vg_fe_tracks_in;
+typedef struct vg_fe_tracks_out {
+    int n;                       /* the list the frame ends with, after updateID */
+    int n_id;
+    int n_msg;
+    int n1, n2, ransac_ran, n_kept, n_new, fallback, ransac_best, ransac_niters;   /* as vg_fe_frame_out */
+    const int* ids;              /* [n] */
+    const int* track_cnt;        /* [n] */
+    const float* cur_xy;         /* [n][2] */
+    const float* un_xy;          /* [n][2] */
+    const float* vel_xy;         /* [n][2] pts_velocity */
+    const int* msg_id;           /* [n_msg] ascending */
+    const double* msg_obs;       /* [n_msg][7] x y 1.0 u v vx vy */
+} vg_fe_tracks_out;
+typedef struct vg_fe_tracks_state {
+    int struct_size;             /* sizeof(vg_fe_tracks_state) */
+    int n;
+    int n_id;
+    double prev_time;
+    float* cur_xy;               /* [n][2] */
+    int* ids;                    /* [n] */
+    int* track_cnt;              /* [n] */
+    float* un_xy;                /* [n][2] */
+    uint8_t* in_map;             /* [n] */
+} vg_fe_tracks_state;
+int vg_fe_tracks_begin(vg_handle* h);
+int vg_fe_tracks_step(vg_handle* h, int n_streams, const vg_fe_tracks_in* in /* [n_streams] */, vg_fe_tracks_out* out /* [n_streams] */);
+int vg_fe_tracks_get(vg_handle* h, int cam, vg_fe_tracks_state* state);
+int vg_fe_tracks_set(vg_handle* h, int cam, const vg_fe_tracks_state* state);
 
 #ifdef __cplusplus
 }

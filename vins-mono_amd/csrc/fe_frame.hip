@@ -284,3 +284,122 @@ extern "C" __global__ __launch_bounds__(256) void fe_rb_finish_kernel(FeDev d, R
     if (r.ctl[RI_PUBLISH] == 0) return;
     ri_finish_body(d, r);
 }
+
+// ================================================================================================ vg_fe_tracks_step: the frame's last kernel
+// grid (S), 256 threads, after fe_rb_finish_kernel (after fe_rb_after_lk_kernel when no stream publishes).  The bookkeeping of
+// FeatureTracker that vg_fe_read_image_batch leaves to its caller, on the resident lists (TkDev, fe_layout.h), from `from` into `to`:
+//   :118-128, :193-198, :55-68  reduceVector / setMask's re-ordering over ids, track_cnt, cur_un_pts: final position -> input position
+//                               is idx1 (not published) or idx2[order[b_kept]] (published), which the frame's kernels left behind
+//   :129                        track_cnt + 1
+//   :71-79                      addPoints: the new corners, count 1
+//   :272-305                    pts_velocity against prev_un_pts_map: float difference, double division by dt, rounded to float
+//   :204-214                    updateID: the list's ids are >= 0 between the frames, so the entries that take n_id++ in list order are
+//                               exactly the new corners, which stand at the end: id = n_id + (position among them)
+//   feature_tracker_node.cpp:133-150  the message: track_cnt > 1, here ascending by id (the order Estimator::processImage's map has)
+// A detection overflow on ANY stream voids the step for all of them: `to` gets TK_NNEW = -1 and nothing else.
+extern "C" __global__ __launch_bounds__(256) void fe_tk_commit_kernel(FeDev d, RbDev b, TkDev t) {
+    __shared__ int wsum[4];
+    __shared__ int s_bad;
+    __shared__ uint8_t flag[TK_MAX];
+    __shared__ int pos[TK_MAX];
+    __shared__ unsigned long long key[TK_MAX];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const size_t cap = (size_t)b.cap;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    for (int s = tid; s < b.S; s += 256)
+        if (b.ctl[(size_t)s * RI_CTL_INTS + RI_PUBLISH] != 0 && d.ncorners[s] < 0) s_bad = 1;
+    __syncthreads();
+    int* th = t.to.hdr + (size_t)c * TK_HDR_INTS;
+    if (s_bad) {
+        if (tid == 0) th[TK_NNEW] = -1;
+        return;
+    }
+    RiDev r;
+    rb_stream(b, c, d, r);
+    const int* fh = t.from.hdr + (size_t)c * TK_HDR_INTS;
+    const int* f_ids = t.from.ids + c * cap;
+    const int* f_cnt = t.from.cnt + c * cap;
+    const float* f_un = t.from.un_xy + c * cap * 2;
+    const uint8_t* f_map = t.from.in_map + c * cap;
+    int* t_ids = t.to.ids + c * cap;
+    int* t_cnt = t.to.cnt + c * cap;
+    float* t_xy = t.to.cur_xy + c * cap * 2;
+    float* t_un = t.to.un_xy + c * cap * 2;
+    float* t_vel = t.to.vel + c * cap * 2;
+    uint8_t* t_map = t.to.in_map + c * cap;
+    const int publish = r.ctl[RI_PUBLISH];
+    const int ncar = publish ? r.ctl[RI_NK] : r.ctl[RI_N1];                 // carried over
+    int nnew = publish ? d.ncorners[0] : 0;
+    nnew = nnew < b.cap - ncar ? nnew : b.cap - ncar;                       // (max_cnt <= max_points: never cuts)
+    const int n = ncar + nnew;
+    const double stamp = *(const double*)(r.ctl + RI_STAMP);
+    const double dt = stamp - *(const double*)(fh + TK_TIME);
+    const int n_id = fh[TK_NID];
+    const float* un = publish ? r.b_un_xy : r.a_un_xy;                      // the lifted list the frame path made
+    for (int k = tid; k < n; k += 256) {
+        const float ux = un[2 * k], uy = un[2 * k + 1];
+        float x, y, vx = 0.f, vy = 0.f;
+        int id, cnt;
+        if (k < ncar) {
+            int i;
+            if (publish) {
+                const int q = r.b_kept[k];
+                i = r.idx2[r.order ? r.order[q] : q];
+            } else
+                i = r.idx1[k];
+            x = d.next_xy[2 * i]; y = d.next_xy[2 * i + 1];
+            id = f_ids[i]; cnt = f_cnt[i] + 1;
+            if (f_map[i]) {
+                vx = (float)((double)(ux - f_un[2 * i]) / dt);
+                vy = (float)((double)(uy - f_un[2 * i + 1]) / dt);
+            }
+        } else {
+            const int j = k - ncar;
+            x = d.corners[2 * j]; y = d.corners[2 * j + 1];
+            id = n_id + j; cnt = 1;
+        }
+        t_ids[k] = id; t_cnt[k] = cnt;
+        t_xy[2 * k] = x; t_xy[2 * k + 1] = y;
+        t_un[2 * k] = ux; t_un[2 * k + 1] = uy;
+        t_vel[2 * k] = vx; t_vel[2 * k + 1] = vy;
+        t_map[k] = k < ncar ? 1 : 0;                                        // (id != -1) before updateID
+        flag[k] = cnt > 1 ? 1 : 0;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // ---- the message: positions with track_cnt > 1 (ordered compaction), then (id, position) pairs sorted by one workgroup: bitonic
+    // over the next power of two, padded with keys above every id
+    const int nm = ri_compact(flag, n, nullptr, pos, wsum);
+    __syncthreads();
+    int P = 1;
+    while (P < nm) P <<= 1;
+    for (int k = tid; k < P; k += 256)
+        key[k] = k < nm ? (((unsigned long long)(unsigned)t_ids[pos[k]] << 32) | (unsigned long long)(unsigned)pos[k]) : ~0ull;
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int i = tid; i < P; i += 256) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long a = key[i], z = key[l];
+                    if ((a > z) == ((i & k2) == 0)) { key[i] = z; key[l] = a; }
+                }
+            }
+        }
+    __syncthreads();
+    int* m_id = t.to.msg_id + c * cap;
+    double* m_obs = t.to.msg_obs + c * cap * 7;
+    for (int m = tid; m < nm; m += 256) {
+        const int p = (int)(key[m] & 0xffffffffull);
+        m_id[m] = (int)(key[m] >> 32);
+        double* o = m_obs + (size_t)m * 7;
+        o[0] = (double)t_un[2 * p]; o[1] = (double)t_un[2 * p + 1]; o[2] = 1.0;
+        o[3] = (double)t_xy[2 * p]; o[4] = (double)t_xy[2 * p + 1];
+        o[5] = (double)t_vel[2 * p]; o[6] = (double)t_vel[2 * p + 1];
+    }
+    if (tid == 0) {
+        th[TK_N] = n; th[TK_NID] = n_id + nnew; th[TK_NMSG] = nm; th[TK_NK] = publish ? ncar : 0; th[TK_NNEW] = nnew;
+        *(double*)(th + TK_TIME) = stamp;
+    }
+}

@@ -41,6 +41,7 @@ __global__ void fe_rb_setmask_kernel(FeDev d, RbDev b);
 __global__ void fe_rb_finish_kernel(FeDev d, RbDev b);
 __global__ void fe_rb_ransac7_kernel(RbDev b, const int* sched, int first, int end);
 __global__ void fe_rb_count_kernel(RbDev b, int first, int end);
+__global__ void fe_tk_commit_kernel(FeDev d, RbDev b, TkDev t);
 }
 void fe_ransac_tables(int nmax, std::vector<int>& sched, std::vector<int>& niters, int stride);
 
@@ -63,6 +64,31 @@ static void rb_free(RbState* q) {
     (void)hipFree(q->dev); (void)hipFree(q->d_sched); (void)hipFree(q->d_tab); (void)hipFree(q->d_base);
     (void)hipHostFree(q->host);
     delete q;
+}
+
+// resident track lists of vg_fe_tracks_* (TkDev, fe_layout.h): two device copies of one block (a step reads dev[cur] and commits into
+// dev[cur ^ 1], which becomes current when the step has succeeded), the pinned mirror the results are handed out from, and the one
+// thing the host mirrors: each stream's list length, for the grid of the tracking kernel
+struct TkState {
+    char* dev[2] = {nullptr, nullptr};
+    char* host = nullptr;
+    int* h_cnt = nullptr;                             // pinned [S][cap]: the counts an order callback is handed come from here
+    size_t bytes = 0, o_ids = 0, o_cnt = 0, o_xy = 0, o_un = 0, o_vel = 0, o_map = 0, o_mid = 0, o_obs = 0;
+    int cur = 0;
+    bool begun = false;
+    std::vector<int> n;
+};
+static void tk_free(TkState* t) {
+    if (!t) return;
+    (void)hipFree(t->dev[0]); (void)hipFree(t->dev[1]); (void)hipHostFree(t->host); (void)hipHostFree(t->h_cnt);
+    delete t;
+}
+static TkBuf tk_buf(const TkState* t, char* base) {
+    TkBuf u;
+    u.hdr = (int*)base; u.ids = (int*)(base + t->o_ids); u.cnt = (int*)(base + t->o_cnt); u.cur_xy = (float*)(base + t->o_xy);
+    u.un_xy = (float*)(base + t->o_un); u.vel = (float*)(base + t->o_vel); u.in_map = (uint8_t*)(base + t->o_map);
+    u.msg_id = (int*)(base + t->o_mid); u.msg_obs = (double*)(base + t->o_obs);
+    return u;
 }
 
 struct FeState {
@@ -102,6 +128,7 @@ struct FeState {
     std::vector<FeCamera> cam;       // [cams] vg_fe_set_camera; cam_set[c] == 0: the pinhole of vg_fe_frame_in::intr
     std::vector<char> cam_set;
     RbState* rb = nullptr;
+    TkState* tk = nullptr;
 };
 
 extern "C" void fe_state_destroy(FeState* s) {
@@ -114,6 +141,7 @@ extern "C" void fe_state_destroy(FeState* s) {
     (void)hipFree(s->sm_pts); (void)hipFree(s->sm_cnt); (void)hipFree(s->sm_n); (void)hipFree(s->sm_kidx); (void)hipFree(s->sm_nk);
     (void)hipFree(s->sm_kxy); (void)hipFree(s->sm_base); (void)hipFree((void*)s->sm_base_ptrs); (void)hipFree(s->lift_in); (void)hipFree(s->lift_out);
     rb_free(s->rb);
+    tk_free(s->tk);
     delete s;
 }
 
@@ -709,8 +737,14 @@ static int rb_ensure(vg_handle* h, FeState* s) {
 
 // FeatureTracker::readImage for the S streams of the handle, the body of vg_fe_read_image (S == 1) and vg_fe_read_image_batch, which
 // have checked h, in, out and S == n_cams; `who` is the entry point the caller used, for the messages.
-static int fe_read_image_streams(vg_handle* h, const char* who, const int S, const vg_fe_frame_in* in, vg_fe_frame_out* out) {
+// `tin` != NULL: the frame of vg_fe_tracks_step -- in[c].n is the length of stream c's resident list and the points are NOT uploaded
+// (the tracking reads them where the last commit left them), the walk-order callbacks are tin[c].order, and the frame ends with
+// fe_tk_commit_kernel and one download of the new lists instead of block B (tk_collect, below, turns it into `tout`).
+static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_frame_out* fo, vg_fe_tracks_out* tout);
+static int fe_read_image_streams(vg_handle* h, const char* who, const int S, const vg_fe_frame_in* in, vg_fe_frame_out* out,
+                                 const vg_fe_tracks_in* tin = nullptr, vg_fe_tracks_out* tout = nullptr) {
     FeState* s = h->fe;
+    TkState* const tk = tin ? s->tk : nullptr;
     auto refuse = [&](int code, const char* why) { h->err = std::string(who) + ": " + why; return code; };
     if (s->max_pts > 2048) return refuse(VG_ERR_UNSUPPORTED, "max_points > 2048");
     // ---- everything that follows from the arguments alone is refused here: no frame has gone up, no stream has moved
@@ -718,7 +752,7 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
     bool any_ransac = false, any_base = false;
     for (int c = 0; c < S; ++c) {
         const vg_fe_frame_in& f = in[c];
-        if (f.struct_size != (int)sizeof(vg_fe_frame_in) || f.n < 0 || (f.n && !f.cur_xy)) return refuse(VG_ERR_BAD_ARG, "struct_size / n / cur_xy of a stream");
+        if (f.struct_size != (int)sizeof(vg_fe_frame_in) || f.n < 0 || (!tk && f.n && !f.cur_xy)) return refuse(VG_ERR_BAD_ARG, "struct_size / n / cur_xy of a stream");
         if (f.n > s->max_pts || f.max_cnt < 0 || f.max_cnt > s->max_pts) return refuse(VG_ERR_BAD_ARG, "n / max_cnt beyond max_points of vg_fe_configure");
         if (f.publish && (f.min_dist < 0 || !(f.f_threshold > 0) || !(f.quality > 0))) return refuse(VG_ERR_BAD_ARG, "min_dist / f_threshold / quality");
         if (f.n > 0 && !s->have_prev) return refuse(VG_ERR_BAD_ARG, "points to track but no previous frame");
@@ -753,6 +787,11 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
     if (any_base && !q->d_base) HIPCHK(h, hipMalloc((void**)&q->d_base, npix * S));
     RbDev bd = b;
     bd.base = q->d_base;
+    TkDev td;
+    if (tk) {
+        td.from = tk_buf(tk, tk->dev[tk->cur]); td.to = tk_buf(tk, tk->dev[tk->cur ^ 1]);
+        bd.xy_in = td.from.cur_xy;
+    }
     for (int c = 0; c < S; ++c)
         if (in[c].publish && in[c].base_mask && in[c].base_mask != q->base_src[c]) {
             HIPCHK(h, hipMemcpyAsync(q->d_base + (size_t)c * npix, in[c].base_mask, npix, hipMemcpyHostToDevice, h->stream));
@@ -781,16 +820,17 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
             k.cam = fe_stream_camera(s, c, f.intr);
             k.thresh2 = (float)(f.f_threshold * f.f_threshold);
             k.max_cnt = f.max_cnt; k.radius = f.min_dist; k.has_base = (f.publish && f.base_mask) ? 1 : 0;
-            if (f.n) memcpy(hxy + (size_t)c * cap * 2, f.cur_xy, sizeof(float) * 2 * f.n);
+            if (tk) memcpy(hctl + c * RI_CTL_INTS + RI_STAMP, &tin[c].stamp, sizeof(double));
+            else if (f.n) memcpy(hxy + (size_t)c * cap * 2, f.cur_xy, sizeof(float) * 2 * f.n);
         }
-        // (cur_pts of the last stream end where its points end)
-        const size_t bytes = q->o_xy + sizeof(float) * 2 * (cap * (S - 1) + in[S - 1].n);
+        // (cur_pts of the last stream end where its points end; resident lists: the control ints and the cameras are all that travels)
+        const size_t bytes = tk ? q->o_xy : q->o_xy + sizeof(float) * 2 * (cap * (S - 1) + in[S - 1].n);
         HIPCHK(h, hipMemcpyAsync(q->d_in, q->host, bytes, hipMemcpyHostToDevice, h->stream));
     }
     rc = vg_fe_build_async(h, equalize);
     if (rc) return rc;
     FeDev d = s->d;
-    d.npts = b.npts; d.prev_xy = b.xy_in; d.skip_idle = 1;
+    d.npts = b.npts; d.prev_xy = bd.xy_in; d.skip_idle = 1;
     if (nmax > 0) hipLaunchKernelGGL(fe_lk_kernel, dim3(nmax, S), dim3(64), 0, h->stream, d);
     hipLaunchKernelGGL(fe_rb_after_lk_kernel, dim3(S), dim3(256), 0, h->stream, d, bd);
     // ---- rejectWithF (:169-202) of every stream that publishes; the kernels leave at once for a stream with fewer than 15 survivors.
@@ -813,7 +853,20 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
     char* hB = hUn + q->un_bytes;
     char* hOrd = hB + q->b_bytes;
     // ONE download: block A of every stream, and the lifted survivors when a stream ends its frame here
-    HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes + (n_pub < S ? q->un_bytes : 0), hipMemcpyDeviceToHost, h->stream));
+    if (tk) {
+        // resident lists: a step in which no stream publishes is committed here and its lists come down with block A; the counts of
+        // the lists travel too when a callback will ask for them
+        bool any_cb = false;
+        for (int c = 0; c < S; ++c) any_cb = any_cb || (in[c].publish && tin[c].order);
+        if (n_pub == 0) {
+            hipLaunchKernelGGL(fe_tk_commit_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, td);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(tk->host, tk->dev[tk->cur ^ 1], tk->bytes, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (any_cb) HIPCHK(h, hipMemcpyAsync(tk->h_cnt, td.from.cnt, sizeof(int) * cap * S, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes, hipMemcpyDeviceToHost, h->stream));
+    } else
+        HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes + (n_pub < S ? q->un_bytes : 0), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int c = 0; c < S; ++c) {
         vg_fe_frame_out& o = out[c];
@@ -831,7 +884,7 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
         }
         if (o.n1 < 0 || o.n1 > in[c].n || o.n2 < 0 || o.n2 > o.n1) return refuse(VG_ERR_NUMERIC, "inconsistent counts from the device");
     }
-    if (n_pub == 0) return VG_OK;
+    if (n_pub == 0) return tk ? tk_collect(h, who, S, out, tout) : VG_OK;
     // ---- the streams whose estimate the device could not finish (LMedS range, a sample OpenCV would have redrawn): the lifted point
     // sets come back, vg_fe_reject_with_f runs the exact schedule, and the survivor list goes up again
     for (int c = 0; c < S; ++c) {
@@ -864,10 +917,25 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
         if (!in[c].publish) continue;
         const int n2 = out[c].n2;
         max_n2 = std::max(max_n2, n2);
-        if (!in[c].order || n2 <= 0) continue;
+        if (!(tk ? (bool)tin[c].order : (bool)in[c].order) || n2 <= 0) continue;
         int* ord = horder + (size_t)c * cap;
         for (int k = 0; k < n2; ++k) ord[k] = -1;
-        if (in[c].order(in[c].user, &out[c], ord) != 0) return refuse(VG_ERR_BAD_ARG, "the order callback of a stream failed");
+        int cb_rc;
+        if (tk) {
+            // the keys setMask sorts by: track_cnt + 1 of the survivors of rejectWithF, in list order
+            std::vector<int> keys((size_t)n2);
+            const int* cnt = tk->h_cnt + (size_t)c * cap;
+            int k1 = 0, k2 = 0;
+            for (int i = 0; i < in[c].n; ++i) {
+                if (!out[c].status_lk[i]) continue;
+                if ((!out[c].ransac_ran || out[c].status_f[k1]) && k2 < n2) keys[k2++] = cnt[i] + 1;
+                ++k1;
+            }
+            if (k2 != n2) return refuse(VG_ERR_NUMERIC, "inconsistent counts from the device");
+            cb_rc = tin[c].order(tin[c].user, c, n2, keys.data(), ord);
+        } else
+            cb_rc = in[c].order(in[c].user, &out[c], ord);
+        if (cb_rc != 0) return refuse(VG_ERR_BAD_ARG, "the order callback of a stream failed");
         std::vector<char> seen((size_t)n2, 0);
         for (int k = 0; k < n2; ++k) {
             if (ord[k] < 0 || ord[k] >= n2 || seen[ord[k]]) return refuse(VG_ERR_BAD_ARG, "an order callback did not return a permutation");
@@ -898,6 +966,13 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
     rc = fe_detect_launch(h, d, quality, (double)radius);
     if (rc) return rc;
     hipLaunchKernelGGL(fe_rb_finish_kernel, dim3(S), dim3(256), 0, h->stream, d, bd);
+    if (tk) {
+        hipLaunchKernelGGL(fe_tk_commit_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, td);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(tk->host, tk->dev[tk->cur ^ 1], tk->bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return tk_collect(h, who, S, out, tout);
+    }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(hB, q->d_b, q->b_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -925,4 +1000,168 @@ extern "C" int vg_fe_read_image_batch(vg_handle* h, int n_streams, const vg_fe_f
     if (!h || !h->fe || !in || !out || n_streams < 1) return VG_ERR_BAD_ARG;
     if (n_streams != h->fe->cams) { h->err = "vg_fe_read_image_batch: n_streams differs from n_cams of vg_fe_configure (the batched streams advance together)"; return VG_ERR_BAD_ARG; }
     return fe_read_image_streams(h, "vg_fe_read_image_batch", n_streams, in, out);
+}
+
+// ================================================================================================ track lists resident on the device
+static int tk_ensure(vg_handle* h, FeState* s) {
+    if (s->tk) return VG_OK;
+    TkState* t = new TkState();
+    const size_t cap = (size_t)s->max_pts, S = (size_t)s->cams;
+    t->o_ids = ri_up(sizeof(int) * TK_HDR_INTS * S, 256);
+    t->o_cnt = t->o_ids + ri_up(sizeof(int) * cap * S, 256);
+    t->o_xy = t->o_cnt + ri_up(sizeof(int) * cap * S, 256);
+    t->o_un = t->o_xy + ri_up(sizeof(float) * 2 * cap * S, 256);
+    t->o_vel = t->o_un + ri_up(sizeof(float) * 2 * cap * S, 256);
+    t->o_map = t->o_vel + ri_up(sizeof(float) * 2 * cap * S, 256);
+    t->o_mid = t->o_map + ri_up(cap * S, 256);
+    t->o_obs = t->o_mid + ri_up(sizeof(int) * cap * S, 256);
+    t->bytes = t->o_obs + ri_up(sizeof(double) * 7 * cap * S, 256);
+    t->n.assign(S, 0);
+    if (hipMalloc((void**)&t->dev[0], t->bytes) != hipSuccess || hipMalloc((void**)&t->dev[1], t->bytes) != hipSuccess ||
+        hipHostMalloc((void**)&t->host, t->bytes, 0) != hipSuccess || hipHostMalloc((void**)&t->h_cnt, sizeof(int) * cap * S, 0) != hipSuccess) {
+        tk_free(t);
+        h->err = "vg_fe_tracks_begin: out of memory for the resident track lists";
+        return VG_ERR_HIP;
+    }
+    s->tk = t;
+    return VG_OK;
+}
+
+extern "C" int vg_fe_tracks_begin(vg_handle* h) {
+    if (!h) return VG_ERR_BAD_ARG;
+    if (!h->fe) { h->err = "vg_fe_tracks_begin: the handle has no front end (vg_fe_configure)"; return VG_ERR_BAD_ARG; }
+    FeState* s = h->fe;
+    if (s->max_pts > TK_MAX) { h->err = "vg_fe_tracks_begin: max_points > 2048"; return VG_ERR_UNSUPPORTED; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = tk_ensure(h, s);
+    if (rc) return rc;
+    TkState* t = s->tk;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemset(t->dev[0], 0, t->bytes));
+    HIPCHK(h, hipMemset(t->dev[1], 0, t->bytes));
+    t->cur = 0;
+    t->n.assign((size_t)s->cams, 0);
+    t->begun = true;
+    return VG_OK;
+}
+
+// the lists the commit kernel left in the pinned mirror -> the caller's vg_fe_tracks_out; the step has succeeded: they become current
+static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_frame_out* fo, vg_fe_tracks_out* tout) {
+    FeState* s = h->fe;
+    TkState* t = s->tk;
+    const size_t cap = (size_t)s->max_pts;
+    const TkBuf u = tk_buf(t, t->host);
+    for (int c = 0; c < S; ++c) {
+        const int* hd = u.hdr + (size_t)c * TK_HDR_INTS;
+        if (hd[TK_NNEW] < 0) { h->err = FE_CAND_OVERFLOW; return VG_ERR_UNSUPPORTED; }
+        if (hd[TK_N] < 0 || hd[TK_N] > (int)cap || hd[TK_NMSG] < 0 || hd[TK_NMSG] > hd[TK_N]) {
+            h->err = std::string(who) + ": inconsistent counts from the device";
+            return VG_ERR_NUMERIC;
+        }
+    }
+    for (int c = 0; c < S; ++c) {
+        const int* hd = u.hdr + (size_t)c * TK_HDR_INTS;
+        vg_fe_tracks_out& o = tout[c];
+        memset(&o, 0, sizeof(o));
+        o.n = hd[TK_N]; o.n_id = hd[TK_NID]; o.n_msg = hd[TK_NMSG];
+        o.n1 = fo[c].n1; o.n2 = fo[c].n2; o.ransac_ran = fo[c].ransac_ran; o.n_kept = hd[TK_NK]; o.n_new = hd[TK_NNEW];
+        o.fallback = fo[c].fallback; o.ransac_best = fo[c].ransac_best; o.ransac_niters = fo[c].ransac_niters;
+        o.ids = u.ids + c * cap; o.track_cnt = u.cnt + c * cap; o.cur_xy = u.cur_xy + c * cap * 2; o.un_xy = u.un_xy + c * cap * 2;
+        o.vel_xy = u.vel + c * cap * 2; o.msg_id = u.msg_id + c * cap; o.msg_obs = u.msg_obs + c * cap * 7;
+        t->n[c] = o.n;
+    }
+    t->cur ^= 1;
+    return VG_OK;
+}
+
+extern "C" int vg_fe_tracks_step(vg_handle* h, int n_streams, const vg_fe_tracks_in* in, vg_fe_tracks_out* out) {
+    VG_RANGE("vg_fe_tracks_step");
+    if (!h || !h->fe || !in || !out || n_streams < 1) return VG_ERR_BAD_ARG;
+    FeState* s = h->fe;
+    if (n_streams != s->cams) { h->err = "vg_fe_tracks_step: n_streams differs from n_cams of vg_fe_configure (the streams advance together)"; return VG_ERR_BAD_ARG; }
+    if (!s->tk || !s->tk->begun) { h->err = "vg_fe_tracks_step: no resident lists (vg_fe_tracks_begin)"; return VG_ERR_BAD_ARG; }
+    std::vector<vg_fe_frame_in> fin((size_t)n_streams);
+    std::vector<vg_fe_frame_out> fout((size_t)n_streams);
+    for (int c = 0; c < n_streams; ++c) {
+        const vg_fe_tracks_in& t = in[c];
+        if (t.struct_size != (int)sizeof(vg_fe_tracks_in)) { h->err = "vg_fe_tracks_step: struct_size of a stream"; return VG_ERR_BAD_ARG; }
+        vg_fe_frame_in& f = fin[c];
+        memset(&f, 0, sizeof(f));
+        f.struct_size = (int)sizeof(vg_fe_frame_in);
+        f.img = t.img; f.stride = t.stride; f.equalize = t.equalize; f.publish = t.publish;
+        f.n = s->tk->n[c];
+        f.max_cnt = t.max_cnt; f.min_dist = t.min_dist; f.quality = t.quality; f.f_threshold = t.f_threshold; f.focal_length = t.focal_length;
+        memcpy(f.intr, t.intr, sizeof(f.intr));
+        f.base_mask = t.base_mask;
+    }
+    const int rc = fe_read_image_streams(h, "vg_fe_tracks_step", n_streams, fin.data(), fout.data(), in, out);
+    // (an error after the upload: the lists stand as they were -- only a finished step makes the committed copy current -- but the
+    //  frames have moved)
+    return rc;
+}
+
+extern "C" int vg_fe_tracks_get(vg_handle* h, int cam, vg_fe_tracks_state* st) {
+    if (!h || !h->fe || !st) return VG_ERR_BAD_ARG;
+    FeState* s = h->fe;
+    if (!s->tk || !s->tk->begun) { h->err = "vg_fe_tracks_get: no resident lists (vg_fe_tracks_begin)"; return VG_ERR_BAD_ARG; }
+    if (cam < 0 || cam >= s->cams || st->struct_size != (int)sizeof(vg_fe_tracks_state)) { h->err = "vg_fe_tracks_get: stream / struct_size"; return VG_ERR_BAD_ARG; }
+    TkState* t = s->tk;
+    const size_t cap = (size_t)s->max_pts, c = (size_t)cam;
+    const TkBuf u = tk_buf(t, t->dev[t->cur]);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int hd[TK_HDR_INTS];
+    HIPCHK(h, hipMemcpy(hd, u.hdr + c * TK_HDR_INTS, sizeof(hd), hipMemcpyDeviceToHost));
+    const int n = hd[TK_N];
+    if (n < 0 || n > (int)cap) { h->err = "vg_fe_tracks_get: inconsistent counts from the device"; return VG_ERR_NUMERIC; }
+    st->n = n; st->n_id = hd[TK_NID];
+    memcpy(&st->prev_time, hd + TK_TIME, sizeof(double));
+    if (n && st->cur_xy) HIPCHK(h, hipMemcpy(st->cur_xy, u.cur_xy + c * cap * 2, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+    if (n && st->ids) HIPCHK(h, hipMemcpy(st->ids, u.ids + c * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (n && st->track_cnt) HIPCHK(h, hipMemcpy(st->track_cnt, u.cnt + c * cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (n && st->un_xy) HIPCHK(h, hipMemcpy(st->un_xy, u.un_xy + c * cap * 2, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+    if (n && st->in_map) HIPCHK(h, hipMemcpy(st->in_map, u.in_map + c * cap, n, hipMemcpyDeviceToHost));
+    return VG_OK;
+}
+
+extern "C" int vg_fe_tracks_set(vg_handle* h, int cam, const vg_fe_tracks_state* st) {
+    if (!h || !h->fe || !st) return VG_ERR_BAD_ARG;
+    FeState* s = h->fe;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_fe_tracks_set: ") + why; return VG_ERR_BAD_ARG; };
+    if (!s->tk || !s->tk->begun) return refuse("no resident lists (vg_fe_tracks_begin)");
+    if (cam < 0 || cam >= s->cams || st->struct_size != (int)sizeof(vg_fe_tracks_state)) return refuse("stream / struct_size");
+    const int n = st->n;
+    if (n < 0 || n > s->max_pts || st->n_id < 0) return refuse("n beyond max_points of vg_fe_configure, or a negative n_id");
+    if (n && (!st->cur_xy || !st->ids || !st->track_cnt || (st->un_xy && !st->in_map))) return refuse("cur_xy / ids / track_cnt (and in_map with un_xy) are required");
+    {
+        std::vector<int> sorted(st->ids, st->ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        for (int k = 0; k < n; ++k) {
+            if (sorted[k] < 0 || sorted[k] >= st->n_id) return refuse("an id is negative or not below n_id");
+            if (k && sorted[k] == sorted[k - 1]) return refuse("an id occurs twice");
+        }
+    }
+    TkState* t = s->tk;
+    const size_t cap = (size_t)s->max_pts, c = (size_t)cam;
+    const TkBuf u = tk_buf(t, t->dev[t->cur]);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int hd[TK_HDR_INTS];
+    memset(hd, 0, sizeof(hd));
+    hd[TK_N] = n; hd[TK_NID] = st->n_id;
+    memcpy(hd + TK_TIME, &st->prev_time, sizeof(double));
+    if (n) {
+        std::vector<float> un((size_t)2 * n, 0.f);
+        std::vector<uint8_t> in_map((size_t)n, 0);
+        if (st->un_xy) {
+            memcpy(un.data(), st->un_xy, sizeof(float) * 2 * n);
+            for (int k = 0; k < n; ++k) in_map[k] = st->in_map[k] ? 1 : 0;
+        }
+        HIPCHK(h, hipMemcpy(u.cur_xy + c * cap * 2, st->cur_xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(u.ids + c * cap, st->ids, sizeof(int) * n, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(u.cnt + c * cap, st->track_cnt, sizeof(int) * n, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(u.un_xy + c * cap * 2, un.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(u.in_map + c * cap, in_map.data(), n, hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpy(u.hdr + c * TK_HDR_INTS, hd, sizeof(hd), hipMemcpyHostToDevice));
+    t->n[c] = n;
+    return VG_OK;
 }

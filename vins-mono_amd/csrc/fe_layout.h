@@ -53,6 +53,7 @@ enum {
     RI_NNEW,           // corners detected (-1: candidate list overflow)
     RI_NITERS,         // iterations that counted
     RI_MAXGOOD,        // inliers of the best model so far, carried between the two parts of the bookkeeping (more than one stream)
+    RI_STAMP = 12,     // vg_fe_tracks_step: _cur_time of the frame, a double in two ints (8-byte aligned: a stream's block is 64 bytes)
     RI_CTL_INTS = 16
 };
 #define RI_FB_COLLINEAR 1           // a sample of the point-independent schedule would have been redrawn by OpenCV
@@ -122,6 +123,33 @@ struct RbDev {
     int* kept_xy;                   // [S][cap][2]
     int* nk;                        // [S] kept points (what fe_stamp_kernel reads); 0 for a stream that does not publish
     const uint8_t* base;            // [S][H][W] fisheye masks (streams with has_base) or nullptr
+};
+// ---- vg_fe_tracks_*: the track lists of the S streams, resident between the frames.  Two copies of one block; a step reads `from` and
+// its commit kernel (fe_tk_commit_kernel, fe_frame.hip) writes `to`, which the host downloads as the step's result and makes the
+// current one when the step has succeeded.
+enum {
+    TK_N = 0,          // list length
+    TK_NID,            // n_id
+    TK_NMSG,           // entries of the message
+    TK_NK,             // points setMask kept (0 for a stream that did not publish)
+    TK_NNEW,           // corners added (-1: a detection overflowed, the step is void)
+    TK_TIME = 8,       // prev_time, a double in two ints
+    TK_HDR_INTS = 16
+};
+#define TK_MAX 2048                 // capacity of the commit kernel's LDS arrays (= the limit of the frame path on max_points)
+struct TkBuf {
+    int* hdr;                       // [S][TK_HDR_INTS]
+    int* ids;                       // [S][cap]
+    int* cnt;                       // [S][cap] track_cnt
+    float* cur_xy;                  // [S][cap][2] cur_pts (what fe_lk_kernel tracks from)
+    float* un_xy;                   // [S][cap][2] cur_un_pts
+    float* vel;                     // [S][cap][2] pts_velocity
+    uint8_t* in_map;                // [S][cap] the point is in prev_un_pts_map under its own id
+    int* msg_id;                    // [S][cap]
+    double* msg_obs;                // [S][cap][7]
+};
+struct TkDev {
+    TkBuf from, to;
 };
 // device scratch of the fundamental-matrix estimate (fe_ransac.hip), one allocation per handle
 struct FeRansacBufs {

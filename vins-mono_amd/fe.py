@@ -25,6 +25,30 @@ class FrameIn(C.Structure):
                 ("focal_length", C.c_double), ("intr", C.c_double * 8), ("base_mask", _u8), ("order", ORDER_FN), ("user", C.c_void_p)]
 
 
+TRACKS_ORDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, _i4, _i4)
+_f8 = C.POINTER(C.c_double)
+
+
+class TracksIn(C.Structure):
+    """vg_fe_tracks_in (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("img", _u8), ("stride", C.c_int), ("equalize", C.c_int), ("publish", C.c_int), ("max_cnt", C.c_int),
+                ("min_dist", C.c_int), ("quality", C.c_double), ("f_threshold", C.c_double), ("focal_length", C.c_double), ("intr", C.c_double * 8),
+                ("base_mask", _u8), ("order", TRACKS_ORDER_FN), ("user", C.c_void_p), ("stamp", C.c_double)]
+
+
+class TracksOut(C.Structure):
+    """vg_fe_tracks_out (include/vinsgpu.h)"""
+    _fields_ = [("n", C.c_int), ("n_id", C.c_int), ("n_msg", C.c_int), ("n1", C.c_int), ("n2", C.c_int), ("ransac_ran", C.c_int), ("n_kept", C.c_int),
+                ("n_new", C.c_int), ("fallback", C.c_int), ("ransac_best", C.c_int), ("ransac_niters", C.c_int),
+                ("ids", _i4), ("track_cnt", _i4), ("cur_xy", _f4), ("un_xy", _f4), ("vel_xy", _f4), ("msg_id", _i4), ("msg_obs", _f8)]
+
+
+class TracksState(C.Structure):
+    """vg_fe_tracks_state (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("n_id", C.c_int), ("prev_time", C.c_double), ("cur_xy", _f4), ("ids", _i4),
+                ("track_cnt", _i4), ("un_xy", _f4), ("in_map", _u8)]
+
+
 CAM_PINHOLE, CAM_MEI = 0, 1
 
 
@@ -84,6 +108,11 @@ class FrontEnd:
         if hasattr(L, "vg_fe_set_camera"):                # (a library built before the camera models: set_camera() / lift() raise AttributeError)
             L.vg_fe_set_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(Camera)]
             L.vg_fe_lift.argtypes = [C.c_void_p, C.POINTER(Camera), _f4, C.c_int, _f4]
+        if hasattr(L, "vg_fe_tracks_step"):               # (a library built before the resident track lists: tracks_*() raise AttributeError)
+            L.vg_fe_tracks_begin.argtypes = [C.c_void_p]
+            L.vg_fe_tracks_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(TracksIn), C.POINTER(TracksOut)]
+            L.vg_fe_tracks_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(TracksState)]
+            L.vg_fe_tracks_set.argtypes = [C.c_void_p, C.c_int, C.POINTER(TracksState)]
         self.hd._chk(L.vg_fe_configure(self.h, width, height, n_cams, max_points), "vg_fe_configure")
 
     def _imgs(self, frames):
@@ -349,6 +378,110 @@ class FrontEnd:
             out["un_xy"] = arr(o.un_xy, (o.n_final, 2))
             outs.append(out)
         return outs
+
+    # ---- track lists resident on the device
+    def tracks_begin(self):
+        """vg_fe_tracks_begin: every stream an empty list, n_id = 0, no previous map"""
+        self.hd._chk(self.lib.vg_fe_tracks_begin(self.h), "vg_fe_tracks_begin")
+
+    def tracks_step(self, imgs, stamps, publish_list, intr_list, max_cnt=150, min_dist=30, equalize=False, f_threshold=1.0, focal_length=460.0,
+                    quality=0.01, base_masks=None, orders=None, n_streams=None, struct_size=None):
+        """vg_fe_tracks_step: one frame for every stream from the resident lists.  imgs / publish_list / intr_list / the scalar options /
+        base_masks as read_image_batch; stamps: _cur_time per stream; orders[c]: None or `order(track_cnt[n2]) -> permutation of range(n2)`
+        (the incremented counts of the survivors of rejectWithF in list order).  Returns per stream a dict of numpy copies: n, n_id, ids,
+        track_cnt, cur_xy, un_xy, vel_xy, msg_id, msg_obs and the diagnostics of vg_fe_tracks_out."""
+        m = len(publish_list)
+        S = m if n_streams is None else int(n_streams)
+
+        def per(v):
+            return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * m
+
+        max_cnt, min_dist, equalize, f_threshold, focal_length, quality, stamps = [per(v) for v in (max_cnt, min_dist, equalize, f_threshold, focal_length, quality, stamps)]
+        frames = [None] * m if imgs is None else [None if f is None else np.ascontiguousarray(f, np.uint8) for f in imgs]
+        masks = [None] * m if base_masks is None else [None if b is None else np.ascontiguousarray(b, np.uint8) for b in base_masks]
+        orders = [None] * m if orders is None else list(orders)
+        assert len(frames) == m and len(intr_list) == m and len(masks) == m and len(orders) == m and len(stamps) == m
+        assert all(f is None or f.shape == (self.H, self.W) for f in frames) and all(b is None or b.shape == (self.H, self.W) for b in masks)
+        self._bkeep_batch = masks
+        tin = (TracksIn * m)()
+        cbs = []
+
+        def make_cb(order):
+            def _cb(_user, _stream, n2, cnt, out_order):
+                try:
+                    perm = np.asarray(order(np.ctypeslib.as_array(cnt, (max(n2, 1),))[:n2].copy()), np.int32)
+                    if perm.shape != (n2,):
+                        return 1
+                    for q in range(n2):
+                        out_order[q] = int(perm[q])
+                    return 0
+                except Exception:                      # (an exception must not travel through the C frames)
+                    return 1
+
+            return TRACKS_ORDER_FN(_cb)
+
+        for c in range(m):
+            f = tin[c]
+            f.struct_size = C.sizeof(TracksIn) if struct_size is None else int(struct_size)
+            f.img = frames[c].ctypes.data_as(_u8) if frames[c] is not None else None
+            f.stride = self.W; f.equalize = int(equalize[c]); f.publish = int(bool(publish_list[c]))
+            f.max_cnt = int(max_cnt[c]); f.min_dist = int(min_dist[c]); f.quality = float(quality[c])
+            f.f_threshold = float(f_threshold[c]); f.focal_length = float(focal_length[c]); f.stamp = float(stamps[c])
+            for i, v in enumerate(intr_list[c] if intr_list[c] is not None else ()):
+                f.intr[i] = float(v)
+            if masks[c] is not None:
+                f.base_mask = masks[c].ctypes.data_as(_u8)
+            cbs.append(make_cb(orders[c]) if orders[c] is not None else C.cast(None, TRACKS_ORDER_FN))
+            f.order = cbs[-1]
+        to = (TracksOut * m)()
+        self.hd._chk(self.lib.vg_fe_tracks_step(self.h, S, tin, to), "vg_fe_tracks_step")
+
+        def arr(ptr, shape, dtype):
+            k = int(np.prod(shape))
+            return np.ctypeslib.as_array(ptr, shape).copy() if k and ptr else np.zeros(shape, dtype)
+
+        outs = []
+        for c in range(m):
+            o = to[c]
+            out = {k: int(getattr(o, k)) for k in ("n", "n_id", "n_msg", "n1", "n2", "n_kept", "n_new", "fallback", "ransac_best", "ransac_niters")}
+            out["ransac_ran"] = bool(o.ransac_ran)
+            out["ids"] = arr(o.ids, (o.n,), np.int32)
+            out["track_cnt"] = arr(o.track_cnt, (o.n,), np.int32)
+            for k in ("cur_xy", "un_xy", "vel_xy"):
+                out[k] = arr(getattr(o, k), (o.n, 2), np.float32)
+            out["msg_id"] = arr(o.msg_id, (o.n_msg,), np.int32)
+            out["msg_obs"] = arr(o.msg_obs, (o.n_msg, 7), np.float64)
+            outs.append(out)
+        return outs
+
+    def tracks_get(self, cam):
+        """vg_fe_tracks_get: the list of one stream between two frames: dict(n, n_id, prev_time, cur_xy, ids, track_cnt, un_xy, in_map)"""
+        cap = self.max_pts
+        xy, un = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        ids, cnt, in_map = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+        st = TracksState()
+        st.struct_size = C.sizeof(TracksState)
+        st.cur_xy, st.ids, st.track_cnt = xy.ctypes.data_as(_f4), ids.ctypes.data_as(_i4), cnt.ctypes.data_as(_i4)
+        st.un_xy, st.in_map = un.ctypes.data_as(_f4), in_map.ctypes.data_as(_u8)
+        self.hd._chk(self.lib.vg_fe_tracks_get(self.h, int(cam), C.byref(st)), "vg_fe_tracks_get")
+        n = st.n
+        return dict(n=n, n_id=st.n_id, prev_time=st.prev_time, cur_xy=xy[:n].copy(), ids=ids[:n].copy(), track_cnt=cnt[:n].copy(),
+                    un_xy=un[:n].copy(), in_map=in_map[:n].copy())
+
+    def tracks_set(self, cam, cur_xy, ids, track_cnt, n_id, prev_time=0.0, un_xy=None, in_map=None):
+        """vg_fe_tracks_set: re-seed one stream between two frames; un_xy None: no previous map"""
+        xy = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
+        ids, cnt = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(track_cnt, np.int32)
+        assert len(ids) == len(xy) and len(cnt) == len(xy)
+        st = TracksState()
+        st.struct_size, st.n, st.n_id, st.prev_time = C.sizeof(TracksState), len(xy), int(n_id), float(prev_time)
+        st.cur_xy, st.ids, st.track_cnt = xy.ctypes.data_as(_f4), ids.ctypes.data_as(_i4), cnt.ctypes.data_as(_i4)
+        if un_xy is not None:
+            un = np.ascontiguousarray(un_xy, np.float32).reshape(-1, 2)
+            im = np.ascontiguousarray(in_map, np.uint8)
+            assert len(un) == len(xy) and len(im) == len(xy)
+            st.un_xy, st.in_map = un.ctypes.data_as(_f4), im.ctypes.data_as(_u8)
+        self.hd._chk(self.lib.vg_fe_tracks_set(self.h, int(cam), C.byref(st)), "vg_fe_tracks_set")
 
     def detect_upload(self, max_corners, masks=None):
         mc = np.ascontiguousarray(max_corners, np.int32)

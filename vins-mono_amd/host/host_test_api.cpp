@@ -316,3 +316,127 @@ extern "C" int vins_host_read_camera(const char* config_file, int* model, double
 }
 extern "C" const char* vins_host_result_path() { return VINS_RESULT_PATH.c_str(); }
 extern "C" const char* vins_host_imu_topic() { return IMU_TOPIC.c_str(); }
+
+// ---- measurement helper of tests/manual/gpu_fe_tracks.py: `steps` frames of S streams, two frames per stream alternating (published /
+// not published), timed on the host clock around calls that end in a synchronise.
+//   mode 0  what a caller has without resident lists: vg_fe_read_image_batch, then the bookkeeping of FeatureTracker and of the node per
+//           stream on the host with the reference's containers (vectors reduced in place, std::map for prev_un_pts_map and the message)
+//   mode 1  vg_fe_tracks_step
+// frames: [2][S] pointers, or NULL = the frames are resident in the two slots `slots` (vg_fe_select_frames before every call).
+// out[0] = seconds of the timed steps, out[1] = entries of the last message over all streams, out[2] = sum of their ids.
+#include <chrono>
+#include <map>
+#include <vector>
+namespace {
+struct LegStream {
+    std::vector<float> pts, un, vel;
+    std::vector<int> ids, cnt;
+    std::map<int, std::pair<float, float>> prev_map;
+    int n_id = 0;
+    double prev_time = 0.0;
+    std::vector<int> msg_id;
+    std::vector<double> msg_obs;
+};
+template <class T> void leg_reduce(std::vector<T>& v, const uint8_t* st, int n, int width) {
+    int j = 0;
+    for (int i = 0; i < n; ++i)
+        if (st[i]) { for (int w = 0; w < width; ++w) v[(size_t)j * width + w] = v[(size_t)i * width + w]; ++j; }
+    v.resize((size_t)j * width);
+}
+void leg_book(LegStream& s, const vg_fe_frame_out& o, int publish, double stamp) {
+    const int n = (int)s.ids.size();
+    s.pts.assign(o.forw_xy, o.forw_xy + 2 * n);
+    leg_reduce(s.pts, o.status_lk, n, 2); leg_reduce(s.ids, o.status_lk, n, 1); leg_reduce(s.cnt, o.status_lk, n, 1);
+    for (int& c : s.cnt) c++;
+    if (publish) {
+        if (o.ransac_ran) { leg_reduce(s.pts, o.status_f, o.n1, 2); leg_reduce(s.ids, o.status_f, o.n1, 1); leg_reduce(s.cnt, o.status_f, o.n1, 1); }
+        std::vector<float> p2; std::vector<int> i2, c2;
+        for (int k = 0; k < o.n_kept; ++k) {
+            const int q = o.kept[k];
+            p2.push_back(s.pts[2 * q]); p2.push_back(s.pts[2 * q + 1]); i2.push_back(s.ids[q]); c2.push_back(s.cnt[q]);
+        }
+        for (int k = 0; k < o.n_new; ++k) { p2.push_back(o.new_xy[2 * k]); p2.push_back(o.new_xy[2 * k + 1]); i2.push_back(-1); c2.push_back(1); }
+        s.pts.swap(p2); s.ids.swap(i2); s.cnt.swap(c2);
+    }
+    const int m = (int)s.ids.size();
+    s.un.assign(o.un_xy, o.un_xy + 2 * m);
+    std::map<int, std::pair<float, float>> cur_map;
+    for (int i = 0; i < m; ++i) cur_map.insert(std::make_pair(s.ids[i], std::make_pair(s.un[2 * i], s.un[2 * i + 1])));
+    s.vel.assign((size_t)2 * m, 0.f);
+    if (!s.prev_map.empty()) {
+        const double dt = stamp - s.prev_time;
+        for (int i = 0; i < m; ++i) {
+            if (s.ids[i] == -1) continue;
+            auto it = s.prev_map.find(s.ids[i]);
+            if (it == s.prev_map.end()) continue;
+            s.vel[2 * i] = (float)((s.un[2 * i] - it->second.first) / dt);
+            s.vel[2 * i + 1] = (float)((s.un[2 * i + 1] - it->second.second) / dt);
+        }
+    }
+    s.prev_map.swap(cur_map);
+    s.prev_time = stamp;
+    for (int i = 0; i < m; ++i)
+        if (s.ids[i] == -1) s.ids[i] = s.n_id++;
+    std::map<int, int> by_id;
+    for (int i = 0; i < m; ++i)
+        if (s.cnt[i] > 1) by_id[s.ids[i]] = i;
+    s.msg_id.clear(); s.msg_obs.clear();
+    for (const auto& kv : by_id) {
+        const int i = kv.second;
+        s.msg_id.push_back(kv.first);
+        const double row[7] = {s.un[2 * i], s.un[2 * i + 1], 1.0, s.pts[2 * i], s.pts[2 * i + 1], s.vel[2 * i], s.vel[2 * i + 1]};
+        s.msg_obs.insert(s.msg_obs.end(), row, row + 7);
+    }
+}
+}  // namespace
+
+extern "C" int vins_host_fe_tracks_leg(vg_handle* h, int S, int mode, const uint8_t* const* frames, const int* slots, int width, int max_cnt,
+                                       int min_dist, const double* intr, int warm, int steps, double* out) {
+    std::vector<LegStream> st((size_t)S);
+    std::vector<vg_fe_frame_in> fin((size_t)S);
+    std::vector<vg_fe_frame_out> fout((size_t)S);
+    std::vector<vg_fe_tracks_in> tin((size_t)S);
+    std::vector<vg_fe_tracks_out> tout((size_t)S);
+    int rc = mode ? vg_fe_tracks_begin(h) : VG_OK;
+    if (rc) return rc;
+    std::chrono::steady_clock::time_point t0;
+    // step -1: frame A published from empty lists; then B published, A not published, B published, ...
+    for (int k = -1; k < warm + steps; ++k) {
+        if (k == warm) t0 = std::chrono::steady_clock::now();
+        const int which = k < 0 ? 0 : (k % 2 == 0 ? 1 : 0), publish = k < 0 || k % 2 == 0;
+        const double stamp = 1.0 + 0.05 * (k + 1);
+        if (!frames && (rc = vg_fe_select_frames(h, slots[which])) != VG_OK) return rc;
+        for (int c = 0; c < S; ++c) {
+            const uint8_t* img = frames ? frames[(size_t)which * S + c] : nullptr;
+            if (mode) {
+                vg_fe_tracks_in& f = tin[c];
+                memset(&f, 0, sizeof(f));
+                f.struct_size = (int)sizeof(f); f.img = img; f.stride = width; f.equalize = 1; f.publish = publish; f.max_cnt = max_cnt;
+                f.min_dist = min_dist; f.quality = 0.01; f.f_threshold = 1.0; f.focal_length = 460.0; f.stamp = stamp;
+                memcpy(f.intr, intr, sizeof(f.intr));
+            } else {
+                vg_fe_frame_in& f = fin[c];
+                memset(&f, 0, sizeof(f));
+                f.struct_size = (int)sizeof(f); f.img = img; f.stride = width; f.equalize = 1; f.publish = publish; f.max_cnt = max_cnt;
+                f.min_dist = min_dist; f.quality = 0.01; f.f_threshold = 1.0; f.focal_length = 460.0;
+                f.n = (int)st[c].ids.size(); f.cur_xy = f.n ? st[c].pts.data() : nullptr;
+                memcpy(f.intr, intr, sizeof(f.intr));
+            }
+        }
+        if (mode) {
+            if ((rc = vg_fe_tracks_step(h, S, tin.data(), tout.data())) != VG_OK) return rc;
+        } else {
+            if ((rc = vg_fe_read_image_batch(h, S, fin.data(), fout.data())) != VG_OK) return rc;
+            for (int c = 0; c < S; ++c) leg_book(st[c], fout[c], publish, stamp);
+        }
+    }
+    out[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    out[1] = out[2] = 0.0;
+    for (int c = 0; c < S; ++c) {
+        const int nm = mode ? tout[c].n_msg : (int)st[c].msg_id.size();
+        const int* id = mode ? tout[c].msg_id : st[c].msg_id.data();
+        out[1] += nm;
+        for (int i = 0; i < nm; ++i) out[2] += id[i];
+    }
+    return VG_OK;
+}
