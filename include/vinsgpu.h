@@ -514,19 +514,33 @@ int vg_fe_detect_masked(vg_handle* h, int cam, int max_corners, double quality, 
  * distortion model (camera_model PinholeCamera.cc:450-510, :646-661).  intr = fx fy cx cy k1 k2 p1 p2; out = (x/z, y/z)
  * as float (cv::Point2f).  The same as vg_fe_lift with a VG_CAM_PINHOLE camera of these eight numbers. */
 int vg_fe_undistort(vg_handle* h, const float* pts_xy, int n, const double* intr, float* out_xy);
-/* ---- Camera models (added within ABI 12).  The models whose liftProjective runs on the device, in double and in the reference's
- * expression order (bit-identical to camodocal's):
+/* ---- Camera models (added within ABI 12).  The models whose liftProjective runs on the device, in double.  The first two in the
+ * reference's expression order (bit-identical to camodocal's):
  *   VG_CAM_PINHOLE  PinholeCamera (PinholeCamera.cc:450-510): what vg_fe_frame_in::intr and vg_fe_undistort describe
  *   VG_CAM_MEI      CataCamera, the unified model (CataCamera.cc:556-626): the pinhole lift with gamma1 gamma2 u0 v0, then
  *                   z = 1 - xi (rho2 + 1) / (xi + sqrt(1 + (1 - xi^2) rho2)), or (1 - rho2) / 2 when xi == 1.0
- * KANNALA_BRANDT and SCARAMUZZA are not offered (their lift is an eigenvalue problem per point). */
+ *   VG_CAM_KANNALA_BRANDT  EquidistantCamera, the equidistant fisheye (EquidistantCamera.cc:427-442, :715-818); p = mu mv u0 v0 k2 k3
+ *                   k4 k5, xi is ignored.  With (ux, uy) = ((1 / mu) px - u0 / mu, (1 / mv) py - v0 / mv) and r = |(ux, uy)|, theta is
+ *                   the root of theta + k2 theta^3 + k3 theta^5 + k4 theta^7 + k5 theta^9 = r that 10 Newton steps from theta = r
+ *                   reach (a fixed count; polynomial and derivative by Horner in theta^2), and the ray is (sin theta ux / r,
+ *                   sin theta uy / r, cos theta) -- (sin theta, 0, cos theta) when r < 1e-10 -- with the library's own sine and cosine
+ *                   (a Cody-Waite reduction by pi / 2 and Taylor polynomials, absolute error about 1e-16): emulated kernels, device and
+ *                   host class give the same bits.  The reference finds theta as the smallest non-negative real eigenvalue of the
+ *                   polynomial's companion matrix: the same number (to about 1e-14) wherever r(theta) is monotone up to the pixel, and
+ *                   (float)(x / z), (float)(y / z) then equal camodocal's up to a float ulp (tests/test_fe_kb_definition.py).  What it is
+ *                   NOT: for a pixel beyond the first maximum of r(theta), or one for which the reference finds no admissible root, the
+ *                   reference returns another branch's root or r itself; this function returns whatever Newton reaches.  Such pixels lie
+ *                   outside the calibrated image circle; the settings the reference ships (config/tum, config/cla,
+ *                   config/realsense/realsense_fisheye) have none inside their frames.
+ * The value 2 is no model.  SCARAMUZZA is not offered. */
 #define VG_CAM_PINHOLE 0
 #define VG_CAM_MEI     1
+#define VG_CAM_KANNALA_BRANDT 3
 typedef struct vg_fe_camera {
     int struct_size;             /* sizeof(vg_fe_camera) */
     int model;                   /* VG_CAM_* */
-    double p[8];                 /* PINHOLE: fx fy cx cy k1 k2 p1 p2;  MEI: gamma1 gamma2 u0 v0 k1 k2 p1 p2 */
-    double xi;                   /* MEI: mirror_parameters.xi; ignored for PINHOLE */
+    double p[8];                 /* PINHOLE: fx fy cx cy k1 k2 p1 p2;  MEI: gamma1 gamma2 u0 v0 k1 k2 p1 p2;  KANNALA_BRANDT: mu mv u0 v0 k2 k3 k4 k5 */
+    double xi;                   /* MEI: mirror_parameters.xi; ignored for PINHOLE and KANNALA_BRANDT */
 } vg_fe_camera;
 /* Set the camera of stream `cam` of a configured handle: from then on vg_fe_read_image / vg_fe_read_image_batch lift that stream's
  * points with it (rejectWithF's two point sets and undistortedPoints' list) and ignore vg_fe_frame_in::intr for that stream.

@@ -19,14 +19,14 @@
 
 #define FDEV __device__ __forceinline__
 
-// liftProjective of the stream's camera (fe_camera.h: PinholeCamera or CataCamera, the same function as fe_lift_kernel of
+// liftProjective of the stream's camera (fe_camera.h: PinholeCamera, CataCamera or EquidistantCamera, the same function as fe_lift_kernel of
 // fe_kernels.hip).  r.cam.model is uniform over the workgroup.
 FDEV void ri_lift(const RiDev& r, float px, float py, double& x, double& y, double& z) { fe_cam_lift(r.cam, px, py, x, y, z); }
 // FOCAL_LENGTH * x / z + COL / 2.0 (feature_tracker.cpp:176-187), rounded to float by cv::Point2f; the pinhole's z is 1.0
 FDEV void ri_virtual(const RiDev& r, float px, float py, float* out) {
     double x, y, z;
     ri_lift(r, px, py, x, y, z);
-    if (r.cam.model == FE_CAM_MEI) { out[0] = (float)(r.focal * x / z + r.half_w); out[1] = (float)(r.focal * y / z + r.half_h); }
+    if (r.cam.model != FE_CAM_PINHOLE) { out[0] = (float)(r.focal * x / z + r.half_w); out[1] = (float)(r.focal * y / z + r.half_h); }
     else { out[0] = (float)(r.focal * x + r.half_w); out[1] = (float)(r.focal * y + r.half_h); }
 }
 

@@ -578,12 +578,12 @@ static FeCamera fe_stream_camera(const FeState* s, int c, const double* intr) { 
 // a caller's vg_fe_camera -> FeCamera, or the reason it is refused
 static const char* fe_camera_check(const vg_fe_camera* in, FeCamera* out) {
     if (in->struct_size != (int)sizeof(vg_fe_camera)) return "struct_size is not sizeof(vg_fe_camera)";
-    if (in->model != VG_CAM_PINHOLE && in->model != VG_CAM_MEI) return "unknown camera model";
+    if (in->model != VG_CAM_PINHOLE && in->model != VG_CAM_MEI && in->model != VG_CAM_KANNALA_BRANDT) return "unknown camera model";
     for (int i = 0; i < 8; ++i)
         if (!std::isfinite(in->p[i])) return "a camera parameter is not finite";
     if (in->model == VG_CAM_MEI && !std::isfinite(in->xi)) return "xi is not finite";
     if (in->p[0] == 0.0 || in->p[1] == 0.0) return "a zero focal length (p[0] / p[1])";
-    out->model = in->model == VG_CAM_MEI ? FE_CAM_MEI : FE_CAM_PINHOLE;
+    out->model = in->model == VG_CAM_MEI ? FE_CAM_MEI : in->model == VG_CAM_KANNALA_BRANDT ? FE_CAM_KB : FE_CAM_PINHOLE;
     for (int i = 0; i < 8; ++i) out->p[i] = in->p[i];
     out->xi = in->model == VG_CAM_MEI ? in->xi : 0.0;
     return nullptr;

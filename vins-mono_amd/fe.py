@@ -49,11 +49,12 @@ class TracksState(C.Structure):
                 ("track_cnt", _i4), ("un_xy", _f4), ("in_map", _u8)]
 
 
-CAM_PINHOLE, CAM_MEI = 0, 1
+CAM_PINHOLE, CAM_MEI, CAM_KANNALA_BRANDT = 0, 1, 3
 
 
 class Camera(C.Structure):
-    """vg_fe_camera (include/vinsgpu.h): Camera.pinhole(fx, fy, cx, cy, k1, k2, p1, p2) or Camera.mei(xi, gamma1, gamma2, u0, v0, k1, k2, p1, p2)"""
+    """vg_fe_camera (include/vinsgpu.h): Camera.pinhole(fx, fy, cx, cy, k1, k2, p1, p2), Camera.mei(xi, gamma1, gamma2, u0, v0, k1, k2, p1, p2)
+    or Camera.kannala_brandt(mu, mv, u0, v0, k2, k3, k4, k5)"""
     _fields_ = [("struct_size", C.c_int), ("model", C.c_int), ("p", C.c_double * 8), ("xi", C.c_double)]
 
     @classmethod
@@ -71,6 +72,10 @@ class Camera(C.Structure):
     @classmethod
     def mei(cls, xi, *p):
         return cls.make(CAM_MEI, p, xi)
+
+    @classmethod
+    def kannala_brandt(cls, mu, mv, u0, v0, k2, k3, k4, k5):
+        return cls.make(CAM_KANNALA_BRANDT, (mu, mv, u0, v0, k2, k3, k4, k5))
 
 
 class FrontEnd:

@@ -60,7 +60,7 @@ void reduceVector(vector<int>& v, vector<uchar> status) {           // :22-29
 
 void CameraModel::liftProjective(float u, float v, double& x, double& y, double& z) const {
     FeCamera c;
-    c.model = model == VG_CAM_MEI ? FE_CAM_MEI : FE_CAM_PINHOLE;
+    c.model = model == VG_CAM_MEI ? FE_CAM_MEI : model == VG_CAM_KANNALA_BRANDT ? FE_CAM_KB : FE_CAM_PINHOLE;
     for (int i = 0; i < 8; ++i) c.p[i] = p[i];
     c.xi = xi;
     fe_cam_lift(c, u, v, x, y, z);
@@ -274,8 +274,8 @@ void FeatureTracker::readIntrinsicParameter(const string& calib_file) {
     //                       projection_parameters fx fy cx cy
     //   model_type MEI:     CataCamera::Parameters::readFromYamlFile (CataCamera.cc:161-203): mirror_parameters xi,
     //                       distortion_parameters k1 k2 p1 p2, projection_parameters gamma1 gamma2 u0 v0
-    // These two lift on the device (csrc/fe_camera.h).  KANNALA_BRANDT and SCARAMUZZA are refused by name: their lift is an eigenvalue
-    // problem per point (EquidistantCamera.cc:716-800) and is not offered.
+    // KANNALA_BRANDT and SCARAMUZZA are refused by name here; readCameraModel below reads KANNALA_BRANDT as well (it lifts on the
+    // device too, csrc/fe_camera.h) for a caller that assigns m_camera.
     VinsYaml fs;
     if (!fs.load(calib_file)) throw std::runtime_error("readIntrinsicParameter: cannot read " + calib_file);
     const std::string model = fs.str("model_type", "PINHOLE");
@@ -293,6 +293,28 @@ void FeatureTracker::readIntrinsicParameter(const string& calib_file) {
     c.p[6] = fs.number("distortion_parameters.p1"); c.p[7] = fs.number("distortion_parameters.p2");
     m_camera = c;
     camera_sent_ = false;                                                    // (a configured stream gets it with its next frame)
+}
+
+CameraModel readCameraModel(const std::string& file) {
+    // CameraFactory::generateCameraFromYamlFile with the models that lift on the device: PINHOLE and MEI as readIntrinsicParameter above,
+    // KANNALA_BRANDT as EquidistantCamera::Parameters::readFromYamlFile (EquidistantCamera.cc:146-182): projection_parameters k2 k3 k4 k5
+    // mu mv u0 v0, stored as vg_fe_camera::p takes them (mu mv u0 v0 k2 k3 k4 k5)
+    VinsYaml fs;
+    if (!fs.load(file)) throw std::runtime_error("readCameraModel: cannot read " + file);
+    const std::string model = fs.str("model_type", "PINHOLE");
+    if (model == "KANNALA_BRANDT") {
+        CameraModel c;
+        c.model = VG_CAM_KANNALA_BRANDT;
+        c.xi = 0.0;
+        const char* keys[8] = {"mu", "mv", "u0", "v0", "k2", "k3", "k4", "k5"};
+        for (int i = 0; i < 8; ++i) c.p[i] = fs.number(std::string("projection_parameters.") + keys[i]);
+        return c;
+    }
+    if (model != "PINHOLE" && model != "MEI")
+        throw std::runtime_error("readCameraModel: camera model " + model + " is not supported (PINHOLE, MEI and KANNALA_BRANDT lift on the device)");
+    FeatureTracker tr;
+    tr.readIntrinsicParameter(file);
+    return tr.m_camera;
 }
 
 void FeatureTracker::undistortedPoints() {                                   // :258-306, lifting on the device

@@ -6,9 +6,9 @@
 //   cv::calcOpticalFlowPyrLK         -> vg_fe_track                          (:113)
 //   cv::goodFeaturesToTrack          -> vg_fe_detect                         (:149)
 //   cv::findFundamentalMat(RANSAC)   -> vg_fe_reject_with_f                  (:191; deterministic RANSAC, ASSUMPTIONS F9)
-// Differences (documented in INTEGRATION.md): the camera model is CameraModel below -- PinholeCamera or CataCamera (MEI) restated
-// from camera_model/src/camera_models/{PinholeCamera,CataCamera}.cc in csrc/fe_camera.h, the function the kernels lift with --
-// instead of camodocal::CameraPtr.
+// Differences (documented in INTEGRATION.md): the camera model is CameraModel below -- PinholeCamera and CataCamera (MEI) restated
+// from camera_model/src/camera_models/{PinholeCamera,CataCamera}.cc, EquidistantCamera (KANNALA_BRANDT) by the definition of
+// csrc/fe_camera.h, the function the kernels lift with -- instead of camodocal::CameraPtr.
 #pragma once
 #include <map>
 #include <string>
@@ -32,14 +32,19 @@ bool inBorder(const cv::Point2f& pt);
 void reduceVector(vector<cv::Point2f>& v, vector<uchar> status);
 void reduceVector(vector<int>& v, vector<uchar> status);
 
-// camodocal::PinholeCamera or camodocal::CataCamera parameters; the default is config/euroc/euroc_config.yaml:13-22
+// camodocal::PinholeCamera, camodocal::CataCamera or camodocal::EquidistantCamera parameters; the default is config/euroc/euroc_config.yaml:13-22
 struct CameraModel {
     int model = VG_CAM_PINHOLE;
-    double p[8] = {461.6, 460.3, 363.0, 248.1, -2.917e-01, 8.228e-02, 5.333e-05, -1.578e-04};   // fx fy cx cy | gamma1 gamma2 u0 v0, then k1 k2 p1 p2
+    double p[8] = {461.6, 460.3, 363.0, 248.1, -2.917e-01, 8.228e-02, 5.333e-05, -1.578e-04};   // fx fy cx cy | gamma1 gamma2 u0 v0, then k1 k2 p1 p2; KANNALA_BRANDT: mu mv u0 v0 k2 k3 k4 k5
     double xi = 0.0;             // MEI: mirror_parameters.xi
     void liftProjective(float u, float v, double& x, double& y, double& z) const;     // the projective ray, as the kernels compute it
     vg_fe_camera abi() const;    // what vg_fe_set_camera / vg_fe_lift take
 };
+
+// The camera of a settings file, for a caller to assign to FeatureTracker::m_camera: PINHOLE and MEI as
+// FeatureTracker::readIntrinsicParameter reads them, and KANNALA_BRANDT (EquidistantCamera::Parameters::readFromYamlFile:
+// projection_parameters k2 k3 k4 k5 mu mv u0 v0).  Throws, naming the model, for anything else.
+CameraModel readCameraModel(const std::string& file);
 
 class FeatureTracker {
   public:

@@ -314,6 +314,25 @@ extern "C" int vins_host_read_camera(const char* config_file, int* model, double
         return -1;
     }
 }
+// The same through readCameraModel (KANNALA_BRANDT as well: *model = VG_CAM_KANNALA_BRANDT, p8 = mu mv u0 v0 k2 k3 k4 k5)
+extern "C" int vins_host_read_camera_model(const char* config_file, int* model, double* p8, double* xi) {
+    try {
+        const CameraModel c = readCameraModel(config_file);
+        *model = c.model; *xi = c.xi;
+        memcpy(p8, c.p, sizeof(c.p));
+        return 0;
+    } catch (const std::exception& e) {
+        g_last_error = e.what();
+        return -1;
+    }
+}
+// CameraModel::liftProjective for n float pixels: rays[3 i ..] = (x, y, z) in double
+extern "C" void vins_host_camera_lift(int model, const double* p8, double xi, const float* pts_xy, int n, double* rays) {
+    CameraModel c;
+    c.model = model; c.xi = xi;
+    memcpy(c.p, p8, sizeof(c.p));
+    for (int i = 0; i < n; ++i) c.liftProjective(pts_xy[2 * i], pts_xy[2 * i + 1], rays[3 * i], rays[3 * i + 1], rays[3 * i + 2]);
+}
 extern "C" const char* vins_host_result_path() { return VINS_RESULT_PATH.c_str(); }
 extern "C" const char* vins_host_imu_topic() { return IMU_TOPIC.c_str(); }
 
