@@ -30,7 +30,7 @@ extern "C" {
                              * 10: vg_config / vg_create_config; vg_ba_batch_is_fused no longer returns 2; 11: vg_fe_read_image;
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
-                             * vg_fe_tracks_begin / _step / _get / _set) */
+                             * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -349,9 +349,11 @@ int vg_ba_reserve(vg_handle* h, int max_landmarks, int max_factors, int max_obs,
  *                                         FeatureManager::removeBackShiftDepth / removeFront (feature_manager.cpp:275-351)
  *     f_manager.removeFailures            (feature_manager.cpp:161-171)
  * A sequence does all of that on the device for a batch of independent windows: the track tables, the states, the IMU constants
- * and the prior never leave HBM; per frame the host sends the new frame's observations (id + 7 doubles each), its state guess
- * (what processIMU propagated) and the pre-integration of the new interval, and reads back the states.  No per-frame packing,
- * no re-upload of the window.  Relocalisation factors and the large-window path are not offered in a sequence.              */
+ * and the prior never leave HBM; per frame the host sends the new frame's observations (id + 7 doubles each) and EITHER its
+ * state guess (what processIMU propagated) and the pre-integration of the new interval (vg_ba_seq_step_async) OR the raw IMU
+ * samples since the frame before (vg_ba_seq_step_imu_async: processIMU runs on the device too, see below), and reads back the
+ * states.  No per-frame packing, no re-upload of the window.  Relocalisation factors and the large-window path are not offered
+ * in a sequence.                                                                                                            */
 typedef struct {
     int n_features;              /* f_manager.feature.size(), list order                                                     */
     const int* feature_id;       /* FeaturePerId::feature_id                                                                 */
@@ -418,7 +420,7 @@ int vg_ba_seq_get_tracks(vg_handle* h, int window, int cap, int* n_features, int
  *   export  the window of slot `window` in the form vg_ba_seq_begin takes it -- states (K x 7, K x 9, 7, 1), the K-1 pre-integration
  *           records (the newest one is the placeholder the next step fills: valid = 0), the prior (caller-allocated as for
  *           vg_ba_optimize; n = 0: none; after a step that chose VG_MARGIN_SECOND_NEW the record of interval K-3 is still the
- *           un-merged one -- the merged record reaches the device with the next frame's imu_merged) -- together with vg_ba_seq_get_tracks this is everything the reference keeps in
+ *           un-merged one -- the merged record reaches the device with the next frame's imu_merged; a sequence in IMU mode holds the merged one already) -- together with vg_ba_seq_get_tracks this is everything the reference keeps in
  *           Ps / Rs / Vs / Bas / Bgs, pre_integrations[], f_manager.feature and last_marginalization_info: a host Estimator can
  *           take the window back (a relocalisation frame, which a sequence does not offer; a checkpoint; a failure re-start);
  *   import  replaces what slot `window` holds (same K and estimate_* options as the sequence; prior from the host or none) while
@@ -427,6 +429,66 @@ int vg_ba_seq_export(vg_handle* h, int window, double* pose, double* speedbias, 
                      vg_ba_prior* prior);
 int vg_ba_seq_import(vg_handle* h, int window, const vg_ba_problem* in, const vg_ba_tracks* tracks);
 int vg_ba_seq_end(vg_handle* h);
+
+/* ---- Sequences that take raw IMU samples: Estimator::processIMU on the device (added within ABI 12) ------------------------------
+ * With vg_ba_seq_step_async the caller still does Estimator::processIMU (estimator.cpp:84-118) and the IMU part of slideWindow()
+ * (:1069-1095) on the host: it keeps the sample buffers of the last two intervals, propagates Ps / Rs / Vs[WINDOW_SIZE],
+ * pre-integrates the new interval (vg_imu_preintegrate, a synchronous round trip), re-integrates the merged one after a dropped
+ * non-keyframe, and uploads two records of 472 doubles per window and frame.  The device holds every input of that work (the
+ * solved newest state, its biases, the record of the interval before), so a sequence switched to IMU mode takes, per frame and
+ * window, ONLY the observations and the raw samples (dt acc gyr) that arrived since the frame before -- what the estimator node
+ * receives from its two topics -- and nothing of the window's IMU data ever leaves HBM.  One vg_ba_seq_step_imu_async does
+ *   processIMU   for every sample in order: pre_integrations[WINDOW_SIZE]->push_back into a fresh record, linearised at the biases
+ *                of slot K-1 as the last slide left them and started from the resident acc_0 / gyr_0 (the arithmetic of
+ *                vg_imu_preintegrate, one shared text); the mid-point propagation of Ps / Rs / Vs[WINDOW_SIZE] (:107-114) from the
+ *                solved state of slot K-1.  The record goes to interval K-2 (valid = sum_dt <= 10), the guess to state slot K-1,
+ *                the biases of slot K-1 stay, acc_0 / gyr_0 become the last sample.
+ *                Rs: the matrix of the NORMALISED quaternion of slot K-1, multiplied per sample by the matrix of the NORMALISED
+ *                deltaQ(un_gyr dt) = (theta / 2, 1) / |.|, converted back and normalised: the project's restatement of processIMU
+ *                (oracle/window_numpy.py propagate, against which the device is tested to 1e-11).  The reference (and
+ *                host/resident_estimator.cpp on its default path) multiplies by the UN-normalised deltaQ matrix, which is not a
+ *                rotation; the two guesses differ by |theta|^3 / 4 per sample (4e-8 in the quaternion over 20 samples of a 200 Hz
+ *                EuRoC-like interval), far below what the solve that follows it resolves.
+ *   the step     of vg_ba_seq_step_async, unchanged: add, key-frame test, triangulate, build, solve, marginalization, slide.
+ *   the merge    after a step that chose VG_MARGIN_SECOND_NEW the record that is at K-3 after the slide is CONTINUED with this
+ *                frame's samples (push_back from the stored sum_dt, delta_p / q / v, jacobian, covariance, with the record's own
+ *                linearisation biases and the measurement that ended it, as estimator.cpp:1069-1081 does); valid is re-evaluated
+ *                on the merged sum_dt.  Difference to the host-fed mode: vg_ba_seq_export returns the MERGED record right after
+ *                such a step (host-fed: the un-merged one until the next frame brings imu_merged).
+ * The states come back as before (vg_ba_batch_download_state, vg_ba_seq_info). */
+typedef struct vg_ba_seq_imu_config {
+    int struct_size;             /* sizeof(vg_ba_seq_imu_config)                                                             */
+    int max_samples;             /* capacity of one frame's sample list, 1 .. 512                                            */
+    double noise[4];             /* ACC_N GYR_N ACC_W GYR_W, as vg_imu_preintegrate                                          */
+} vg_ba_seq_imu_config;
+/* After vg_ba_seq_begin, before the first step: switches the running sequence to IMU mode.  seed[w] = acc_0(3) gyr_0(3) g(3):
+ * the newest IMU measurement (Estimator::acc_0 / gyr_0) and Estimator::g of that estimator (per window: the reference refines
+ * it at initialisation).  State slot K-2 is copied into K-1 on the device (what slideWindow leaves; vg_ba_seq_import does the
+ * same in this mode), so the "frame K-1 is a placeholder" rule of vg_ba_seq_begin keeps holding for the caller. */
+int vg_ba_seq_imu_begin(vg_handle* h, int nwin, const vg_ba_seq_imu_config* cfg, const double* seed /* [nwin][9] */);
+typedef struct vg_ba_frame_imu {
+    int n_samples;               /* 1 .. max_samples.  ONE sample makes a singular covariance (the position rows of V are dt / 2
+                                  * times its velocity rows, integration_base.h:113-124): the record is exact, the solve of a
+                                  * window that holds such an interval may report VG_ERR_NUMERIC                              */
+    const double* samples;       /* n_samples x 7: dt acc gyr, in arrival order                                              */
+    int n_obs;
+    const int* feature_id;       /* ascending                                                                                */
+    const double* obs;           /* n_obs x 7, as vg_ba_frame                                                                */
+} vg_ba_frame_imu;
+/* Refused with VG_ERR_BAD_ARG before anything is uploaded (vg_last_error says why; the sequence stays usable): no
+ * vg_ba_seq_imu_begin, n_samples < 1 or > max_samples, samples NULL, a sample that is not finite, nwin other than the sequence's,
+ * ids not ascending.  vg_ba_seq_step_async is refused on a sequence in IMU mode (it would leave the resident measurement stale). */
+int vg_ba_seq_step_imu_async(vg_handle* h, int nwin, const vg_ba_frame_imu* const* frames);
+/* Parity tap and re-seed of ONE window between two frames.
+ *   get  seed9: the last measurement + g; guess_pose7 / guess_sb9: the state guess the LAST step propagated.  Any pointer may be NULL.
+ *   set  seed9, after vg_ba_seq_import of that window. */
+int vg_ba_seq_imu_get(vg_handle* h, int window, double* seed9, double* guess_pose7, double* guess_sb9);
+int vg_ba_seq_imu_set(vg_handle* h, int window, const double* seed9);
+/* Measurement tap: with timing on, every step records HIP events around ba_seq_imu_kernel and around ba_seq_merge_kernel (all
+ * windows of the batch); vg_ba_seq_imu_times waits for the last step's merge and returns the two device times in ms (either
+ * pointer may be NULL).  VG_ERR_BAD_ARG without a sequence in IMU mode, or when the last step was not timed. */
+int vg_ba_seq_imu_timing(vg_handle* h, int on);
+int vg_ba_seq_imu_times(vg_handle* h, float* imu_kernel_ms, float* merge_kernel_ms);
 
 /* Form of the prior factor the marginalization hands back (marginalization_factor.cpp:285-296 builds J0 = S^1/2 V^T,
  * r0 = S^-1/2 V^T b' from the eigen-decomposition A' = V S V^T of the kept system).  Everything downstream uses the factor

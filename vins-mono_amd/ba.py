@@ -72,6 +72,14 @@ class Frame(C.Structure):             # vg_ba_frame
                 ("imu_merged", C.POINTER(ImuPreint)), ("n_obs", C.c_int), ("feature_id", _pi), ("obs", _pd)]
 
 
+class SeqImuConfig(C.Structure):      # vg_ba_seq_imu_config
+    _fields_ = [("struct_size", C.c_int), ("max_samples", C.c_int), ("noise", C.c_double * 4)]
+
+
+class FrameImu(C.Structure):          # vg_ba_frame_imu
+    _fields_ = [("n_samples", C.c_int), ("samples", _pd), ("n_obs", C.c_int), ("feature_id", _pi), ("obs", _pd)]
+
+
 SEQ_INFO = ("flag", "n_features", "n_tracked", "n_parallax", "n_landmarks", "n_factors", "status", "n_after")
 
 
@@ -270,6 +278,13 @@ class Handle:
         L.vg_ba_seq_end.argtypes = [C.c_void_p]
         L.vg_ba_seq_export.argtypes = [C.c_void_p, C.c_int, _pd, _pd, _pd, _pd, C.POINTER(ImuPreint), C.POINTER(Prior)]
         L.vg_ba_seq_import.argtypes = [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Tracks)]
+        if hasattr(L, "vg_ba_seq_imu_begin"):             # (added within ABI 12: tests/manual/bench_with_lib.py loads older builds)
+            L.vg_ba_seq_imu_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(SeqImuConfig), _pd]
+            L.vg_ba_seq_step_imu_async.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(FrameImu))]
+            L.vg_ba_seq_imu_get.argtypes = [C.c_void_p, C.c_int, _pd, _pd, _pd]
+            L.vg_ba_seq_imu_set.argtypes = [C.c_void_p, C.c_int, _pd]
+            L.vg_ba_seq_imu_timing.argtypes = [C.c_void_p, C.c_int]
+            L.vg_ba_seq_imu_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -587,15 +602,16 @@ class Handle:
         m = n.value
         return dict(id=ids[:m].copy(), start=st[:m].copy(), nobs=nb[:m].copy(), solve_flag=fl[:m].copy(), depth=dep[:m].copy(), obs=obs[:m].copy())
 
-    def seq_export(self, w, K):
-        """The window of slot w between two frames, as vg_ba_seq_begin takes it: (prob-dict fields, tracks dict)."""
+    def seq_export(self, w, K, raw_imu=False):
+        """The window of slot w between two frames, as vg_ba_seq_begin takes it: (prob-dict fields, tracks dict).
+        raw_imu: parity tap -- every record as the device holds it, with its `valid` flag (otherwise an invalid one is None)."""
         o = _Out(K, 0, False, True)
         imu = (ImuPreint * (K - 1))()
         self._chk(self.lib.vg_ba_seq_export(self.h, int(w), _dp(o.pose), _dp(o.sb), _dp(o.ex), _dp(o.td), imu, C.byref(o.prior)), "vg_ba_seq_export")
         recs = []
         for q in imu:
-            recs.append(None if not q.valid else dict(
-                sum_dt=q.sum_dt, delta_p=np.array(q.delta_p), delta_q=np.array(q.delta_q), delta_v=np.array(q.delta_v), lin_ba=np.array(q.linearized_ba),
+            recs.append(None if not (q.valid or raw_imu) else dict(
+                **(dict(valid=int(q.valid)) if raw_imu else {}), sum_dt=q.sum_dt, delta_p=np.array(q.delta_p), delta_q=np.array(q.delta_q), delta_v=np.array(q.delta_v), lin_ba=np.array(q.linearized_ba),
                 lin_bg=np.array(q.linearized_bg), jacobian=np.array(q.jacobian).reshape(15, 15), covariance=np.array(q.covariance).reshape(15, 15)))
         t = self.seq_tracks(w, K)
         rows = np.concatenate([t['obs'][f, :n][:, [0, 1, 7, 2, 3, 4, 5, 6]] for f, n in enumerate(t['nobs'])]) if len(t['id']) else np.zeros((0, 8))
@@ -615,6 +631,61 @@ class Handle:
         t.solve_flag = _ip(a['flag']) if a['flag'] is not None else None
         t.depth, t.obs = _dp(a['depth']), _dp(a['obs'])
         self._chk(self.lib.vg_ba_seq_import(self.h, int(w), C.byref(p.struct), C.byref(t)), "vg_ba_seq_import")
+
+    # ---- sequences that take raw IMU samples (include/vinsgpu.h vg_ba_seq_imu_*): processIMU on the device
+    def seq_imu_begin(self, seeds, noise, max_samples=64, struct_size=None):
+        """After seq_begin, before the first step.  seeds[w] = acc_0 (3), gyr_0 (3), g (3): the newest IMU measurement and the gravity
+        vector of window w; noise = (acc_n, gyr_n, acc_w, gyr_w); max_samples: capacity of one frame's sample list (1 .. 512)."""
+        s = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 9)
+        cfg = SeqImuConfig(C.sizeof(SeqImuConfig) if struct_size is None else int(struct_size), int(max_samples))
+        cfg.noise[:] = [float(x) for x in noise]
+        self._chk(self.lib.vg_ba_seq_imu_begin(self.h, len(s), C.byref(cfg), _dp(s)), "vg_ba_seq_imu_begin")
+
+    @staticmethod
+    def seq_pack_frames_imu(frames):
+        """The vg_ba_frame_imu* array of one step: frames[w] = dict(samples (n, 7) [dt acc gyr] in arrival order, ids (m,),
+        obs (m, 7) [x y z u v vx vy])."""
+        n = len(frames)
+        fs, keep = (FrameImu * n)(), []
+        for w, f in enumerate(frames):
+            ids = np.ascontiguousarray(f['ids'], dtype=np.int32)
+            obs = np.ascontiguousarray(f['obs'], dtype=np.float64).reshape(-1, 7)
+            smp = None if f['samples'] is None else np.ascontiguousarray(f['samples'], dtype=np.float64).reshape(-1, 7)
+            keep.append((ids, obs, smp))
+            fs[w].n_samples = int(f['n_samples']) if 'n_samples' in f else (0 if smp is None else len(smp))
+            fs[w].samples = _dp(smp) if smp is not None and smp.size else None
+            fs[w].n_obs = len(ids)
+            fs[w].feature_id, fs[w].obs = _ip(ids), _dp(obs)
+        fp = (C.POINTER(FrameImu) * n)(*[C.pointer(fs[w]) for w in range(n)])
+        return (n, fp, fs, keep)
+
+    def seq_step_imu(self, frames):
+        """One frame for every window from its raw IMU samples and observations (vg_ba_seq_step_imu_async); frames: a list of
+        dicts or the result of seq_pack_frames_imu."""
+        packed = frames if isinstance(frames, tuple) else self.seq_pack_frames_imu(frames)
+        self._chk(self.lib.vg_ba_seq_step_imu_async(self.h, packed[0], packed[1]), "vg_ba_seq_step_imu_async")
+
+    def seq_imu_get(self, w):
+        """parity tap: dict(acc_0, gyr_0, g: the resident measurement and gravity; pose (7,), sb (9,): the state guess the LAST step
+        propagated)."""
+        seed, pose, sb = np.zeros(9), np.zeros(7), np.zeros(9)
+        self._chk(self.lib.vg_ba_seq_imu_get(self.h, int(w), _dp(seed), _dp(pose), _dp(sb)), "vg_ba_seq_imu_get")
+        return dict(acc_0=seed[:3].copy(), gyr_0=seed[3:6].copy(), g=seed[6:].copy(), pose=pose, sb=sb)
+
+    def seq_imu_set(self, w, seed):
+        """acc_0, gyr_0, g of ONE window, after seq_import of that window."""
+        s = np.ascontiguousarray(seed, dtype=np.float64).reshape(9)
+        self._chk(self.lib.vg_ba_seq_imu_set(self.h, int(w), _dp(s)), "vg_ba_seq_imu_set")
+
+    def seq_imu_timing(self, on=True):
+        """HIP events around ba_seq_imu_kernel and ba_seq_merge_kernel of every following step (vg_ba_seq_imu_timing)."""
+        self._chk(self.lib.vg_ba_seq_imu_timing(self.h, 1 if on else 0), "vg_ba_seq_imu_timing")
+
+    def seq_imu_times(self):
+        """(ms in ba_seq_imu_kernel, ms in ba_seq_merge_kernel) of the last step, all windows of the batch."""
+        a, b = C.c_float(), C.c_float()
+        self._chk(self.lib.vg_ba_seq_imu_times(self.h, C.byref(a), C.byref(b)), "vg_ba_seq_imu_times")
+        return float(a.value), float(b.value)
 
     def seq_end(self):
         self._chk(self.lib.vg_ba_seq_end(self.h), "vg_ba_seq_end")

@@ -1317,14 +1317,20 @@ extern "C" int vg_ba_reserve(vg_handle* h, int max_landmarks, int max_factors, i
 // ---- windows that stay on the device from frame to frame (kernels: csrc/ba_seq.hip) ---------------------------------------
 extern "C" hipError_t ba_seq_launch_front(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int cur, hipStream_t stream);
 extern "C" hipError_t ba_seq_launch_slide(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int cur, hipStream_t stream);
+extern "C" hipError_t ba_seq_launch_imu(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, hipStream_t stream);
+extern "C" hipError_t ba_seq_launch_merge(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, hipStream_t stream);
+extern "C" hipError_t ba_seq_launch_imu_seed(const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int w0, int n, hipStream_t stream);
 extern "C" int ba_seq_limits(int* ft_max, int* nin_max, int* hdr_ints, int* in_rows_off);
 
 static void seq_free(BaSeq& Q) {
     SeqDev& D = Q.D;
     for (int k = 0; k < 2; ++k) { (void)hipFree(D.ft_i[k]); (void)hipFree(D.ft_d[k]); D.ft_i[k] = nullptr; D.ft_d[k] = nullptr; }
-    (void)hipFree(D.sp); (void)hipFree(D.in_i); (void)hipFree(D.in_d); (void)hipFree(D.info);
-    D.sp = nullptr; D.in_i = nullptr; D.in_d = nullptr; D.info = nullptr;
+    (void)hipFree(D.sp); (void)hipFree(D.in_i); (void)hipFree(D.in_d); (void)hipFree(D.info); (void)hipFree(D.imu_st);
+    D.sp = nullptr; D.in_i = nullptr; D.in_d = nullptr; D.info = nullptr; D.imu_st = nullptr;
+    D.imu_mode = 0; D.MS = 0;
     Q.h_in_i.release(); Q.h_in_d.release(); Q.h_info.release();
+    for (hipEvent_t& ev : Q.ev_imu) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    Q.imu_timing = Q.imu_timed = false;
     Q.active = false;
 }
 extern "C" void ba_seq_release(vg_handle* h) { seq_free(h->ba.seq); }
@@ -1411,6 +1417,7 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
     D.fi_stride = up(hdr_ints + 5 * FT, 8);
     D.fd_stride = up(FT + FT * K * 8, 8);
     D.ii_stride = up(8 + NIN, 8);
+    D.rows_off = rows_off;
     D.id_stride = up(rows_off + NIN * 8, 8);
     D.sp_stride = up(2 + 2 * (K + 4), 8);
     D.max_iters = windows[0]->max_iters; D.marg_mode = B.marg_mode;
@@ -1445,6 +1452,8 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
     return VG_OK;
 }
 
+static int seq_launch_step(vg_handle* h, const SeqDev& D);
+
 extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* const* frames) {
     VG_RANGE("vg_ba_seq_step_async");
     if (!h || !frames) return VG_ERR_BAD_ARG;
@@ -1452,8 +1461,11 @@ extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* c
     BaSeq& Q = B.seq;
     if (!Q.active || !B.uploaded || nwin != Q.nwin || nwin != B.nwin) { h->err = "vg_ba_seq_step_async: no sequence with that many windows"; return VG_ERR_BAD_ARG; }
     const SeqDev& D = Q.D;
-    int rows_off = 0;
-    (void)ba_seq_limits(nullptr, nullptr, nullptr, &rows_off);
+    if (D.imu_mode) {
+        h->err = "vg_ba_seq_step_async: this sequence takes raw IMU samples (vg_ba_seq_step_imu_async): a host-fed frame would leave the resident measurement stale";
+        return VG_ERR_BAD_ARG;
+    }
+    const int rows_off = D.rows_off;
     for (int w = 0; w < nwin; ++w) {
         const vg_ba_frame* f = frames[w];
         if (!f || !f->imu_new || f->n_obs < 0 || (f->n_obs > 0 && (!f->feature_id || !f->obs))) return VG_ERR_BAD_ARG;
@@ -1487,10 +1499,26 @@ extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* c
         if (f->imu_merged) put_imu(d + 16 + BA_IMU_STRIDE, *f->imu_merged);
         for (int k = 0; k < f->n_obs; ++k) { memcpy(d + rows_off + (size_t)k * 8, f->obs + (size_t)k * 7, 7 * 8); d[rows_off + (size_t)k * 8 + 7] = 0.0; }
     });
+    return seq_launch_step(h, D);
+}
+
+// the packed frame staging of every window goes up, then the kernels of one frame.  D: the sequence's SeqDev with the staging
+// strides of THIS step (the kernels get it by value)
+static int seq_launch_step(vg_handle* h, const SeqDev& D) {
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    hipError_t e;
     HIPCHK(h, hipMemcpyAsync(D.in_i, Q.h_in_i.data(), Q.h_in_i.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(D.in_d, Q.h_in_d.data(), Q.h_in_d.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_join, h->stream));
-    hipError_t e = ba_seq_launch_front(B.L, B.dL, B.P, D, Q.cur, h->stream);
+    const bool timed = D.imu_mode && Q.imu_timing;
+    if (D.imu_mode) {
+        if (timed) HIPCHK(h, hipEventRecord(Q.ev_imu[0], h->stream));
+        e = ba_seq_launch_imu(B.L, B.dL, B.P, D, h->stream);
+        if (e != hipSuccess) { h->err = std::string("launch of the sequence IMU kernel: ") + hipGetErrorString(e); return VG_ERR_HIP; }
+        if (timed) HIPCHK(h, hipEventRecord(Q.ev_imu[1], h->stream));
+    }
+    e = ba_seq_launch_front(B.L, B.dL, B.P, D, Q.cur, h->stream);
     if (e != hipSuccess) { h->err = std::string("launch of the sequence front kernels: ") + hipGetErrorString(e); return VG_ERR_HIP; }
     int rc = launch_solve_in_mode(h);
     if (rc) return rc;
@@ -1501,9 +1529,139 @@ extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* c
     e = ba_launch_carry_prior(B.nwin, B.P.mout, B.P.miout, B.L.mo_J0, B.L.mo_r0, B.L.mo_x0, B.L.mo_stride, B.L.mi_stride, B.L.mcap,
                               9 * (B.L.K + 4), B.P.pri, B.L.po_x0, B.L.po_r0, B.L.po_J0, B.L.pld, B.L.pstride, h->stream);
     if (e == hipSuccess) e = ba_seq_launch_slide(B.L, B.dL, B.P, D, Q.cur, h->stream);
+    if (e == hipSuccess && timed) e = hipEventRecord(Q.ev_imu[2], h->stream);
+    if (e == hipSuccess && D.imu_mode) e = ba_seq_launch_merge(B.L, B.dL, B.P, D, h->stream);
+    if (e == hipSuccess && timed) e = hipEventRecord(Q.ev_imu[3], h->stream);
     if (e != hipSuccess) { h->err = std::string("launch of the sequence slide kernels: ") + hipGetErrorString(e); return VG_ERR_HIP; }
+    Q.imu_timed = timed;
     Q.cur ^= 1;
     B.mout_pending = false;                                      // (carried already; the slots' host mirror is not maintained in a sequence)
+    return VG_OK;
+}
+
+// ---- raw IMU samples in, processIMU on the device (ba_seq_imu_kernel / ba_seq_merge_kernel) ------------------------------------
+extern "C" int vg_ba_seq_imu_begin(vg_handle* h, int nwin, const vg_ba_seq_imu_config* cfg, const double* seed) {
+    VG_RANGE("vg_ba_seq_imu_begin");
+    if (!h || !cfg || !seed) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    SeqDev& D = Q.D;
+    if (!Q.active || !B.uploaded || nwin != Q.nwin || nwin != B.nwin) { h->err = "vg_ba_seq_imu_begin: no sequence with that many windows"; return VG_ERR_BAD_ARG; }
+    if (cfg->struct_size != (int)sizeof(vg_ba_seq_imu_config)) { h->err = "vg_ba_seq_imu_begin: vg_ba_seq_imu_config::struct_size is not sizeof(vg_ba_seq_imu_config)"; return VG_ERR_BAD_ARG; }
+    if (cfg->max_samples < 1 || cfg->max_samples > 512) { h->err = "vg_ba_seq_imu_begin: max_samples outside 1 .. 512"; return VG_ERR_BAD_ARG; }
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(cfg->noise[k])) { h->err = "vg_ba_seq_imu_begin: a noise density is not finite"; return VG_ERR_BAD_ARG; }
+    for (size_t k = 0; k < (size_t)nwin * 9; ++k) if (!std::isfinite(seed[k])) { h->err = "vg_ba_seq_imu_begin: a seed value is not finite"; return VG_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the frame staging of this mode: [samples max_samples x 7 | rows max_new_obs x 8] per window
+    const int rows_off = up(7 * cfg->max_samples, 8), id_stride = up(rows_off + D.NIN * 8, 8);
+    double* in_d = nullptr;
+    double* st = nullptr;
+    HIPCHK(h, hipMalloc((void**)&in_d, (size_t)nwin * id_stride * sizeof(double)));
+    if (hipMalloc((void**)&st, (size_t)nwin * SEQ_IMU_ST * sizeof(double)) != hipSuccess) { (void)hipFree(in_d); h->err = "vg_ba_seq_imu_begin: out of device memory"; return VG_ERR_HIP; }
+    std::vector<double> hs((size_t)nwin * SEQ_IMU_ST, 0.0);
+    for (int w = 0; w < nwin; ++w) memcpy(hs.data() + (size_t)w * SEQ_IMU_ST, seed + (size_t)w * 9, 9 * sizeof(double));
+    (void)hipFree(D.in_d); (void)hipFree(D.imu_st);
+    D.in_d = in_d; D.imu_st = st;
+    D.rows_off = rows_off; D.id_stride = id_stride; D.MS = cfg->max_samples; D.imu_mode = 1;
+    memcpy(D.noise, cfg->noise, sizeof(D.noise));
+    HIPCHK(h, hipMemcpy(D.imu_st, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, ba_seq_launch_imu_seed(B.dL, B.P, D, 0, nwin, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return VG_OK;
+}
+
+extern "C" int vg_ba_seq_step_imu_async(vg_handle* h, int nwin, const vg_ba_frame_imu* const* frames) {
+    VG_RANGE("vg_ba_seq_step_imu_async");
+    if (!h || !frames) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    if (!Q.active || !B.uploaded || nwin != Q.nwin || nwin != B.nwin) { h->err = "vg_ba_seq_step_imu_async: no sequence with that many windows"; return VG_ERR_BAD_ARG; }
+    const SeqDev& D0 = Q.D;
+    if (!D0.imu_mode) { h->err = "vg_ba_seq_step_imu_async: vg_ba_seq_imu_begin has not been called for this sequence"; return VG_ERR_BAD_ARG; }
+    for (int w = 0; w < nwin; ++w) {
+        const vg_ba_frame_imu* f = frames[w];
+        if (!f || f->n_obs < 0 || (f->n_obs > 0 && (!f->feature_id || !f->obs))) { h->err = "vg_ba_seq_step_imu_async: a frame or its observation arrays are missing"; return VG_ERR_BAD_ARG; }
+        if (f->n_samples < 1 || !f->samples) { h->err = "vg_ba_seq_step_imu_async: a frame needs at least one IMU sample"; return VG_ERR_BAD_ARG; }
+        if (f->n_samples > D0.MS) { h->err = "vg_ba_seq_step_imu_async: more samples than vg_ba_seq_imu_config::max_samples"; return VG_ERR_BAD_ARG; }
+        for (int k = 0; k < 7 * f->n_samples; ++k)
+            if (!std::isfinite(f->samples[k])) { h->err = "vg_ba_seq_step_imu_async: an IMU sample is not finite"; return VG_ERR_BAD_ARG; }
+        if (f->n_obs > D0.NIN) { h->err = "vg_ba_seq_step_imu_async: more observations than vg_ba_seq_config::max_new_obs"; return VG_ERR_UNSUPPORTED; }
+        for (int k = 1; k < f->n_obs; ++k)
+            if (f->feature_id[k] <= f->feature_id[k - 1]) { h->err = "vg_ba_seq_step_imu_async: feature ids of a frame must be strictly ascending"; return VG_ERR_BAD_ARG; }
+    }
+    // the staging is packed at the strides THIS step needs (largest sample and observation count of the batch), not at the
+    // capacities: what goes up per window is up8(7 max n_samples) + 8 max n_obs doubles and 8 + max n_obs ints
+    int ns_max = 1, no_max = 0;
+    for (int w = 0; w < nwin; ++w) { ns_max = std::max(ns_max, frames[w]->n_samples); no_max = std::max(no_max, frames[w]->n_obs); }
+    SeqDev S = Q.D;
+    S.rows_off = up(7 * ns_max, 8);
+    S.id_stride = up(S.rows_off + no_max * 8, 8);
+    S.ii_stride = up(8 + no_max, 8);
+    if (S.rows_off > Q.D.rows_off || S.id_stride > Q.D.id_stride || S.ii_stride > Q.D.ii_stride) { h->err = "vg_ba_seq_step_imu_async: staging layout beyond its capacity"; return VG_ERR_BAD_ARG; }
+    const SeqDev& D = S;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipEventSynchronize(h->ev_join));                  // the staging buffers are re-used (as in vg_ba_seq_step_async)
+    HIPCHK(h, Q.h_in_i.resize((size_t)nwin * D.ii_stride));
+    HIPCHK(h, Q.h_in_d.resize((size_t)nwin * D.id_stride));
+    tl_pack_cap = h->ba.pack_threads;
+    for_windows(nwin, [&](int, int w) {
+        const vg_ba_frame_imu* f = frames[w];
+        int* i = Q.h_in_i.data() + (size_t)w * D.ii_stride;
+        double* d = Q.h_in_d.data() + (size_t)w * D.id_stride;
+        i[0] = f->n_obs; i[1] = i[2] = i[3] = 0;
+        i[4] = f->n_samples; i[5] = i[6] = i[7] = 0;
+        memcpy(i + 8, f->feature_id, sizeof(int) * f->n_obs);
+        memcpy(d, f->samples, sizeof(double) * 7 * f->n_samples);
+        for (int k = 0; k < f->n_obs; ++k) { memcpy(d + D.rows_off + (size_t)k * 8, f->obs + (size_t)k * 7, 7 * 8); d[D.rows_off + (size_t)k * 8 + 7] = 0.0; }
+    });
+    return seq_launch_step(h, D);
+}
+
+extern "C" int vg_ba_seq_imu_get(vg_handle* h, int window, double* seed9, double* guess_pose7, double* guess_sb9) {
+    if (!h) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    if (!Q.active || !Q.D.imu_mode || window < 0 || window >= Q.nwin) { h->err = "vg_ba_seq_imu_get: no such window of a sequence that takes raw IMU samples"; return VG_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    double st[SEQ_IMU_ST];
+    HIPCHK(h, hipMemcpy(st, Q.D.imu_st + (size_t)window * SEQ_IMU_ST, sizeof(st), hipMemcpyDeviceToHost));
+    if (seed9) memcpy(seed9, st, 9 * sizeof(double));
+    if (guess_pose7) memcpy(guess_pose7, st + 16, 7 * sizeof(double));
+    if (guess_sb9) memcpy(guess_sb9, st + 23, 9 * sizeof(double));
+    return VG_OK;
+}
+
+extern "C" int vg_ba_seq_imu_timing(vg_handle* h, int on) {
+    if (!h) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    if (!Q.active || !Q.D.imu_mode) { h->err = "vg_ba_seq_imu_timing: no sequence that takes raw IMU samples"; return VG_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (on) for (hipEvent_t& ev : Q.ev_imu) if (!ev) HIPCHK(h, hipEventCreate(&ev));
+    Q.imu_timing = on != 0;
+    if (!on) Q.imu_timed = false;
+    return VG_OK;
+}
+
+extern "C" int vg_ba_seq_imu_times(vg_handle* h, float* imu_ms, float* merge_ms) {
+    if (!h) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    if (!Q.active || !Q.D.imu_mode || !Q.imu_timed) { h->err = "vg_ba_seq_imu_times: the last step was not timed (vg_ba_seq_imu_timing)"; return VG_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipEventSynchronize(Q.ev_imu[3]));
+    if (imu_ms) HIPCHK(h, hipEventElapsedTime(imu_ms, Q.ev_imu[0], Q.ev_imu[1]));
+    if (merge_ms) HIPCHK(h, hipEventElapsedTime(merge_ms, Q.ev_imu[2], Q.ev_imu[3]));
+    return VG_OK;
+}
+
+extern "C" int vg_ba_seq_imu_set(vg_handle* h, int window, const double* seed9) {
+    if (!h || !seed9) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    if (!Q.active || !Q.D.imu_mode || window < 0 || window >= Q.nwin) { h->err = "vg_ba_seq_imu_set: no such window of a sequence that takes raw IMU samples"; return VG_ERR_BAD_ARG; }
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(seed9[k])) { h->err = "vg_ba_seq_imu_set: a seed value is not finite"; return VG_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(Q.D.imu_st + (size_t)window * SEQ_IMU_ST, seed9, 9 * sizeof(double), hipMemcpyHostToDevice));
     return VG_OK;
 }
 
@@ -1642,5 +1800,9 @@ extern "C" int vg_ba_seq_import(vg_handle* h, int window, const vg_ba_problem* p
     seq_fill_tracks(t, FT, K, hdr_ints, ti.data(), td.data());
     HIPCHK(h, hipMemcpy(D.ft_i[Q.cur] + (size_t)window * D.fi_stride, ti.data(), ti.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(D.ft_d[Q.cur] + (size_t)window * D.fd_stride, td.data(), td.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (D.imu_mode) {                                            // the newest slot as slideWindow leaves it: the device propagates from there
+        HIPCHK(h, ba_seq_launch_imu_seed(B.dL, B.P, D, window, 1, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
     return VG_OK;
 }

@@ -20,6 +20,9 @@
 //                        pre-integration shift for both flags), FeatureManager::removeBackShiftDepth / removeFront
 //                        (feature_manager.cpp:275-351), removeFailures (:161-171); the new prior's block table.
 //
+// A sequence that takes raw IMU samples (vg_ba_seq_imu_begin) runs ba_seq_imu_kernel in front of all this and ba_seq_merge_kernel
+// behind it: Estimator::processIMU (estimator.cpp:84-118) and the IMU part of slideWindow() (:1069-1095) on the device.
+//
 // One workgroup per window.  The track table is a plain ordered list (ints: id, start_frame, n_obs, solve_flag, landmark index in
 // the current problem; doubles: estimated_depth and K rows of 8 per track); the slide writes the surviving tracks, compacted in
 // order, into the window's second table, so no kernel moves rows in place.  Order matters: it is the order of para_Feature.
@@ -27,6 +30,7 @@
 #include "ba_math.h"
 #include "tri_dlt.h"
 #include "ba_layout.h"
+#include "imu_step.h"
 #include "vg_handle.h"
 #include "../../include/vinsgpu.h"
 
@@ -87,7 +91,7 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_add_kernel(const BaL
     const int* ii = S.in_i + (size_t)w * S.ii_stride;
     const double* idd = S.in_d + (size_t)w * S.id_stride;
     const int* inid = ii + 8;
-    const double* rows = idd + SEQ_IN_ROWS;
+    const double* rows = idd + S.rows_off;
     int* info = S.info + (size_t)w * VG_SEQ_INFO_INTS;
     const int n = T.hdr[0];
     int nin = ii[0];
@@ -164,6 +168,9 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_add_kernel(const BaL
     }
     // ---- what processIMU produced (estimator.cpp:83-117): state of the new frame, pre_integrations[WINDOW_SIZE]; after a dropped
     //      non-keyframe also the merged pre_integrations[WINDOW_SIZE - 1] (:1069-1085)
+    //      (a sequence that takes raw samples has all of this from ba_seq_imu_kernel / ba_seq_merge_kernel already: its staging
+    //      holds samples where a host-fed one holds the records)
+    if (S.imu_mode) return;
     if (tid < 7) di[L.do_pose + 7 * WS + tid] = idd[SEQ_IN_POSE + tid];
     if (tid >= 32 && tid < 41) di[L.do_sb + 9 * WS + (tid - 32)] = idd[SEQ_IN_SB + (tid - 32)];
     for (int e = tid; e < 467; e += SEQ_NT) di[L.do_imu + (size_t)(K - 2) * BA_IMU_STRIDE + e] = idd[SEQ_IN_IMU_NEW + e];
@@ -466,6 +473,138 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_slide_kernel(const B
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// Estimator::processIMU (estimator.cpp:84-118) for the samples of one frame, one wavefront per window, in front of ba_seq_add_kernel:
+// pre_integrations[WINDOW_SIZE]->push_back into a fresh record (csrc/imu_step.h: the arithmetic of vg_imu_preintegrate) linearised at
+// the biases of slot K-1 and started from the resident acc_0 / gyr_0, beside it the mid-point propagation of Ps / Rs / Vs[WINDOW_SIZE]
+// (:107-114; wave-uniform 3x3 work that the compiler schedules into the LDS waits of the 15x15 products).  Rs is the matrix of the
+// normalised quaternion of slot K-1, multiplied per sample by the matrix of the normalised deltaQ (the project's restatement,
+// oracle/window_numpy.py propagate), and goes back as a normalised quaternion.
+// rotation matrix -> quaternion with w >= 0 wherever w resolves (the convention of the project's restatement, synth._R2q: a
+// guess whose quaternion keeps its sign from frame to frame; Eigen's conversion (R_to_q) takes over for w < 1e-3)
+DEV void R_to_q_wpos(const double* m, double* q) {
+    const double w = sqrt(fmax(1e-300, 1 + m[0] + m[4] + m[8])) / 2;
+    if (w > 1e-3) {
+        q[0] = (m[7] - m[5]) / (4 * w); q[1] = (m[2] - m[6]) / (4 * w); q[2] = (m[3] - m[1]) / (4 * w); q[3] = w;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[i * 4]) i = 2;
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        double t = sqrt(m[i * 4] - m[j * 4] - m[k * 4] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[k * 3 + j] - m[j * 3 + k]) * t;
+        q[j] = (m[j * 3 + i] + m[i * 3 + j]) * t;
+        q[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
+    }
+}
+
+extern "C" __global__ __launch_bounds__(64) void ba_seq_imu_kernel(const BaLayout* __restrict__ Lp, BaPtrs P, SeqDev S) {
+    __shared__ ImuPreLds s;
+    const BaLayout& L = *Lp;
+    const int w = blockIdx.x, lane = threadIdx.x, K = S.K;
+    int* ia = P.iarr + (size_t)w * L.istride;
+    double* di = P.din + (size_t)w * L.dstride;
+    const double* smp = S.in_d + (size_t)w * S.id_stride;
+    double* st = S.imu_st + (size_t)w * SEQ_IMU_ST;
+    double* xp = di + L.do_pose + 7 * (K - 1);
+    double* xs = di + L.do_sb + 9 * (K - 1);
+    int ns = S.in_i[(size_t)w * S.ii_stride + 4];
+    if (ns > S.MS) ns = S.MS;                                             // (the host refuses such a frame)
+    double first[6], bias[6], g[3], Pw[3], Vw[3], R[9];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { first[i] = st[i]; bias[i] = xs[3 + i]; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { g[i] = st[6 + i]; Pw[i] = xp[i]; Vw[i] = xs[i]; }
+    {
+        double q[4] = {xp[3], xp[4], xp[5], xp[6]};
+        q_normalize(q);
+        q_to_R(q, R);
+    }
+    ImuRun r;
+    imu_enter(s, r, nullptr, first, bias, S.noise[0], S.noise[1], S.noise[2], S.noise[3], lane);
+    for (int k = 0; k < ns; ++k) {
+        const double* sm = smp + (size_t)k * 7;
+        {   // Ps / Rs / Vs[WINDOW_SIZE] (:107-114), from acc_0 / gyr_0 as they are BEFORE push_back moves them on
+            const double dt = sm[0];
+            const double a0[3] = {r.acc0[0] - r.ba[0], r.acc0[1] - r.ba[1], r.acc0[2] - r.ba[2]};
+            const double a1[3] = {sm[1] - r.ba[0], sm[2] - r.ba[1], sm[3] - r.ba[2]};
+            double u0[3], u1[3], dR[9], Rn[9];
+            m3_vec(R, a0, u0);
+            double dq[4] = {(0.5 * (r.gyr0[0] + sm[4]) - r.bg[0]) * dt / 2, (0.5 * (r.gyr0[1] + sm[5]) - r.bg[1]) * dt / 2,
+                            (0.5 * (r.gyr0[2] + sm[6]) - r.bg[2]) * dt / 2, 1.0};
+            q_normalize(dq);
+            q_to_R(dq, dR);
+            m3_mul(R, dR, Rn);
+            m3_vec(Rn, a1, u1);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const double ua = 0.5 * ((u0[i] - g[i]) + (u1[i] - g[i]));
+                Pw[i] = Pw[i] + dt * Vw[i] + 0.5 * dt * dt * ua;
+                Vw[i] = Vw[i] + dt * ua;
+            }
+        }
+        imu_push_back(s, r, sm, lane);
+    }
+    imu_leave(s, r, di + L.do_imu + (size_t)(K - 2) * BA_IMU_STRIDE, lane);
+    if (lane == 1) ia[L.io_imu_valid + (K - 2)] = (r.sum_dt <= 10.0) ? 1 : 0;
+    if (lane == 0) {
+        double q[4];
+        R_to_q_wpos(R, q);
+        q_normalize(q);
+        for (int i = 0; i < 3; ++i) { xp[i] = Pw[i]; xs[i] = Vw[i]; st[16 + i] = Pw[i]; st[23 + i] = Vw[i]; }
+        for (int i = 0; i < 4; ++i) { xp[3 + i] = q[i]; st[19 + i] = q[i]; }
+        for (int i = 0; i < 6; ++i) { st[26 + i] = bias[i]; st[9 + i] = first[i]; }
+        for (int i = 0; i < 3; ++i) { st[i] = r.acc0[i]; st[3 + i] = r.gyr0[i]; }
+    }
+}
+
+// The IMU part of slideWindow() after a dropped non-keyframe (estimator.cpp:1069-1081): pre_integrations[WINDOW_SIZE - 1] -- record
+// K-3 after the slide -- takes this frame's samples.  No sample history: the stored record IS the state push_back continues from
+// (sum_dt, delta_p / q / v, jacobian, covariance, its own linearisation biases), the samples are still in the frame staging, and the
+// measurement that ended the record is the one ba_seq_imu_kernel kept.  Windows that marginalized the oldest frame leave at once.
+extern "C" __global__ __launch_bounds__(64) void ba_seq_merge_kernel(const BaLayout* __restrict__ Lp, BaPtrs P, SeqDev S) {
+    __shared__ ImuPreLds s;
+    const BaLayout& L = *Lp;
+    const int w = blockIdx.x, lane = threadIdx.x, K = S.K;
+    if (S.info[(size_t)w * VG_SEQ_INFO_INTS + VG_SEQ_FLAG] != VG_MARGIN_SECOND_NEW) return;
+    int* ia = P.iarr + (size_t)w * L.istride;
+    double* rec = P.din + (size_t)w * L.dstride + L.do_imu + (size_t)(K - 3) * BA_IMU_STRIDE;
+    const double* smp = S.in_d + (size_t)w * S.id_stride;
+    const double* st = S.imu_st + (size_t)w * SEQ_IMU_ST;
+    int ns = S.in_i[(size_t)w * S.ii_stride + 4];
+    if (ns > S.MS) ns = S.MS;
+    ImuRun r;
+    imu_enter(s, r, rec, st + 9, nullptr, S.noise[0], S.noise[1], S.noise[2], S.noise[3], lane);
+    for (int k = 0; k < ns; ++k) imu_push_back(s, r, smp + (size_t)k * 7, lane);
+    imu_leave(s, r, rec, lane);
+    if (lane == 1) ia[L.io_imu_valid + (K - 3)] = (ia[L.io_imu_valid + (K - 3)] && r.sum_dt <= 10.0) ? 1 : 0;
+}
+
+// what slideWindow() leaves in the newest slot: a copy of the frame before it (vg_ba_seq_imu_begin / vg_ba_seq_import in IMU mode)
+extern "C" __global__ __launch_bounds__(64) void ba_seq_imu_seed_kernel(const BaLayout* __restrict__ Lp, BaPtrs P, SeqDev S, int w0) {
+    const BaLayout& L = *Lp;
+    const int w = w0 + blockIdx.x, t = threadIdx.x, K = S.K;
+    double* di = P.din + (size_t)w * L.dstride;
+    if (t < 7) di[L.do_pose + 7 * (K - 1) + t] = di[L.do_pose + 7 * (K - 2) + t];
+    else if (t < 16) di[L.do_sb + 9 * (K - 1) + (t - 7)] = di[L.do_sb + 9 * (K - 2) + (t - 7)];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" hipError_t ba_seq_launch_imu(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, hipStream_t stream) {
+    hipLaunchKernelGGL(ba_seq_imu_kernel, dim3(L.nwin), dim3(64), 0, stream, dL, P, S);
+    return hipGetLastError();
+}
+extern "C" hipError_t ba_seq_launch_merge(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, hipStream_t stream) {
+    hipLaunchKernelGGL(ba_seq_merge_kernel, dim3(L.nwin), dim3(64), 0, stream, dL, P, S);
+    return hipGetLastError();
+}
+extern "C" hipError_t ba_seq_launch_imu_seed(const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int w0, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(ba_seq_imu_seed_kernel, dim3(n), dim3(64), 0, stream, dL, P, S, w0);
+    return hipGetLastError();
+}
 extern "C" hipError_t ba_seq_launch_front(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int cur, hipStream_t stream) {
     hipLaunchKernelGGL(ba_seq_add_kernel, dim3(L.nwin), dim3(SEQ_NT), 0, stream, dL, P, S, cur);
     hipError_t e = hipGetLastError();

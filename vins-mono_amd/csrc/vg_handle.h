@@ -38,13 +38,23 @@ struct SeqDev {
     int* in_i;
     double* in_d;
     int* info;                       // [nwin][VG_SEQ_INFO_INTS]
+    // ---- raw IMU samples in, processIMU on the device (vg_ba_seq_imu_begin); all zero in a host-fed sequence
+    int rows_off;                    // observation rows of the frame staging start here (host-fed: behind the two records; IMU mode: behind the samples)
+    int imu_mode, MS;                // IMU mode: frame staging doubles are [samples MS x 7 | rows NIN x 8], staging ints [4] = n_samples
+    double noise[4];                 // ACC_N GYR_N ACC_W GYR_W
+    double* imu_st;                  // [nwin][SEQ_IMU_ST]: acc_0 gyr_0 g (9) | the measurement in front of the last frame's samples (6) | - |
+                                     //                     state guess the last step propagated: pose (7) at 16, speedbias (9) at 23
 };
+#define SEQ_IMU_ST 32
 struct BaSeq {
     bool active = false;
     int nwin = 0, cur = 0;
     SeqDev D = {};
     PinnedBuf<int> h_in_i, h_info;
     PinnedBuf<double> h_in_d;
+    bool imu_timing = false;         // vg_ba_seq_imu_timing: HIP events around ba_seq_imu_kernel and ba_seq_merge_kernel
+    bool imu_timed = false;          // the last step recorded them
+    hipEvent_t ev_imu[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 struct BaBatch {

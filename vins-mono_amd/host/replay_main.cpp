@@ -28,7 +28,9 @@
 //     map of processImage): `seq` for one estimator whose tracks are NOT in the file (window.bin holds states and IMU samples only,
 //     L = 0 and n = 0) but come from FeatureTracker::readImage over frames.bin -- the first WINDOW_SIZE frames fill the window that
 //     is handed over, every further frame is one processImage + solve.  tests/e2e_vio.py renders the frames.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -319,6 +321,12 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
     // takes them over (handOver + begin) and estimator 0 is re-seeded once more in place (reseed): the rest of the run must not notice
     const char* hb_env = getenv("VINS_REPLAY_HANDBACK");
     const int handback_frame = hb_env ? atoi(hb_env) : -1;
+    // VINS_REPLAY_DEVICE_IMU=1: processIMU on the device too (ResidentEstimators::useDeviceImu)
+    const char* di_env = getenv("VINS_REPLAY_DEVICE_IMU");
+    const bool device_imu = di_env && atoi(di_env) != 0;
+    if (device_imu) resp->useDeviceImu();
+    // VINS_REPLAY_TIMING=1: per frame "T,<frame>,<ms in processIMU>,<ms in solve()>" on stderr (tests/manual/gpu_seq_imu.py)
+    const bool timing = getenv("VINS_REPLAY_TIMING") != nullptr;
     for (int i = 0; i < N; ++i) {
         // the estimator as the reference's code would hold it between two frames, then handed over
         Estimator est;
@@ -377,16 +385,23 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
         for (int k = 0; k <= WINDOW_SIZE; ++k) { delete est.pre_integrations[k]; est.pre_integrations[k] = nullptr; }
     }
     resp->begin();
+    // VINS_REPLAY_KERNEL_TIMES=1 (with the IMU on the device): per frame "K,<frame>,<ms in ba_seq_imu_kernel>,<ms in ba_seq_merge_kernel>"
+    // on stderr, from HIP events; asking for them waits for the merge, so such a run is not one to take host times from
+    const bool kernel_times = device_imu && getenv("VINS_REPLAY_KERNEL_TIMES") != nullptr;
+    if (kernel_times) resp->deviceImuTiming(true);
     FILE* o = fopen(out, "w");
     std::vector<double> smp((size_t)S * 7);
     double fe_ms = 0;
     for (int w = 0; w < W; ++w) {
         std::vector<double> stamp(N);
+        double imu_ms = 0;
         for (int i = 0; i < N; ++i) {
             rd.d(&stamp[i], 1);
             rd.d(smp.data(), S * 7);
+            const auto t_imu = std::chrono::steady_clock::now();
             for (int s = 0; s < S; ++s)
                 resp->processIMU(i, smp[7 * s], Vector3d(smp[7 * s + 1], smp[7 * s + 2], smp[7 * s + 3]), Vector3d(smp[7 * s + 4], smp[7 * s + 5], smp[7 * s + 6]));
+            imu_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_imu).count();
             int n;
             rd.i(&n, 1);
             ResidentEstimators::Image image;
@@ -408,6 +423,12 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
         const auto t_solve = std::chrono::steady_clock::now();
         resp->solve();
         const double solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_solve).count();
+        if (timing) fprintf(stderr, "T,%d,%.4f,%.4f\n", w, imu_ms, solve_ms);
+        if (kernel_times) {
+            float ik = 0, mk = 0;
+            resp->deviceImuTimes(ik, mk);
+            fprintf(stderr, "K,%d,%.5f,%.5f\n", w, ik, mk);
+        }
         for (int i = 0; i < N; ++i) {
             // (the mirror is post-slide: the frame just solved sits in slot WINDOW_SIZE either way)
             const ResidentEstimators::One& e = (*resp)[i];
@@ -419,6 +440,7 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
         }
         if (w == handback_frame) {
             std::unique_ptr<ResidentEstimators> next(new ResidentEstimators(N, 512, 512));
+            if (device_imu) next->useDeviceImu();
             std::vector<std::unique_ptr<Estimator>> back;
             for (int i = 0; i < N; ++i) {
                 back.emplace_back(new Estimator());
@@ -430,8 +452,21 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
             for (auto& e : back)
                 for (int k = 0; k <= WINDOW_SIZE; ++k) { delete e->pre_integrations[k]; e->pre_integrations[k] = nullptr; }
             resp = std::move(next);
+            if (kernel_times) resp->deviceImuTiming(true);
         }
     }
+    // which side ran processIMU, and (device) how far the resident acc_0 / gyr_0 are from the last sample the host handed on
+    fprintf(stderr, "M,%s\n", resp->deviceImu() ? "device" : "host");
+    if (resp->deviceImu())
+        for (int i = 0; i < N; ++i) {
+            double s[9];
+            resp->residentMeasurement(i, s);
+            const ResidentEstimators::One& e = (*resp)[i];
+            const double m[6] = {e.acc_0.x(), e.acc_0.y(), e.acc_0.z(), e.gyr_0.x(), e.gyr_0.y(), e.gyr_0.z()};
+            double worst = 0;
+            for (int k = 0; k < 6; ++k) worst = std::max(worst, std::fabs(s[k] - m[k]));
+            fprintf(stderr, "A,%d,%.3g\n", i, worst);
+        }
     fclose(o);
     fclose(rd.f);
     vg_destroy(h);

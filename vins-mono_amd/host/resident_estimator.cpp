@@ -48,6 +48,31 @@ void ResidentEstimators::reseed(int i, Estimator& e, const Vector3d& acc_0, cons
     const int rc = vg_ba_seq_import(vg_, i, &w->prob, &w->tracks);
     delete w;
     if (rc != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_import: ") + vg_last_error(vg_));
+    if (device_imu_) {
+        const One& o = est_[i];
+        const double seed[9] = {o.acc_0.x(), o.acc_0.y(), o.acc_0.z(), o.gyr_0.x(), o.gyr_0.y(), o.gyr_0.z(), o.g.x(), o.g.y(), o.g.z()};
+        if (vg_ba_seq_imu_set(vg_, i, seed) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_set: ") + vg_last_error(vg_));
+    }
+}
+
+void ResidentEstimators::useDeviceImu(int max_samples) {
+    if (begun_) throw std::runtime_error("useDeviceImu() after begin()");
+    device_imu_ = true;
+    max_samples_ = max_samples;
+}
+
+void ResidentEstimators::deviceImuTiming(bool on) {
+    if (!begun_ || !device_imu_) throw std::runtime_error("deviceImuTiming(): the IMU state is not on the device");
+    if (vg_ba_seq_imu_timing(vg_, on ? 1 : 0) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_timing: ") + vg_last_error(vg_));
+}
+
+void ResidentEstimators::deviceImuTimes(float& imu_kernel_ms, float& merge_kernel_ms) {
+    if (vg_ba_seq_imu_times(vg_, &imu_kernel_ms, &merge_kernel_ms) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_times: ") + vg_last_error(vg_));
+}
+
+void ResidentEstimators::residentMeasurement(int i, double seed9[9]) {
+    if (!begun_ || !device_imu_) throw std::runtime_error("residentMeasurement(): the IMU state is not on the device");
+    if (vg_ba_seq_imu_get(vg_, i, seed9, nullptr, nullptr) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_get: ") + vg_last_error(vg_));
 }
 
 ResidentEstimators::Window* ResidentEstimators::pack(int i, Estimator& e, const Vector3d& acc_0, const Vector3d& gyr_0) {
@@ -146,7 +171,7 @@ void ResidentEstimators::handBack(int i, Estimator& e) {
         e.td = td;
     }
     for (int j = 0; j <= WINDOW_SIZE; ++j) { delete e.pre_integrations[j]; e.pre_integrations[j] = nullptr; }
-    if (o.merge_pending) {
+    if (o.merge_pending && !device_imu_) {                          // (with the IMU on the device the exported record IS the merged one)
         // the last frame was dropped as a non-keyframe: pre_integrations[WINDOW_SIZE - 1] has taken its samples (estimator.cpp:1069-1085)
         // but the device still holds the record of the shorter interval (the merged one travels with the NEXT frame): integrate it now
         const int ns = (int)o.prev.samples.size() / 7;
@@ -242,6 +267,18 @@ void ResidentEstimators::begin() {
     cfg.max_features = max_features_; cfg.max_new_obs = max_new_obs_; cfg.init_depth = INIT_DEPTH; cfg.min_parallax = MIN_PARALLAX;
     if (vg_ba_seq_begin(vg_, size(), &cfg, pb.data(), tr.data()) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_begin: ") + vg_last_error(vg_));
     for (Window*& w : win_) { delete w; w = nullptr; }
+    if (device_imu_) {
+        vg_ba_seq_imu_config ic;
+        memset(&ic, 0, sizeof(ic));
+        ic.struct_size = (int)sizeof(ic); ic.max_samples = max_samples_;
+        ic.noise[0] = ACC_N; ic.noise[1] = GYR_N; ic.noise[2] = ACC_W; ic.noise[3] = GYR_W;
+        std::vector<double> seed;
+        for (const One& o : est_) {
+            const double s[9] = {o.acc_0.x(), o.acc_0.y(), o.acc_0.z(), o.gyr_0.x(), o.gyr_0.y(), o.gyr_0.z(), o.g.x(), o.g.y(), o.g.z()};
+            seed.insert(seed.end(), s, s + 9);
+        }
+        if (vg_ba_seq_imu_begin(vg_, size(), &ic, seed.data()) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_begin: ") + vg_last_error(vg_));
+    }
     begun_ = true;
 }
 
@@ -253,6 +290,7 @@ void ResidentEstimators::processIMU(int i, double dt, const Vector3d& acc, const
     if (!o.first_imu) { o.first_imu = true; o.acc_0 = acc; o.gyr_0 = gyr; }
     const double r[7] = {dt, acc.x(), acc.y(), acc.z(), gyr.x(), gyr.y(), gyr.z()};
     o.cur.samples.insert(o.cur.samples.end(), r, r + 7);            // pre_integrations[frame_count]->push_back (:95): integrated in solve()
+    if (device_imu_) { o.acc_0 = acc; o.gyr_0 = gyr; return; }       // the propagation runs on the device too (vg_ba_seq_step_imu_async)
     const int j = WINDOW_SIZE;
     const Vector3d un_acc_0 = o.Rs[j] * (o.acc_0 - o.Bas[j]) - o.g;
     const Vector3d un_gyr = (o.gyr_0 + gyr) * 0.5 - o.Bgs[j];
@@ -277,7 +315,29 @@ void ResidentEstimators::processImage(int i, const Image& image) {
 
 void ResidentEstimators::solve() {
     if (!begun_) throw std::runtime_error("solve() before begin()");
-    const int n = size(), K = WINDOW_SIZE + 1;
+    const int n = size();
+    if (device_imu_) {
+        // ---- raw samples and observations, nothing else: processIMU and the merge of slideWindow() run on the device
+        std::vector<vg_ba_frame_imu> fr(n);
+        std::vector<const vg_ba_frame_imu*> frp(n);
+        for (int i = 0; i < n; ++i) {
+            One& o = est_[i];
+            if (!o.have_frame) throw std::runtime_error("solve(): estimator " + std::to_string(i) + " has no frame");
+            memset(&fr[i], 0, sizeof(vg_ba_frame_imu));
+            fr[i].n_samples = (int)o.cur.samples.size() / 7; fr[i].samples = o.cur.samples.data();
+            fr[i].n_obs = (int)o.ids.size(); fr[i].feature_id = o.ids.data(); fr[i].obs = o.rows.data();
+            frp[i] = &fr[i];
+        }
+        if (vg_ba_seq_step_imu_async(vg_, n, frp.data()) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_step_imu_async: ") + vg_last_error(vg_));
+    } else {
+        stepFromHost();
+    }
+    finishStep();
+}
+
+// processIMU's results from the host: the running intervals (and the merged ones) integrated in one batched call, the propagated guess
+void ResidentEstimators::stepFromHost() {
+    const int n = size();
     // ---- the running intervals (and the merged ones) integrated in one batched call
     std::vector<int> off(1, 0), which;                              // interval q belongs to estimator which[q] / 2, odd = merged
     std::vector<double> smp, first, bias;
@@ -319,7 +379,11 @@ void ResidentEstimators::solve() {
         f.n_obs = (int)o.ids.size(); f.feature_id = o.ids.data(); f.obs = o.rows.data();
     }
     if (vg_ba_seq_step_async(vg_, n, frp.data()) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_step_async: ") + vg_last_error(vg_));
-    // ---- states of the solved windows, the key-frame decisions
+}
+
+// states of the solved windows, the key-frame decisions; the host mirror and the sample buffers follow the slide
+void ResidentEstimators::finishStep() {
+    const int n = size(), K = WINDOW_SIZE + 1;
     std::vector<double> pose((size_t)n * 7 * K), sb((size_t)n * 9 * K), ex((size_t)n * 7), td(n);
     std::vector<vg_ba_state> st(n);
     std::vector<vg_ba_state*> stp(n);

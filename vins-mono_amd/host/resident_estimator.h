@@ -3,7 +3,7 @@
 // (vins_estimator/src/estimator.h:32-33) with the estimator's index in front:
 //     processIMU(i, dt, linear_acceleration, angular_velocity)        estimator.cpp:83-117
 //     processImage(i, image)                                          estimator.cpp:120-215 (solver_flag == NON_LINEAR branch)
-// processIMU does what the reference's does on the host: it keeps the raw samples of the running interval (dt_buf / acc_buf /
+// processIMU does what the reference's does on the host (unless useDeviceImu() moved that to the device as well): it keeps the raw samples of the running interval (dt_buf / acc_buf /
 // gyr_buf of IntegrationBase) and propagates Ps / Rs / Vs of the newest frame.  processImage only stores the frame;
 // solve() then runs ONE device step for all estimators (addFeatureCheckParallax, triangulate, optimization(), slideWindow(),
 // removeFailures(): vg_ba_seq_step_async) and brings the states back.  f_manager, para_*, pre_integrations[] and
@@ -56,6 +56,18 @@ class ResidentEstimators {
     // Hand-over of estimator i between two frames (after slideWindow()): its states, pre_integrations[1 .. WINDOW_SIZE - 1] (the
     // last one with its raw samples), f_manager.feature and last_marginalization_info; acc_0 / gyr_0 = the newest IMU sample.
     void handOver(int i, Estimator& e, const Vector3d& acc_0, const Vector3d& gyr_0);
+    // Opt-in, before begin(): Estimator::processIMU and the IMU part of slideWindow() run on the device (vg_ba_seq_imu_begin /
+    // vg_ba_seq_step_imu_async).  processIMU then only buffers the samples (no propagation, no integration), solve() sends them with
+    // the observations, and Ps / Rs / Vs[WINDOW_SIZE] of the mirror are filled from the downloaded states as before.  The raw samples
+    // stay buffered on the host for handBack.
+    // max_samples: the most IMU samples one frame may bring (1 .. 512; a capacity, the step uploads what a frame holds).
+    void useDeviceImu(int max_samples = 512);
+    bool deviceImu() const { return device_imu_; }
+    // parity tap in that mode: acc_0 (3), gyr_0 (3), g (3) as the DEVICE holds them for estimator i (vg_ba_seq_imu_get)
+    void residentMeasurement(int i, double seed9[9]);
+    // measurement taps in that mode (vg_ba_seq_imu_timing / _times): device time of the IMU kernel and of the merge of the last solve(), ms
+    void deviceImuTiming(bool on);
+    void deviceImuTimes(float& imu_kernel_ms, float& merge_kernel_ms);
     void begin();                             // vg_ba_seq_begin once every estimator has been handed over
     // The way back, between two frames: window i of the running sequence into the members of a host Estimator (Ps / Rs / Vs / Bas /
     // Bgs, ric / tic / td, pre_integrations[1 .. WINDOW_SIZE - 1] -- the last one with its raw samples --, f_manager.feature,
@@ -77,4 +89,8 @@ class ResidentEstimators {
     vg_handle* vg_ = nullptr;
     int max_features_, max_new_obs_;
     bool begun_ = false;
+    bool device_imu_ = false;
+    int max_samples_ = 512;
+    void stepFromHost();                      // solve(): the host-fed step (pre-integration + propagated guess from here)
+    void finishStep();                        // solve(): download, mirror, sample buffers
 };
