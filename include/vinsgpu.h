@@ -30,7 +30,8 @@ extern "C" {
                              * 10: vg_config / vg_create_config; vg_ba_batch_is_fused no longer returns 2; 11: vg_fe_read_image;
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
-                             * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async) */
+                             * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
+                             * vg_vio_begin / _step_async / _get_frame / _end) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -815,6 +816,54 @@ int vg_fe_tracks_begin(vg_handle* h);
 int vg_fe_tracks_step(vg_handle* h, int n_streams, const vg_fe_tracks_in* in /* [n_streams] */, vg_fe_tracks_out* out /* [n_streams] */);
 int vg_fe_tracks_get(vg_handle* h, int cam, vg_fe_tracks_state* state);
 int vg_fe_tracks_set(vg_handle* h, int cam, const vg_fe_tracks_state* state);
+
+/* ---- Front end feeds resident sequences on the device: one call per frame (added within ABI 12, nothing existing changed) -----------
+ * vg_fe_tracks_step builds the estimator's message (msg_id / msg_obs) in HBM and vg_ba_seq_step_imu_async reads a frame's observations
+ * from HBM; between the two calls the message travels to the pinned mirror, through the caller and up again.  These calls join the two on
+ * ONE handle that runs n_cams camera + IMU streams, stream c feeding window c: images and IMU samples go up, states come down, the tracks
+ * and the observations stay on the device.
+ *
+ * vg_vio_begin       needs, else VG_ERR_BAD_ARG with a vg_last_error text: resident lists begun (vg_fe_tracks_begin); a running sequence
+ *                    in IMU mode (vg_ba_seq_begin + vg_ba_seq_imu_begin) on the same handle; n_cams == nwin; max_points <=
+ *                    vg_ba_seq_config::max_new_obs; flags of VG_VIO_*.  The lists may hold tracks and the windows a seeded state -- the
+ *                    normal case: initialisation stays on the host, the caller runs the first K-1 frames through vg_fe_tracks_step,
+ *                    seeds the sequence from the collected messages and switches to vg_vio_step_async (the ids stay consistent
+ *                    because the list is resident).
+ * vg_vio_step_async  one frame for every stream.  The frame of vg_fe_tracks_step (same kernels, same host finish of RANSAC and
+ *                    detection); fe.publish must be uniform over the streams of one call.  On a frame that publishes, one kernel
+ *                    (ba_seq_bridge_kernel) moves every stream's message from the commit kernel's output into the staging
+ *                    ba_seq_add_kernel reads, and the step of vg_ba_seq_step_imu_async follows; only the samples and their counts are
+ *                    uploaded.  On a frame that does not publish only the front end runs and n_samples must be 0: the caller keeps
+ *                    accumulating samples until the next published frame.
+ *                    out[c].fe: the counts of vg_fe_tracks_out; its array pointers are NULL unless the bridge was begun with
+ *                    VG_VIO_LISTS -- without it the download after the commit kernel carries the header block only, neither the lists
+ *                    nor the message.
+ *   refused with VG_ERR_BAD_ARG before anything is uploaded or launched (no stream and no window moves): no bridge; struct_size; n
+ *                    other than n_cams; mixed publish; n_samples outside 1 .. max_samples on a frame that publishes or not 0 on one
+ *                    that does not; samples NULL; a sample that is not finite; everything vg_fe_tracks_step refuses.
+ *   failure after the front end's upload (a callback's, a detection overflow): the estimator part is NOT launched, the windows stay;
+ *                    the lists behave as vg_fe_tracks_step documents.
+ *   States come back as before: vg_ba_batch_download_state, vg_ba_seq_info.
+ * vg_vio_get_frame   parity tap: what the last publishing step staged for one window -- n_obs, ids, rows of 7 doubles -- read from the
+ *                    sequence's staging buffers on the device; arrays of capacity cap (either may be NULL).
+ * vg_vio_end         ends the bridge; lists and sequence go on.
+ * Mixing: vg_fe_tracks_step and vg_ba_seq_step_imu_async stay legal between two vg_vio_step_async calls (the same state).
+ * vg_ba_seq_end, vg_ba_seq_begin, vg_ba_seq_imu_begin (it replaces the staging and may change max_samples), vg_fe_configure and
+ * vg_fe_tracks_begin end the bridge: a later vg_vio_step_async is refused until vg_vio_begin is called again. */
+typedef struct vg_vio_in {
+    int struct_size;             /* sizeof(vg_vio_in)                                                                          */
+    int n_samples;               /* IMU rows since the previous PUBLISHED frame, as estimator_node's getMeasurements pairs them */
+    const double* samples;       /* n_samples x 7: dt acc gyr                                                                  */
+    vg_fe_tracks_in fe;          /* exactly what vg_fe_tracks_step takes for this stream                                       */
+} vg_vio_in;
+typedef struct vg_vio_out {
+    vg_fe_tracks_out fe;         /* counts; the array pointers are NULL unless VG_VIO_LISTS                                    */
+} vg_vio_out;
+enum { VG_VIO_LISTS = 1 };
+int vg_vio_begin(vg_handle* h, int flags);
+int vg_vio_step_async(vg_handle* h, int n, const vg_vio_in* in /* [n] */, vg_vio_out* out /* [n] */);
+int vg_vio_get_frame(vg_handle* h, int window, int cap, int* n_obs, int* feature_id, double* obs7);
+int vg_vio_end(vg_handle* h);
 
 #ifdef __cplusplus
 }

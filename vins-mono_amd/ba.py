@@ -285,6 +285,10 @@ class Handle:
             L.vg_ba_seq_imu_set.argtypes = [C.c_void_p, C.c_int, _pd]
             L.vg_ba_seq_imu_timing.argtypes = [C.c_void_p, C.c_int]
             L.vg_ba_seq_imu_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        if hasattr(L, "vg_vio_begin"):                    # (added within ABI 12)
+            L.vg_vio_begin.argtypes = [C.c_void_p, C.c_int]
+            L.vg_vio_get_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, _pi, _pi, _pd]
+            L.vg_vio_end.argtypes = [C.c_void_p]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -689,6 +693,28 @@ class Handle:
 
     def seq_end(self):
         self._chk(self.lib.vg_ba_seq_end(self.h), "vg_ba_seq_end")
+
+    # ---- the front end feeds the sequence on the device, one call per frame (include/vinsgpu.h vg_vio_*)
+    def vio_begin(self, lists=False):
+        """After tracks_begin (fe.FrontEnd on this handle), seq_begin and seq_imu_begin: stream c feeds window c.  lists: VG_VIO_LISTS,
+        every step also returns the lists and the message (otherwise counts only)."""
+        self._chk(self.lib.vg_vio_begin(self.h, 1 if lists else 0), "vg_vio_begin")
+        self._vio_lists = bool(lists)
+
+    def vio_step(self, front_end, samples, **step_args):
+        """vg_vio_step_async: the frame of front_end.tracks_step(**step_args) and, when it publishes, the step of seq_step_imu with
+        samples[c] for window c and the observations taken from stream c's message on the device (fe.FrontEnd.vio_step)."""
+        return front_end.vio_step(samples, lists=getattr(self, "_vio_lists", False), **step_args)
+
+    def vio_frame(self, w, cap=1024):
+        """parity tap: (ids, obs (n, 7)) the last publishing vio_step staged for window w, read from the device"""
+        n = C.c_int()
+        ids, obs = np.zeros(max(cap, 1), np.int32), np.zeros((max(cap, 1), 7))
+        self._chk(self.lib.vg_vio_get_frame(self.h, int(w), int(cap), C.byref(n), _ip(ids), _dp(obs)), "vg_vio_get_frame")
+        return ids[:n.value].copy(), obs[:n.value].copy()
+
+    def vio_end(self):
+        self._chk(self.lib.vg_vio_end(self.h), "vg_vio_end")
 
     def imu_preintegrate(self, intervals, biases, noise):
         """Batched IntegrationBase (integration_base.h:30-158).  intervals[k] = [(dt, acc, gyr), ...] with entry 0 =

@@ -1321,6 +1321,12 @@ extern "C" hipError_t ba_seq_launch_imu(const BaLayout& L, const BaLayout* dL, c
 extern "C" hipError_t ba_seq_launch_merge(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, hipStream_t stream);
 extern "C" hipError_t ba_seq_launch_imu_seed(const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int w0, int n, hipStream_t stream);
 extern "C" int ba_seq_limits(int* ft_max, int* nin_max, int* hdr_ints, int* in_rows_off);
+extern "C" hipError_t ba_seq_launch_bridge(const BaLayout& L, const SeqDev& S, const int* tk_hdr, const int* msg_id, const double* msg_obs, int cap,
+                                           const double* smp, int smp_stride, hipStream_t stream);
+// the front end's side of vg_vio_* (fe_host.hip)
+extern "C" int fe_vio_limits(vg_handle* h, int* n_cams, int* max_points);
+extern "C" int fe_tracks_step_impl(vg_handle* h, const char* who, int n_streams, const vg_fe_tracks_in* in, vg_fe_tracks_out* out, int lists);
+extern "C" void fe_vio_message(vg_handle* h, const int** tk_hdr, const int** msg_id, const double** msg_obs);
 
 static void seq_free(BaSeq& Q) {
     SeqDev& D = Q.D;
@@ -1329,6 +1335,9 @@ static void seq_free(BaSeq& Q) {
     D.sp = nullptr; D.in_i = nullptr; D.in_d = nullptr; D.info = nullptr; D.imu_st = nullptr;
     D.imu_mode = 0; D.MS = 0;
     Q.h_in_i.release(); Q.h_in_d.release(); Q.h_info.release();
+    (void)hipFree(Q.vio_d); Q.vio_d = nullptr;
+    Q.h_vio.release();
+    Q.vio = Q.vio_staged = false; Q.vio_flags = 0;
     for (hipEvent_t& ev : Q.ev_imu) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
     Q.imu_timing = Q.imu_timed = false;
     Q.active = false;
@@ -1452,7 +1461,8 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
     return VG_OK;
 }
 
-static int seq_launch_step(vg_handle* h, const SeqDev& D);
+struct SeqBridge { const int* tk_hdr; const int* msg_id; const double* msg_obs; int cap, smp_stride; };
+static int seq_launch_step(vg_handle* h, const SeqDev& D, const SeqBridge* bridge = nullptr);
 
 extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* const* frames) {
     VG_RANGE("vg_ba_seq_step_async");
@@ -1503,14 +1513,23 @@ extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* c
 }
 
 // the packed frame staging of every window goes up, then the kernels of one frame.  D: the sequence's SeqDev with the staging
-// strides of THIS step (the kernels get it by value)
-static int seq_launch_step(vg_handle* h, const SeqDev& D) {
+// strides of THIS step (the kernels get it by value).  bridge (vg_vio_step_async): only the packed samples go up, and
+// ba_seq_bridge_kernel fills the staging from them and from the front end's message in HBM
+static int seq_launch_step(vg_handle* h, const SeqDev& D, const SeqBridge* bridge) {
     BaBatch& B = h->ba;
     BaSeq& Q = B.seq;
     hipError_t e;
-    HIPCHK(h, hipMemcpyAsync(D.in_i, Q.h_in_i.data(), Q.h_in_i.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(D.in_d, Q.h_in_d.data(), Q.h_in_d.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev_join, h->stream));
+    if (bridge) {
+        HIPCHK(h, hipMemcpyAsync(Q.vio_d, Q.h_vio.data(), Q.h_vio.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev_join, h->stream));
+        e = ba_seq_launch_bridge(B.L, D, bridge->tk_hdr, bridge->msg_id, bridge->msg_obs, bridge->cap, Q.vio_d, bridge->smp_stride, h->stream);
+        if (e != hipSuccess) { h->err = std::string("launch of the sequence bridge kernel: ") + hipGetErrorString(e); return VG_ERR_HIP; }
+    } else {
+        HIPCHK(h, hipMemcpyAsync(D.in_i, Q.h_in_i.data(), Q.h_in_i.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(D.in_d, Q.h_in_d.data(), Q.h_in_d.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev_join, h->stream));
+    }
+    Q.vio_staged = bridge != nullptr;
     const bool timed = D.imu_mode && Q.imu_timing;
     if (D.imu_mode) {
         if (timed) HIPCHK(h, hipEventRecord(Q.ev_imu[0], h->stream));
@@ -1563,6 +1582,8 @@ extern "C" int vg_ba_seq_imu_begin(vg_handle* h, int nwin, const vg_ba_seq_imu_c
     for (int w = 0; w < nwin; ++w) memcpy(hs.data() + (size_t)w * SEQ_IMU_ST, seed + (size_t)w * 9, 9 * sizeof(double));
     (void)hipFree(D.in_d); (void)hipFree(D.imu_st);
     D.in_d = in_d; D.imu_st = st;
+    Q.vio = Q.vio_staged = false;                                // (a bridge begun for the staging just replaced ends here,
+    (void)hipFree(Q.vio_d); Q.vio_d = nullptr;                   //  and its sample block was sized for the old max_samples)
     D.rows_off = rows_off; D.id_stride = id_stride; D.MS = cfg->max_samples; D.imu_mode = 1;
     memcpy(D.noise, cfg->noise, sizeof(D.noise));
     HIPCHK(h, hipMemcpy(D.imu_st, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1616,6 +1637,107 @@ extern "C" int vg_ba_seq_step_imu_async(vg_handle* h, int nwin, const vg_ba_fram
         for (int k = 0; k < f->n_obs; ++k) { memcpy(d + D.rows_off + (size_t)k * 8, f->obs + (size_t)k * 7, 7 * 8); d[D.rows_off + (size_t)k * 8 + 7] = 0.0; }
     });
     return seq_launch_step(h, D);
+}
+
+// ---- the front end feeds the sequence on the device: one call per frame (include/vinsgpu.h vg_vio_*) ---------------------------------
+extern "C" int vg_vio_begin(vg_handle* h, int flags) {
+    VG_RANGE("vg_vio_begin");
+    if (!h) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_vio_begin: ") + why; return VG_ERR_BAD_ARG; };
+    if (flags & ~VG_VIO_LISTS) return refuse("unknown flags");
+    int cams = 0, max_pts = 0;
+    if (fe_vio_limits(h, &cams, &max_pts) != VG_OK) return refuse("no front end with resident lists (vg_fe_configure, vg_fe_tracks_begin)");
+    if (!Q.active || !B.uploaded) return refuse("no running sequence (vg_ba_seq_begin)");
+    if (!Q.D.imu_mode) return refuse("the sequence does not take raw IMU samples (vg_ba_seq_imu_begin)");
+    if (cams != Q.nwin) return refuse("n_cams of vg_fe_configure differs from the windows of the sequence (stream c feeds window c)");
+    if (max_pts > Q.D.NIN) return refuse("max_points of vg_fe_configure exceeds vg_ba_seq_config::max_new_obs");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the sample block holds max_samples rows per window: vg_ba_seq_imu_begin, the only call that changes max_samples, drops it
+    if (!Q.vio_d) HIPCHK(h, hipMalloc((void**)&Q.vio_d, (size_t)Q.nwin * (8 + up(7 * Q.D.MS, 8)) * sizeof(double)));
+    Q.vio = true; Q.vio_flags = flags; Q.vio_staged = false;
+    return VG_OK;
+}
+
+extern "C" int vg_vio_end(vg_handle* h) {
+    if (!h) return VG_ERR_BAD_ARG;
+    h->ba.seq.vio = false;
+    return VG_OK;
+}
+
+extern "C" int vg_vio_step_async(vg_handle* h, int n, const vg_vio_in* in, vg_vio_out* out) {
+    VG_RANGE("vg_vio_step_async");
+    if (!h || !in || !out) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_vio_step_async: ") + why; return VG_ERR_BAD_ARG; };
+    int cams = 0, max_pts = 0;
+    if (!Q.vio || !Q.active || !B.uploaded || !Q.D.imu_mode || fe_vio_limits(h, &cams, &max_pts) != VG_OK || cams != Q.nwin)
+        return refuse("no bridge (vg_vio_begin; vg_ba_seq_end, vg_fe_configure and vg_fe_tracks_begin end it)");
+    if (n != Q.nwin) return refuse("n differs from n_cams of vg_fe_configure (stream c feeds window c)");
+    // ---- everything that follows from the arguments alone: nothing has gone up, no stream and no window has moved
+    const int publish = in[0].fe.publish ? 1 : 0;
+    int ns_max = 0;
+    for (int w = 0; w < n; ++w) {
+        const vg_vio_in& f = in[w];
+        if (f.struct_size != (int)sizeof(vg_vio_in)) return refuse("struct_size of a stream");
+        if ((f.fe.publish ? 1 : 0) != publish) return refuse("publish differs between the streams (the windows advance together)");
+        if (!publish) {
+            if (f.n_samples != 0) return refuse("IMU samples with a frame that does not publish (they go up with the next published frame)");
+            continue;
+        }
+        if (f.n_samples < 1 || !f.samples) return refuse("a published frame needs at least one IMU sample");
+        if (f.n_samples > Q.D.MS) return refuse("more samples than vg_ba_seq_imu_config::max_samples");
+        for (int k = 0; k < 7 * f.n_samples; ++k)
+            if (!std::isfinite(f.samples[k])) return refuse("an IMU sample is not finite");
+        ns_max = std::max(ns_max, f.n_samples);
+    }
+    // ---- the frame of vg_fe_tracks_step (its own refusals come before its upload)
+    std::vector<vg_fe_tracks_in> tin((size_t)n);
+    std::vector<vg_fe_tracks_out> tout((size_t)n);
+    for (int w = 0; w < n; ++w) tin[w] = in[w].fe;
+    const int rc = fe_tracks_step_impl(h, "vg_vio_step_async", n, tin.data(), tout.data(), (Q.vio_flags & VG_VIO_LISTS) ? 1 : 0);
+    if (rc) return rc;                                           // (the estimator part is not launched: the windows stay)
+    for (int w = 0; w < n; ++w) out[w].fe = tout[w];
+    if (!publish) return VG_OK;
+    // ---- the samples, packed at the largest count of the step, and the step of vg_ba_seq_step_imu_async
+    const int sstride = 8 + up(7 * ns_max, 8);
+    HIPCHK(h, hipEventSynchronize(h->ev_join));                  // the staging buffers are re-used (as in vg_ba_seq_step_async)
+    HIPCHK(h, Q.h_vio.resize((size_t)n * sstride));
+    for (int w = 0; w < n; ++w) {
+        double* d = Q.h_vio.data() + (size_t)w * sstride;
+        memset(d, 0, sizeof(double) * sstride);
+        memcpy(d, &in[w].n_samples, sizeof(int));
+        memcpy(d + 8, in[w].samples, sizeof(double) * 7 * in[w].n_samples);
+    }
+    SeqBridge br;
+    fe_vio_message(h, &br.tk_hdr, &br.msg_id, &br.msg_obs);
+    br.cap = max_pts; br.smp_stride = sstride;
+    return seq_launch_step(h, Q.D, &br);
+}
+
+extern "C" int vg_vio_get_frame(vg_handle* h, int window, int cap, int* n_obs, int* feature_id, double* obs7) {
+    if (!h || !n_obs || cap < 0) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    if (!Q.active || !Q.vio_staged || window < 0 || window >= Q.nwin) { h->err = "vg_vio_get_frame: no such window of a sequence whose last step was a publishing vg_vio_step_async"; return VG_ERR_BAD_ARG; }
+    const SeqDev& D = Q.D;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int hdr[8];
+    HIPCHK(h, hipMemcpy(hdr, D.in_i + (size_t)window * D.ii_stride, sizeof(hdr), hipMemcpyDeviceToHost));
+    const int n = hdr[0];
+    *n_obs = n;
+    if (n < 0 || n > D.NIN) { h->err = "vg_vio_get_frame: inconsistent count from the device"; return VG_ERR_NUMERIC; }
+    if (n > cap) { h->err = "vg_vio_get_frame: capacity too small"; return VG_ERR_BAD_ARG; }
+    if (n && feature_id) HIPCHK(h, hipMemcpy(feature_id, D.in_i + (size_t)window * D.ii_stride + 8, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (n && obs7) {
+        std::vector<double> rows((size_t)n * 8);
+        HIPCHK(h, hipMemcpy(rows.data(), D.in_d + (size_t)window * D.id_stride + D.rows_off, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
+        for (int k = 0; k < n; ++k) memcpy(obs7 + (size_t)k * 7, rows.data() + (size_t)k * 8, sizeof(double) * 7);
+    }
+    return VG_OK;
 }
 
 extern "C" int vg_ba_seq_imu_get(vg_handle* h, int window, double* seed9, double* guess_pose7, double* guess_sb9) {

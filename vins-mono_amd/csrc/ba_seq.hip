@@ -23,6 +23,9 @@
 // A sequence that takes raw IMU samples (vg_ba_seq_imu_begin) runs ba_seq_imu_kernel in front of all this and ba_seq_merge_kernel
 // behind it: Estimator::processIMU (estimator.cpp:84-118) and the IMU part of slideWindow() (:1069-1095) on the device.
 //
+// A sequence fed by the front end on the same handle (vg_vio_step_async) runs ba_seq_bridge_kernel in front of all that: the message
+// fe_tk_commit_kernel left in HBM becomes the frame staging ba_seq_add_kernel reads, without a trip through the host.
+//
 // One workgroup per window.  The track table is a plain ordered list (ints: id, start_frame, n_obs, solve_flag, landmark index in
 // the current problem; doubles: estimated_depth and K rows of 8 per track); the slide writes the surviving tracks, compacted in
 // order, into the window's second table, so no kernel moves rows in place.  Order matters: it is the order of para_Feature.
@@ -32,6 +35,7 @@
 #include "ba_layout.h"
 #include "imu_step.h"
 #include "vg_handle.h"
+#include "fe_layout.h"
 #include "../../include/vinsgpu.h"
 
 #define SEQ_NT 256
@@ -593,6 +597,68 @@ extern "C" __global__ __launch_bounds__(64) void ba_seq_imu_seed_kernel(const Ba
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// vg_vio_step_async: the message the front end's commit kernel (fe_tk_commit_kernel, fe_frame.hip) left in HBM for stream w goes to
+// where ba_seq_add_kernel reads the frame of window w, in front of ba_seq_imu_kernel.  One workgroup per stream / window.
+//   ints     ii[0] = n_msg, ii[4] = n_samples, the rest of the header 0; ids behind it (16-byte copies when max_points is a multiple of 4:
+//            the streams' id lists are max_points ints apart)
+//   doubles  the samples from the step's packed upload to the front of the staging; the rows [x y z u v vx vy] -> [x y z u v vx vy 0]
+//            at rows_off: 64 rows at a time through LDS -- 224 16-byte loads of the packed 7-double rows (two scalar loads where the
+//            stream's rows start at an odd double) and 256 16-byte stores, one quarter row per thread
+// The staging is at the CAPACITY strides of vg_ba_seq_imu_begin: the host does not know n_msg before the launch.  n_msg is written as
+// it is and the copy clamped at NIN: ba_seq_add_kernel reports the over-capacity frame, as on the host-fed path.
+extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_bridge_kernel(SeqDev S, const int* __restrict__ tk_hdr, const int* __restrict__ msg_id,
+                                                                         const double* __restrict__ msg_obs, int cap,
+                                                                         const double* __restrict__ smp, int smp_stride) {
+    __shared__ double s_row[64 * 7];
+    const int w = blockIdx.x, tid = threadIdx.x;
+    int* ii = S.in_i + (size_t)w * S.ii_stride;
+    double* idd = S.in_d + (size_t)w * S.id_stride;
+    const double* sw = smp + (size_t)w * smp_stride;
+    const int n_msg = tk_hdr[(size_t)w * TK_HDR_INTS + TK_NMSG];
+    const int ns_in = *(const int*)sw;
+    const int ns = ns_in < 0 ? 0 : (ns_in > S.MS ? S.MS : ns_in);         // (the host refuses such a frame)
+    const int nin = n_msg < 0 ? 0 : (n_msg > S.NIN ? S.NIN : n_msg);
+    if (tid < 8) ii[tid] = tid == 0 ? n_msg : (tid == 4 ? ns_in : 0);
+    // ---- samples: 7 ns doubles, pairs (an odd count takes the zero the host padded with; rows_off >= up8(7 MS))
+    for (int k = tid; k < (7 * ns + 1) >> 1; k += SEQ_NT) ((double2*)idd)[k] = ((const double2*)(sw + 8))[k];
+    // ---- ids
+    const int* mid = msg_id + (size_t)w * cap;
+    const int nq = (cap & 3) == 0 ? nin >> 2 : 0;
+    for (int k = tid; k < nq; k += SEQ_NT) ((int4*)(ii + 8))[k] = ((const int4*)mid)[k];
+    for (int i = 4 * nq + tid; i < nin; i += SEQ_NT) ii[8 + i] = mid[i];
+    // ---- rows
+    const double* src = msg_obs + (size_t)w * cap * 7;
+    double* rows = idd + S.rows_off;
+    const bool al = (((size_t)w * cap * 7) & 1) == 0;                     // (msg_obs itself is 256-byte aligned; 64 rows are 448 doubles)
+    for (int r0 = 0; r0 < nin; r0 += 64) {
+        const int rem = (nin - r0 < 64 ? nin - r0 : 64) * 7;
+        const double* p = src + (size_t)r0 * 7;
+        const int e = 2 * tid;
+        if (e + 1 < rem && al) {
+            const double2 v = *(const double2*)(p + e);
+            s_row[e] = v.x; s_row[e + 1] = v.y;
+        } else {
+            if (e < rem) s_row[e] = p[e];
+            if (e + 1 < rem) s_row[e + 1] = p[e + 1];
+        }
+        __syncthreads();
+        const int r = tid >> 2, q = tid & 3;
+        if (r0 + r < nin) {
+            double2 v;
+            v.x = s_row[7 * r + 2 * q];
+            v.y = q < 3 ? s_row[7 * r + 2 * q + 1] : 0.0;
+            *(double2*)(rows + (size_t)(r0 + r) * 8 + 2 * q) = v;
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" hipError_t ba_seq_launch_bridge(const BaLayout& L, const SeqDev& S, const int* tk_hdr, const int* msg_id, const double* msg_obs, int cap,
+                                           const double* smp, int smp_stride, hipStream_t stream) {
+    hipLaunchKernelGGL(ba_seq_bridge_kernel, dim3(L.nwin), dim3(SEQ_NT), 0, stream, S, tk_hdr, msg_id, msg_obs, cap, smp, smp_stride);
+    return hipGetLastError();
+}
 extern "C" hipError_t ba_seq_launch_imu(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, hipStream_t stream) {
     hipLaunchKernelGGL(ba_seq_imu_kernel, dim3(L.nwin), dim3(64), 0, stream, dL, P, S);
     return hipGetLastError();

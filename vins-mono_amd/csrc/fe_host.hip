@@ -155,6 +155,7 @@ extern "C" int vg_fe_configure(vg_handle* h, int width, int height, int n_cams, 
     if (!h || width < 32 || height < 32 || n_cams < 1 || max_points < 1) return VG_ERR_BAD_ARG;
     if ((width * height) % 4) { h->err = "width*height must be a multiple of 4"; return VG_ERR_UNSUPPORTED; }
     HIPCHK(h, hipSetDevice(h->device));
+    h->ba.seq.vio = false;                // (vg_vio_*: the bridge ends with the lists it reads)
     if (h->fe) { fe_state_destroy(h->fe); h->fe = nullptr; }
     FeState* s = new FeState();
     h->fe = s;
@@ -740,9 +741,10 @@ static int rb_ensure(vg_handle* h, FeState* s) {
 // `tin` != NULL: the frame of vg_fe_tracks_step -- in[c].n is the length of stream c's resident list and the points are NOT uploaded
 // (the tracking reads them where the last commit left them), the walk-order callbacks are tin[c].order, and the frame ends with
 // fe_tk_commit_kernel and one download of the new lists instead of block B (tk_collect, below, turns it into `tout`).
-static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_frame_out* fo, vg_fe_tracks_out* tout);
+// `lists` == false (vg_vio_step_async without VG_VIO_LISTS): only the header block of the new lists comes down, `tout` carries counts.
+static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_frame_out* fo, vg_fe_tracks_out* tout, bool lists);
 static int fe_read_image_streams(vg_handle* h, const char* who, const int S, const vg_fe_frame_in* in, vg_fe_frame_out* out,
-                                 const vg_fe_tracks_in* tin = nullptr, vg_fe_tracks_out* tout = nullptr) {
+                                 const vg_fe_tracks_in* tin = nullptr, vg_fe_tracks_out* tout = nullptr, bool lists = true) {
     FeState* s = h->fe;
     TkState* const tk = tin ? s->tk : nullptr;
     auto refuse = [&](int code, const char* why) { h->err = std::string(who) + ": " + why; return code; };
@@ -788,6 +790,7 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
     RbDev bd = b;
     bd.base = q->d_base;
     TkDev td;
+    const size_t tk_down = tk ? (lists ? tk->bytes : sizeof(int) * TK_HDR_INTS * (size_t)S) : 0;
     if (tk) {
         td.from = tk_buf(tk, tk->dev[tk->cur]); td.to = tk_buf(tk, tk->dev[tk->cur ^ 1]);
         bd.xy_in = td.from.cur_xy;
@@ -861,7 +864,7 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
         if (n_pub == 0) {
             hipLaunchKernelGGL(fe_tk_commit_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, td);
             HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipMemcpyAsync(tk->host, tk->dev[tk->cur ^ 1], tk->bytes, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(tk->host, tk->dev[tk->cur ^ 1], tk_down, hipMemcpyDeviceToHost, h->stream));
         }
         if (any_cb) HIPCHK(h, hipMemcpyAsync(tk->h_cnt, td.from.cnt, sizeof(int) * cap * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(hA, q->d_a, q->a_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -884,7 +887,7 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
         }
         if (o.n1 < 0 || o.n1 > in[c].n || o.n2 < 0 || o.n2 > o.n1) return refuse(VG_ERR_NUMERIC, "inconsistent counts from the device");
     }
-    if (n_pub == 0) return tk ? tk_collect(h, who, S, out, tout) : VG_OK;
+    if (n_pub == 0) return tk ? tk_collect(h, who, S, out, tout, lists) : VG_OK;
     // ---- the streams whose estimate the device could not finish (LMedS range, a sample OpenCV would have redrawn): the lifted point
     // sets come back, vg_fe_reject_with_f runs the exact schedule, and the survivor list goes up again
     for (int c = 0; c < S; ++c) {
@@ -969,9 +972,9 @@ static int fe_read_image_streams(vg_handle* h, const char* who, const int S, con
     if (tk) {
         hipLaunchKernelGGL(fe_tk_commit_kernel, dim3(S), dim3(256), 0, h->stream, d, bd, td);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(tk->host, tk->dev[tk->cur ^ 1], tk->bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(tk->host, tk->dev[tk->cur ^ 1], tk_down, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return tk_collect(h, who, S, out, tout);
+        return tk_collect(h, who, S, out, tout, lists);
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(hB, q->d_b, q->b_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1042,11 +1045,12 @@ extern "C" int vg_fe_tracks_begin(vg_handle* h) {
     t->cur = 0;
     t->n.assign((size_t)s->cams, 0);
     t->begun = true;
+    h->ba.seq.vio = false;                // (vg_vio_*: a bridge over the lists just emptied ends here)
     return VG_OK;
 }
 
 // the lists the commit kernel left in the pinned mirror -> the caller's vg_fe_tracks_out; the step has succeeded: they become current
-static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_frame_out* fo, vg_fe_tracks_out* tout) {
+static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_frame_out* fo, vg_fe_tracks_out* tout, bool lists) {
     FeState* s = h->fe;
     TkState* t = s->tk;
     const size_t cap = (size_t)s->max_pts;
@@ -1066,25 +1070,26 @@ static int tk_collect(vg_handle* h, const char* who, const int S, const vg_fe_fr
         o.n = hd[TK_N]; o.n_id = hd[TK_NID]; o.n_msg = hd[TK_NMSG];
         o.n1 = fo[c].n1; o.n2 = fo[c].n2; o.ransac_ran = fo[c].ransac_ran; o.n_kept = hd[TK_NK]; o.n_new = hd[TK_NNEW];
         o.fallback = fo[c].fallback; o.ransac_best = fo[c].ransac_best; o.ransac_niters = fo[c].ransac_niters;
+        t->n[c] = o.n;
+        if (!lists) continue;
         o.ids = u.ids + c * cap; o.track_cnt = u.cnt + c * cap; o.cur_xy = u.cur_xy + c * cap * 2; o.un_xy = u.un_xy + c * cap * 2;
         o.vel_xy = u.vel + c * cap * 2; o.msg_id = u.msg_id + c * cap; o.msg_obs = u.msg_obs + c * cap * 7;
-        t->n[c] = o.n;
     }
     t->cur ^= 1;
     return VG_OK;
 }
 
-extern "C" int vg_fe_tracks_step(vg_handle* h, int n_streams, const vg_fe_tracks_in* in, vg_fe_tracks_out* out) {
-    VG_RANGE("vg_fe_tracks_step");
+// the body of vg_fe_tracks_step; vg_vio_step_async (ba_host.hip) runs the same frame under its own name, with or without the lists
+extern "C" int fe_tracks_step_impl(vg_handle* h, const char* who, int n_streams, const vg_fe_tracks_in* in, vg_fe_tracks_out* out, int lists) {
     if (!h || !h->fe || !in || !out || n_streams < 1) return VG_ERR_BAD_ARG;
     FeState* s = h->fe;
-    if (n_streams != s->cams) { h->err = "vg_fe_tracks_step: n_streams differs from n_cams of vg_fe_configure (the streams advance together)"; return VG_ERR_BAD_ARG; }
-    if (!s->tk || !s->tk->begun) { h->err = "vg_fe_tracks_step: no resident lists (vg_fe_tracks_begin)"; return VG_ERR_BAD_ARG; }
+    if (n_streams != s->cams) { h->err = std::string(who) + ": n_streams differs from n_cams of vg_fe_configure (the streams advance together)"; return VG_ERR_BAD_ARG; }
+    if (!s->tk || !s->tk->begun) { h->err = std::string(who) + ": no resident lists (vg_fe_tracks_begin)"; return VG_ERR_BAD_ARG; }
     std::vector<vg_fe_frame_in> fin((size_t)n_streams);
     std::vector<vg_fe_frame_out> fout((size_t)n_streams);
     for (int c = 0; c < n_streams; ++c) {
         const vg_fe_tracks_in& t = in[c];
-        if (t.struct_size != (int)sizeof(vg_fe_tracks_in)) { h->err = "vg_fe_tracks_step: struct_size of a stream"; return VG_ERR_BAD_ARG; }
+        if (t.struct_size != (int)sizeof(vg_fe_tracks_in)) { h->err = std::string(who) + ": struct_size of a stream"; return VG_ERR_BAD_ARG; }
         vg_fe_frame_in& f = fin[c];
         memset(&f, 0, sizeof(f));
         f.struct_size = (int)sizeof(vg_fe_frame_in);
@@ -1094,10 +1099,29 @@ extern "C" int vg_fe_tracks_step(vg_handle* h, int n_streams, const vg_fe_tracks
         memcpy(f.intr, t.intr, sizeof(f.intr));
         f.base_mask = t.base_mask;
     }
-    const int rc = fe_read_image_streams(h, "vg_fe_tracks_step", n_streams, fin.data(), fout.data(), in, out);
+    const int rc = fe_read_image_streams(h, who, n_streams, fin.data(), fout.data(), in, out, lists != 0);
     // (an error after the upload: the lists stand as they were -- only a finished step makes the committed copy current -- but the
     //  frames have moved)
     return rc;
+}
+
+extern "C" int vg_fe_tracks_step(vg_handle* h, int n_streams, const vg_fe_tracks_in* in, vg_fe_tracks_out* out) {
+    VG_RANGE("vg_fe_tracks_step");
+    return fe_tracks_step_impl(h, "vg_fe_tracks_step", n_streams, in, out, 1);
+}
+
+// what vg_vio_begin / vg_vio_step_async ask the front end: streams and capacity of the resident lists (VG_ERR_BAD_ARG: none begun) ...
+extern "C" int fe_vio_limits(vg_handle* h, int* n_cams, int* max_points) {
+    FeState* s = h->fe;
+    if (!s || !s->tk || !s->tk->begun) return VG_ERR_BAD_ARG;
+    *n_cams = s->cams; *max_points = s->max_pts;
+    return VG_OK;
+}
+// ... and where the commit kernel of the last finished step left every stream's message, on the device
+extern "C" void fe_vio_message(vg_handle* h, const int** tk_hdr, const int** msg_id, const double** msg_obs) {
+    const TkState* t = h->fe->tk;
+    const TkBuf u = tk_buf(t, t->dev[t->cur]);
+    *tk_hdr = u.hdr; *msg_id = u.msg_id; *msg_obs = u.msg_obs;
 }
 
 extern "C" int vg_fe_tracks_get(vg_handle* h, int cam, vg_fe_tracks_state* st) {

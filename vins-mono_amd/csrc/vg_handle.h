@@ -55,6 +55,14 @@ struct BaSeq {
     bool imu_timing = false;         // vg_ba_seq_imu_timing: HIP events around ba_seq_imu_kernel and ba_seq_merge_kernel
     bool imu_timed = false;          // the last step recorded them
     hipEvent_t ev_imu[4] = {nullptr, nullptr, nullptr, nullptr};
+    // ---- the front end feeds the sequence on the device (vg_vio_*): the message of every stream goes from the commit kernel's output
+    //      into in_i / in_d at the CAPACITY strides (ba_seq_bridge_kernel); what goes up per step is vio_d, per window
+    //      [n_samples (an int in the first of 8 doubles) | samples n x 7], packed at the largest sample count of the step
+    bool vio = false;                // vg_vio_begin .. vg_vio_end / vg_ba_seq_end / vg_fe_configure / vg_fe_tracks_begin
+    int vio_flags = 0;               // VG_VIO_*
+    bool vio_staged = false;         // in_i / in_d hold what the last step's bridge kernel staged (vg_vio_get_frame)
+    double* vio_d = nullptr;         // [nwin][8 + up8(7 MS)]
+    PinnedBuf<double> h_vio;
 };
 
 struct BaBatch {

@@ -43,6 +43,19 @@ class TracksOut(C.Structure):
                 ("ids", _i4), ("track_cnt", _i4), ("cur_xy", _f4), ("un_xy", _f4), ("vel_xy", _f4), ("msg_id", _i4), ("msg_obs", _f8)]
 
 
+class VioIn(C.Structure):
+    """vg_vio_in (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("n_samples", C.c_int), ("samples", _f8), ("fe", TracksIn)]
+
+
+class VioOut(C.Structure):
+    """vg_vio_out (include/vinsgpu.h)"""
+    _fields_ = [("fe", TracksOut)]
+
+
+VG_VIO_LISTS = 1
+
+
 class TracksState(C.Structure):
     """vg_fe_tracks_state (include/vinsgpu.h)"""
     _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("n_id", C.c_int), ("prev_time", C.c_double), ("cur_xy", _f4), ("ids", _i4),
@@ -118,6 +131,8 @@ class FrontEnd:
             L.vg_fe_tracks_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(TracksIn), C.POINTER(TracksOut)]
             L.vg_fe_tracks_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(TracksState)]
             L.vg_fe_tracks_set.argtypes = [C.c_void_p, C.c_int, C.POINTER(TracksState)]
+        if hasattr(L, "vg_vio_step_async"):               # (a library built before the one-call path: vio_step() raises AttributeError)
+            L.vg_vio_step_async.argtypes = [C.c_void_p, C.c_int, C.POINTER(VioIn), C.POINTER(VioOut)]
         self.hd._chk(L.vg_fe_configure(self.h, width, height, n_cams, max_points), "vg_fe_configure")
 
     def _imgs(self, frames):
@@ -397,6 +412,16 @@ class FrontEnd:
         track_cnt, cur_xy, un_xy, vel_xy, msg_id, msg_obs and the diagnostics of vg_fe_tracks_out."""
         m = len(publish_list)
         S = m if n_streams is None else int(n_streams)
+        tin, _keep = self._tracks_in(imgs, stamps, publish_list, intr_list, max_cnt, min_dist, equalize, f_threshold, focal_length, quality,
+                                     base_masks, orders, struct_size)
+        to = (TracksOut * m)()
+        self.hd._chk(self.lib.vg_fe_tracks_step(self.h, S, tin, to), "vg_fe_tracks_step")
+        return [self._tracks_out(to[c]) for c in range(m)]
+
+    def _tracks_in(self, imgs, stamps, publish_list, intr_list, max_cnt, min_dist, equalize, f_threshold, focal_length, quality, base_masks,
+                   orders, struct_size):
+        """the vg_fe_tracks_in array of one step and what must outlive the call (frames, masks, callbacks)"""
+        m = len(publish_list)
 
         def per(v):
             return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * m
@@ -438,26 +463,50 @@ class FrontEnd:
                 f.base_mask = masks[c].ctypes.data_as(_u8)
             cbs.append(make_cb(orders[c]) if orders[c] is not None else C.cast(None, TRACKS_ORDER_FN))
             f.order = cbs[-1]
-        to = (TracksOut * m)()
-        self.hd._chk(self.lib.vg_fe_tracks_step(self.h, S, tin, to), "vg_fe_tracks_step")
+        return tin, (frames, masks, cbs)
+
+    @staticmethod
+    def _tracks_out(o, lists=True):
+        """numpy copies of one vg_fe_tracks_out; lists False: the counts, and which array pointers were NULL"""
 
         def arr(ptr, shape, dtype):
             k = int(np.prod(shape))
             return np.ctypeslib.as_array(ptr, shape).copy() if k and ptr else np.zeros(shape, dtype)
 
-        outs = []
+        out = {k: int(getattr(o, k)) for k in ("n", "n_id", "n_msg", "n1", "n2", "n_kept", "n_new", "fallback", "ransac_best", "ransac_niters")}
+        out["ransac_ran"] = bool(o.ransac_ran)
+        if not lists:
+            out["null_pointers"] = [k for k in ("ids", "track_cnt", "cur_xy", "un_xy", "vel_xy", "msg_id", "msg_obs") if not getattr(o, k)]
+            return out
+        out["ids"] = arr(o.ids, (o.n,), np.int32)
+        out["track_cnt"] = arr(o.track_cnt, (o.n,), np.int32)
+        for k in ("cur_xy", "un_xy", "vel_xy"):
+            out[k] = arr(getattr(o, k), (o.n, 2), np.float32)
+        out["msg_id"] = arr(o.msg_id, (o.n_msg,), np.int32)
+        out["msg_obs"] = arr(o.msg_obs, (o.n_msg, 7), np.float64)
+        return out
+
+    def vio_step(self, samples, imgs, stamps, publish_list, intr_list, max_cnt=150, min_dist=30, equalize=False, f_threshold=1.0, focal_length=460.0,
+                 quality=0.01, base_masks=None, orders=None, n_streams=None, struct_size=None, vio_struct_size=None, lists=False):
+        """vg_vio_step_async: one frame for every stream and, when it publishes, the estimator step of window c from stream c's message
+        on the device.  samples[c]: (n, 7) [dt acc gyr] since the previous PUBLISHED frame, None / empty on a frame that does not
+        publish; everything else as tracks_step.  lists: the bridge was begun with VG_VIO_LISTS (the dicts of tracks_step); otherwise
+        the counts of vg_fe_tracks_out and `null_pointers`, the names of its array pointers that were NULL."""
+        m = len(publish_list)
+        S = m if n_streams is None else int(n_streams)
+        tin, _keep = self._tracks_in(imgs, stamps, publish_list, intr_list, max_cnt, min_dist, equalize, f_threshold, focal_length, quality,
+                                     base_masks, orders, struct_size)
+        vin, smp = (VioIn * m)(), []
         for c in range(m):
-            o = to[c]
-            out = {k: int(getattr(o, k)) for k in ("n", "n_id", "n_msg", "n1", "n2", "n_kept", "n_new", "fallback", "ransac_best", "ransac_niters")}
-            out["ransac_ran"] = bool(o.ransac_ran)
-            out["ids"] = arr(o.ids, (o.n,), np.int32)
-            out["track_cnt"] = arr(o.track_cnt, (o.n,), np.int32)
-            for k in ("cur_xy", "un_xy", "vel_xy"):
-                out[k] = arr(getattr(o, k), (o.n, 2), np.float32)
-            out["msg_id"] = arr(o.msg_id, (o.n_msg,), np.int32)
-            out["msg_obs"] = arr(o.msg_obs, (o.n_msg, 7), np.float64)
-            outs.append(out)
-        return outs
+            a = None if samples is None or samples[c] is None else np.ascontiguousarray(samples[c], np.float64).reshape(-1, 7)
+            smp.append(a)
+            vin[c].struct_size = C.sizeof(VioIn) if vio_struct_size is None else int(vio_struct_size)
+            vin[c].n_samples = 0 if a is None else len(a)
+            vin[c].samples = a.ctypes.data_as(_f8) if a is not None and a.size else None
+            vin[c].fe = tin[c]
+        vo = (VioOut * m)()
+        self.hd._chk(self.lib.vg_vio_step_async(self.h, S, vin, vo), "vg_vio_step_async")
+        return [self._tracks_out(vo[c].fe, lists) for c in range(m)]
 
     def tracks_get(self, cam):
         """vg_fe_tracks_get: the list of one stream between two frames: dict(n, n_id, prev_time, cur_xy, ids, track_cnt, un_xy, in_map)"""
