@@ -7,7 +7,8 @@
 //
 // How it is used.  This file includes the reference's own "feature_tracker.h" — `camodocal::CameraPtr m_camera`, the cv::Mat
 // members, `showUndistortion`, the globals of parameters.h all stay what they are — and defines exactly those four members.  In a
-// catkin workspace: add this file and include/vinsgpu.h to feature_tracker, link libvinsgpu.so, and remove the four definitions
+// catkin workspace: add this file, include/vinsgpu.h and host/vg_pack.h (the packers it shares with the project's own classes;
+// header-only) to feature_tracker, link libvinsgpu.so, and remove the four definitions
 // from feature_tracker.cpp (or weaken them:  objcopy --weaken-symbol=_ZN14FeatureTracker9readImageERKN2cv3MatEd
 // --weaken-symbol=_ZN14FeatureTracker7setMaskEv --weaken-symbol=_ZN14FeatureTracker11rejectWithFEv
 // --weaken-symbol=_ZN14FeatureTracker17undistortedPointsEv).  feature_tracker_node.cpp, parameters.cpp, addPoints / updateID /
@@ -20,9 +21,9 @@
 // device runs :87-125 (CLAHE, pyramid, LK, border test, reduceVector) and, on a published frame, rejectWithF, setMask's walk, the
 // detection, addPoints and the lifting of undistortedPoints without the host in between; the results come back in one block.  The one
 // question a published frame still puts to the host is the ORDER of setMask's walk: the reference's std::sort by track_cnt (:48) is not
-// stable, so the order among equal counts is whatever this translation unit's std::sort makes of the sequence -- the callback below runs
-// that very sort call and hands the permutation down.  A camera that is not a camodocal::PinholeCamera takes the step-by-step members
-// (its lifting runs on the host).
+// stable, so the order among equal counts is whatever this translation unit's std::sort makes of the sequence -- the callback
+// (vg_pack::order_callback, instantiated here) runs that very sort call and hands the permutation down.  A camera that is not a
+// camodocal::PinholeCamera takes the step-by-step members (its lifting runs on the host).
 //
 // What the step-by-step bodies (setMask / rejectWithF / undistortedPoints as members, and readImage for other camera models) do instead
 // of the reference's:
@@ -48,6 +49,7 @@
 
 #include "feature_tracker.h"
 #include "vinsgpu.h"
+#include "vg_pack.h"
 
 namespace {
 
@@ -99,15 +101,11 @@ FeSide& ensure(FeatureTracker* t, int w, int h) {
 void FeatureTracker::setMask() {                                      // feature_tracker.cpp:36-69
     FeSide& s = ensure(this, COL, ROW);
     // prefer to keep features that are tracked for long time (:43-51): the reference's own sort, verbatim semantics
-    vector<pair<int, pair<cv::Point2f, int>>> cnt_pts_id;
-    for (unsigned int i = 0; i < forw_pts.size(); i++) cnt_pts_id.push_back(make_pair(track_cnt[i], make_pair(forw_pts[i], ids[i])));
-    sort(cnt_pts_id.begin(), cnt_pts_id.end(),
-         [](const pair<int, pair<cv::Point2f, int>>& a, const pair<int, pair<cv::Point2f, int>>& b) { return a.first > b.first; });
+    std::vector<float> xy;
+    std::vector<int> cnt, kept((size_t)s.capacity, 0);
+    vg_pack::OrderCtx<FeatureTracker>::SortedList cnt_pts_id;
+    vg_pack::sorted_for_setmask(*this, s.capacity, xy, cnt, cnt_pts_id);
     const int n = (int)cnt_pts_id.size();
-    if (n > s.capacity) throw std::runtime_error("FeatureTracker::setMask: more points than the configured capacity");
-    std::vector<float> xy((size_t)s.capacity * 2, 0.f);
-    std::vector<int> cnt((size_t)s.capacity, 0), kept((size_t)s.capacity, 0);
-    for (int i = 0; i < n; ++i) { xy[2 * i] = cnt_pts_id[i].second.first.x; xy[2 * i + 1] = cnt_pts_id[i].second.first.y; cnt[i] = cnt_pts_id[i].first; }
     // :38-41: the fisheye mask or all-255 is the canvas; the walk in sorted order (the device's own sort by count is stable, i.e. the
     // identity on an already sorted list) keeps a point iff the canvas is still 255 under it and blanks a disc of MIN_DIST around it
     std::vector<uint8_t> base;
@@ -120,73 +118,11 @@ void FeatureTracker::setMask() {                                      // feature
     }
     int nk = 0;
     chk(vg_fe_set_mask(s.vg, xy.data(), cnt.data(), &n, basep, MIN_DIST, kept.data(), &nk), s.vg, "vg_fe_set_mask");
-    forw_pts.clear();
-    ids.clear();
-    track_cnt.clear();
-    for (int k = 0; k < nk; ++k) {
-        const auto& it = cnt_pts_id[kept[k]];
-        forw_pts.push_back(it.second.first);
-        ids.push_back(it.second.second);
-        track_cnt.push_back(it.first);
-    }
+    vg_pack::take_setmask_result(*this, cnt_pts_id, kept.data(), nk);
 }
 
 namespace {
 void undistorted_points(FeatureTracker* t, FeSide& s, const float* lifted);
-
-// What readImage does with the statuses of a frame (:115-128, :193-198): forw_pts as the tracking left them, reduceVector by
-// `status && inBorder`, track_cnt++, reduceVector by findFundamentalMat's mask -- the reference's own reduceVector calls on the class's
-// vectors, fed with what the device computed.
-void apply_statuses(FeatureTracker* t, const vg_fe_frame_out* a, int n_in) {
-    t->forw_pts.resize(n_in);
-    for (int i = 0; i < n_in; i++) t->forw_pts[i] = cv::Point2f(a->forw_xy[2 * i], a->forw_xy[2 * i + 1]);
-    if (n_in > 0) {
-        vector<uchar> status(a->status_lk, a->status_lk + n_in);
-        reduceVector(t->prev_pts, status);
-        reduceVector(t->cur_pts, status);
-        reduceVector(t->forw_pts, status);
-        reduceVector(t->ids, status);
-        reduceVector(t->cur_un_pts, status);
-        reduceVector(t->track_cnt, status);
-    }
-    for (auto& n : t->track_cnt) n++;
-    if (a->ransac_ran) {
-        vector<uchar> status(a->status_f, a->status_f + a->n1);
-        reduceVector(t->prev_pts, status);
-        reduceVector(t->cur_pts, status);
-        reduceVector(t->forw_pts, status);
-        reduceVector(t->cur_un_pts, status);
-        reduceVector(t->ids, status);
-        reduceVector(t->track_cnt, status);
-    }
-}
-
-struct OrderCtx {
-    FeatureTracker* t;
-    int n_in;
-    vector<pair<int, pair<cv::Point2f, int>>> sorted;      // setMask's cnt_pts_id (:43), the third field holding the list index instead of the id
-};
-// the order of setMask's walk = the reference's sort call (:47-51): same element type, same comparator, same std::sort -- the permutation
-// of a sort depends on the outcomes of its comparisons only, and those look at the counts
-int order_callback(void* user, const vg_fe_frame_out* after, int* order) {
-    OrderCtx* c = static_cast<OrderCtx*>(user);
-    const FeatureTracker* t = c->t;
-    // The survivors with their counts (:115-128, :193-198: track_cnt++ after the tracking), formed ON THE SIDE: the class's vectors are
-    // only touched once the library call has returned VG_OK, so a frame that fails later (detection overflow, a HIP error) leaves the
-    // tracker as it was.
-    c->sorted.clear();
-    for (int i = 0, k = 0, idx = 0; i < c->n_in; i++) {
-        if (!after->status_lk[i]) continue;
-        const bool keep = !after->ransac_ran || after->status_f[k];
-        k++;
-        if (keep) c->sorted.push_back(make_pair(t->track_cnt[i] + 1, make_pair(cv::Point2f(after->forw_xy[2 * i], after->forw_xy[2 * i + 1]), idx++)));
-    }
-    if ((int)c->sorted.size() != after->n2) return 1;
-    sort(c->sorted.begin(), c->sorted.end(),
-         [](const pair<int, pair<cv::Point2f, int>>& a, const pair<int, pair<cv::Point2f, int>>& b) { return a.first > b.first; });
-    for (int q = 0; q < after->n2; q++) order[q] = c->sorted[q].second.second;
-    return 0;
-}
 }  // namespace
 
 void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {     // feature_tracker.cpp:81-167
@@ -201,11 +137,7 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {     // f
     if (s.pinhole && s.capacity <= 2048) {
         // ---- one call per frame
         vg_fe_frame_in in;
-        std::memset(&in, 0, sizeof(in));
-        in.struct_size = (int)sizeof(in);
-        in.img = _img.data; in.stride = (int)_img.step; in.equalize = EQUALIZE; in.publish = PUB_THIS_FRAME ? 1 : 0;
-        in.cur_xy = cur_pts.empty() ? nullptr : &cur_pts[0].x; in.n = (int)cur_pts.size();
-        in.max_cnt = MAX_CNT; in.min_dist = MIN_DIST; in.quality = 0.01; in.f_threshold = F_THRESHOLD; in.focal_length = FOCAL_LENGTH;
+        vg_pack::fill_frame_in(*this, _img, PUB_THIS_FRAME, EQUALIZE, MAX_CNT, MIN_DIST, F_THRESHOLD, FOCAL_LENGTH, in);
         std::memcpy(in.intr, s.intr, sizeof(in.intr));
         if (FISHEYE && PUB_THIS_FRAME) {                                     // :38-41: the fisheye mask is setMask's canvas
             if (fisheye_mask.rows != ROW || fisheye_mask.cols != COL) throw std::runtime_error("FeatureTracker::readImage: fisheye_mask is not ROW x COL");
@@ -217,8 +149,8 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {     // f
                 in.base_mask = s.base_copy.data();
             }
         }
-        OrderCtx ctx{this, in.n, {}};
-        in.order = order_callback; in.user = &ctx;
+        vg_pack::OrderCtx<FeatureTracker> ctx{this, in.n, {}};
+        in.order = vg_pack::order_callback<FeatureTracker>; in.user = &ctx;
         if (in.n > s.capacity) throw std::runtime_error("FeatureTracker::readImage: more points than the configured capacity");
         vg_fe_frame_out out;
         chk(vg_fe_read_image(s.vg, &in, &out), s.vg, "vg_fe_read_image");
@@ -228,22 +160,8 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {     // f
             prev_img = cur_img = forw_img = _img;
         else
             forw_img = _img;
-        apply_statuses(this, &out, in.n);                                    // only now: the call returned VG_OK
-        if (PUB_THIS_FRAME) {
-            // setMask's outcome (:53-68): the kept points in the order of the walk
-            vector<cv::Point2f> kept_pts;
-            vector<int> kept_ids, kept_cnt;
-            for (int k = 0; k < out.n_kept; k++) {
-                const auto& it = ctx.sorted[out.kept[k]];
-                kept_pts.push_back(it.second.first);
-                kept_ids.push_back(ids[it.second.second]);
-                kept_cnt.push_back(it.first);
-            }
-            forw_pts = kept_pts; ids = kept_ids; track_cnt = kept_cnt;
-            n_pts.clear();                                                   // :144-156
-            for (int k = 0; k < out.n_new; k++) n_pts.push_back(cv::Point2f(out.new_xy[2 * k], out.new_xy[2 * k + 1]));
-            addPoints();                                                     // the reference's (:71-79)
-        }
+        vg_pack::apply_statuses(*this, out, in.n);                           // only now: the call returned VG_OK
+        if (PUB_THIS_FRAME) vg_pack::apply_published(*this, out, ctx.sorted);   // (its addPoints() is the reference's, :71-79)
         if ((int)forw_pts.size() != out.n_final) throw std::runtime_error("FeatureTracker::readImage: list length differs from the device's");
         lifted = out.un_xy;
     } else {
@@ -333,15 +251,7 @@ void FeatureTracker::rejectWithF() {                                        // f
 namespace {
 // undistortedPoints() (feature_tracker.cpp:258-306); `lifted` = the (x / z, y / z) pairs of cur_pts when the device already formed them
 void undistorted_points(FeatureTracker* t, FeSide& s, const float* lifted) {
-    vector<cv::Point2f>& cur_pts = t->cur_pts;
-    vector<cv::Point2f>& cur_un_pts = t->cur_un_pts;
-    vector<cv::Point2f>& pts_velocity = t->pts_velocity;
-    vector<int>& ids = t->ids;
-    map<int, cv::Point2f>& cur_un_pts_map = t->cur_un_pts_map;
-    map<int, cv::Point2f>& prev_un_pts_map = t->prev_un_pts_map;
-    const double cur_time = t->cur_time, prev_time = t->prev_time;
-    cur_un_pts.clear();
-    cur_un_pts_map.clear();
+    const vector<cv::Point2f>& cur_pts = t->cur_pts;
     const int n = (int)cur_pts.size();
     std::vector<float> un_own;
     const float* un = lifted;
@@ -359,31 +269,7 @@ void undistorted_points(FeatureTracker* t, FeSide& s, const float* lifted) {
             }
         un = un_own.data();
     }
-    for (int i = 0; i < n; i++) {
-        cur_un_pts.push_back(cv::Point2f(un[2 * i], un[2 * i + 1]));
-        cur_un_pts_map.insert(make_pair(ids[i], cv::Point2f(un[2 * i], un[2 * i + 1])));
-    }
-    // caculate points velocity (:270-304)
-    if (!prev_un_pts_map.empty()) {
-        double dt = cur_time - prev_time;
-        pts_velocity.clear();
-        for (unsigned int i = 0; i < cur_un_pts.size(); i++) {
-            if (ids[i] != -1) {
-                std::map<int, cv::Point2f>::iterator it = prev_un_pts_map.find(ids[i]);
-                if (it != prev_un_pts_map.end()) {
-                    double v_x = (cur_un_pts[i].x - it->second.x) / dt;
-                    double v_y = (cur_un_pts[i].y - it->second.y) / dt;
-                    pts_velocity.push_back(cv::Point2f(v_x, v_y));
-                } else
-                    pts_velocity.push_back(cv::Point2f(0, 0));
-            } else {
-                pts_velocity.push_back(cv::Point2f(0, 0));
-            }
-        }
-    } else {
-        for (unsigned int i = 0; i < cur_pts.size(); i++) pts_velocity.push_back(cv::Point2f(0, 0));
-    }
-    prev_un_pts_map = cur_un_pts_map;
+    vg_pack::lifted_points(*t, un);                                          // cur_un_pts, the map, the velocities (:267-304)
 }
 }  // namespace
 

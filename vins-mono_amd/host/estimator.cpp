@@ -2,6 +2,7 @@
 // vins_estimator/src/estimator.cpp:486-619; optimization() follows :670-1003 with the ceres::Problem, ceres::Solve
 // and the MarginalizationInfo machinery replaced by ONE call of vg_ba_optimize (solve + gauge fix + marginalization).
 #include "estimator.h"
+#include "vg_pack.h"
 #include "yaml_config.h"
 #include <cmath>
 #include <cstring>
@@ -125,12 +126,7 @@ void Estimator::repropagate(IntegrationBase* p) {
     const int off[2] = {0, n};
     vg_imu_preint out;
     if (vg_imu_preintegrate(vg_, 1, off, smp.data(), first, bias, noise, &out) != VG_OK) throw std::runtime_error(std::string("vg_imu_preintegrate: ") + vg_last_error(vg_));
-    p->sum_dt = out.sum_dt;
-    p->delta_p = Vector3d(out.delta_p[0], out.delta_p[1], out.delta_p[2]);
-    p->delta_v = Vector3d(out.delta_v[0], out.delta_v[1], out.delta_v[2]);
-    p->delta_q = Quaterniond(out.delta_q[3], out.delta_q[0], out.delta_q[1], out.delta_q[2]);
-    for (int r = 0; r < 15; ++r)
-        for (int c = 0; c < 15; ++c) { p->jacobian(r, c) = out.jacobian[r * 15 + c]; p->covariance(r, c) = out.covariance[r * 15 + c]; }
+    vg_pack::preint_from_abi(*p, out);
 }
 
 void Estimator::slideWindow() {
@@ -282,82 +278,22 @@ void Estimator::optimization() {
     vector2double();                                            // estimator.cpp:701
     const int K = WINDOW_SIZE + 1;
     // ---- factor tables instead of problem.AddResidualBlock (:711-764)
-    vector<int> lm_start, lm_nobs, lm_off;
-    vector<double> obs;
-    for (auto& it : f_manager.feature) {
-        it.used_num = it.feature_per_frame.size();
-        if (!(it.used_num >= 2 && it.start_frame < WINDOW_SIZE - 2)) continue;
-        lm_start.push_back(it.start_frame);
-        lm_nobs.push_back((int)it.feature_per_frame.size());
-        lm_off.push_back((int)obs.size() / 7);
-        for (auto& f : it.feature_per_frame) {
-            const double row[7] = {f.point.x(), f.point.y(), f.uv.x(), f.uv.y(), f.velocity.x(), f.velocity.y(), f.cur_td};
-            obs.insert(obs.end(), row, row + 7);
-        }
-    }
-    const int L = (int)lm_start.size();
-    // relocalisation factors (:769-801): ProjectionFactor(first observation, matched point) on (para_Pose[start], relo_Pose,
-    // ex, depth) for every optimised landmark that started at or before the loop frame and has a match (match_points are
-    // sorted by feature id, like f_manager.feature)
-    vector<int> relo_lm;
-    vector<double> relo_xy;
-    if (relocalization_info) {
-        size_t retrive = 0;
-        int feature_index = -1;
-        for (auto& it : f_manager.feature) {
-            if (!(it.used_num >= 2 && it.start_frame < WINDOW_SIZE - 2)) continue;
-            ++feature_index;
-            if (it.start_frame > relo_frame_local_index) continue;
-            while (retrive < match_points.size() && (int)match_points[retrive].z() < it.feature_id) ++retrive;
-            if (retrive < match_points.size() && (int)match_points[retrive].z() == it.feature_id) {
-                relo_lm.push_back(feature_index);
-                relo_xy.push_back(match_points[retrive].x());
-                relo_xy.push_back(match_points[retrive].y());
-                ++retrive;
-            }
-        }
-    }
+    vg_pack::FactorTables ft;
+    vg_pack::collect_factors(*this, WINDOW_SIZE, ft);
+    const int L = (int)ft.lm_start.size();
     vector<vg_imu_preint> imu(K - 1);
-    for (int i = 0; i < WINDOW_SIZE; i++) {                      // IMUFactor(pre_integrations[j]), j = i + 1 (:711-718)
-        const IntegrationBase* p = pre_integrations[i + 1];
-        vg_imu_preint& m = imu[i];
-        memset(&m, 0, sizeof(m));
-        if (!p) continue;
-        m.valid = 1; m.sum_dt = p->sum_dt;
-        for (int k = 0; k < 3; ++k) { m.delta_p[k] = p->delta_p(k); m.delta_v[k] = p->delta_v(k); m.linearized_ba[k] = p->linearized_ba(k); m.linearized_bg[k] = p->linearized_bg(k); }
-        m.delta_q[0] = p->delta_q.x(); m.delta_q[1] = p->delta_q.y(); m.delta_q[2] = p->delta_q.z(); m.delta_q[3] = p->delta_q.w();
-        for (int r = 0; r < 15; ++r)                            // Eigen is column-major, the C-ABI row-major: convert explicitly
-            for (int c = 0; c < 15; ++c) { m.jacobian[r * 15 + c] = p->jacobian(r, c); m.covariance[r * 15 + c] = p->covariance(r, c); }
-    }
+    for (int i = 0; i < WINDOW_SIZE; i++) vg_pack::preint_to_abi(imu[i], pre_integrations[i + 1]);    // IMUFactor(pre_integrations[j]), j = i + 1 (:711-718)
     vg_ba_problem pb;
     memset(&pb, 0, sizeof(pb));
-    pb.K = K; pb.L = L; pb.n_obs = (int)obs.size() / 7;
+    pb.K = K; pb.L = L; pb.n_obs = (int)ft.obs.size() / 7;
     pb.pose = &para_Pose[0][0]; pb.speedbias = &para_SpeedBias[0][0]; pb.ex_pose = &para_Ex_Pose[0][0]; pb.td = para_Td[0][0];
     pb.inv_depth = &para_Feature[0][0];
-    pb.lm_start = lm_start.data(); pb.lm_nobs = lm_nobs.data(); pb.lm_obs_off = lm_off.data(); pb.obs = obs.data(); pb.imu = imu.data();
-    // MarginalizationFactor(last_marginalization_info) on last_marginalization_parameter_blocks (:703-709): the blocks are
-    // identified by their para_* ADDRESSES, as in the reference; the C-ABI wants (kind, frame index)
-    vector<int> pkind, pindex;
-    vector<double> pJ0, px0;
-    if (last_marginalization_info) {
-        MarginalizationInfo* mi = last_marginalization_info;
-        const int n = mi->n, nb = (int)mi->keep_block_size.size();
-        for (int b = 0; b < nb; ++b) {
-            int kind, index;
-            if (!block_of(last_marginalization_parameter_blocks[b], kind, index)) throw std::runtime_error("prior block address outside the para_* arrays");
-            pkind.push_back(kind); pindex.push_back(index);
-            px0.insert(px0.end(), mi->keep_block_data[b], mi->keep_block_data[b] + mi->keep_block_size[b]);
-        }
-        pJ0.resize((size_t)n * n);
-        for (int r = 0; r < n; ++r)
-            for (int c = 0; c < n; ++c) pJ0[(size_t)r * n + c] = mi->linearized_jacobians(r, c);
-        pb.prior_n = n; pb.prior_nblocks = nb;
-        pb.prior_block_kind = pkind.data(); pb.prior_block_index = pindex.data();
-        pb.prior_J0 = pJ0.data(); pb.prior_r0 = mi->linearized_residuals.data(); pb.prior_x0 = px0.data();
-    }
-    relo_in_problem = relocalization_info && !relo_lm.empty();
+    pb.lm_start = ft.lm_start.data(); pb.lm_nobs = ft.lm_nobs.data(); pb.lm_obs_off = ft.lm_off.data(); pb.obs = ft.obs.data(); pb.imu = imu.data();
+    vg_pack::PriorIn prior;                                     // MarginalizationFactor(last_marginalization_info) (:703-709)
+    vg_pack::prior_to_problem(*this, prior, pb);
+    relo_in_problem = relocalization_info && !ft.relo_lm.empty();
     if (relo_in_problem) {
-        pb.relo_n = (int)relo_lm.size(); pb.relo_pose = relo_Pose; pb.relo_lm = relo_lm.data(); pb.relo_xy = relo_xy.data();
+        pb.relo_n = (int)ft.relo_lm.size(); pb.relo_pose = relo_Pose; pb.relo_lm = ft.relo_lm.data(); pb.relo_xy = ft.relo_xy.data();
     }
     pb.estimate_extrinsic = ESTIMATE_EXTRINSIC ? 1 : 0; pb.estimate_td = ESTIMATE_TD ? 1 : 0; pb.max_iters = NUM_ITERATIONS;
     pb.focal = FOCAL_LENGTH_D; pb.tr = TR; pb.row = ROW_D; pb.g_norm = G_NORM;
@@ -387,14 +323,8 @@ void Estimator::optimization() {
 void Estimator::collectPrior() {
     if (!prior_pending) return;
     prior_pending = false;
-    const int K = WINDOW_SIZE + 1;
-    const int cap = 6 * K + 32, capb = K + 8;
-    vector<int> nkind(capb), nindex(capb);
-    vector<double> nJ0((size_t)cap * cap), nr0(cap), nx0(9 * capb);      // x0 holds 9 doubles per block at most (speed-bias)
-    vg_ba_prior pr;
-    memset(&pr, 0, sizeof(pr));
-    pr.cap = cap; pr.cap_blocks = capb; pr.block_kind = nkind.data(); pr.block_index = nindex.data();
-    pr.J0 = nJ0.data(); pr.r0 = nr0.data(); pr.x0 = nx0.data();
+    vg_pack::PriorOut buf(WINDOW_SIZE + 1);
+    vg_ba_prior& pr = buf.pr;
     const int rc = vg_ba_optimize_prior(vg_, &pr);
     if (rc != VG_OK) throw std::runtime_error(std::string("vg_ba_optimize_prior: ") + vg_last_error(vg_));
     if (solver_failed) {
@@ -406,42 +336,8 @@ void Estimator::collectPrior() {
         last_marginalization_parameter_blocks.clear();
         return;
     }
-    if (pr.valid) {                                             // last_marginalization_info = marginalization_info (:926-929 / :992-996)
-        MarginalizationInfo* mi = new MarginalizationInfo();
-        mi->n = pr.n; mi->m = pr.m;
-        mi->linearized_jacobians.resize(pr.n, pr.n);
-        mi->linearized_residuals.resize(pr.n);
-        for (int r = 0; r < pr.n; ++r) {
-            mi->linearized_residuals(r) = nr0[r];
-            for (int c = 0; c < pr.n; ++c) mi->linearized_jacobians(r, c) = nJ0[(size_t)r * pr.n + c];
-        }
-        vector<double*> blocks;
-        int off = 0, x0o = 0;
-        for (int b = 0; b < pr.nblocks; ++b) {
-            const int kind = nkind[b], idx = nindex[b];
-            const int gs = kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 7), ls = kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 6);
-            mi->keep_block_size.push_back(gs);
-            mi->keep_block_idx.push_back(pr.m + off);
-            double* d = new double[gs];
-            memcpy(d, nx0.data() + x0o, sizeof(double) * gs);
-            mi->keep_block_data.push_back(d);
-            // addr_shift (:913-924 / :969-990): the block's address in the SLID window (the device already re-labelled it)
-            blocks.push_back(kind == VG_BLK_POSE ? para_Pose[idx] : kind == VG_BLK_SPEEDBIAS ? para_SpeedBias[idx] : kind == VG_BLK_EXPOSE ? para_Ex_Pose[0] : para_Td[0]);
-            off += ls; x0o += gs;
-        }
-        delete last_marginalization_info;
-        last_marginalization_info = mi;
-        last_marginalization_parameter_blocks = blocks;
-    }
+    if (pr.valid) vg_pack::install_prior(*this, pr, pr.m);      // last_marginalization_info = marginalization_info (:926-929 / :992-996)
     // else: MARGIN_SECOND_NEW without Pose[WINDOW_SIZE-1] in the prior: the old prior and its blocks stay (:935-936)
 }
 
-bool Estimator::block_of(const double* addr, int& kind, int& index) const {
-    for (int i = 0; i <= WINDOW_SIZE; ++i) {
-        if (addr == para_Pose[i]) { kind = VG_BLK_POSE; index = i; return true; }
-        if (addr == para_SpeedBias[i]) { kind = VG_BLK_SPEEDBIAS; index = i; return true; }
-    }
-    if (addr == para_Ex_Pose[0]) { kind = VG_BLK_EXPOSE; index = 0; return true; }
-    if (addr == para_Td[0]) { kind = VG_BLK_TD; index = 0; return true; }
-    return false;
-}
+bool Estimator::block_of(const double* addr, int& kind, int& index) const { return vg_pack::block_of(*this, addr, kind, index); }

@@ -1,6 +1,7 @@
 // feature_tracker.cpp — see feature_tracker.h.  Control flow follows feature_tracker/src/feature_tracker.cpp of the
 // reference (cited per block); the arithmetic runs on the GPU through libvinsgpu.so.
 #include "feature_tracker.h"
+#include "vg_pack.h"
 #include <cstring>
 #include "yaml_config.h"
 #include <algorithm>
@@ -85,23 +86,15 @@ void FeatureTracker::setMask() {                             // feature_tracker.
     // std::sort gives.  The same call is made here, and the device walks the list in that order (its own sort by count is stable,
     // i.e. the identity on a sorted list) -- the result is the reference's on the platform this is built on (tests/test_fe_dropin.py).
     // `mask` itself stays on the device: goodFeaturesToTrack below consumes it there (vg_fe_detect_masked).
-    const int n = (int)forw_pts.size();
-    if (n > fe_capacity_) throw std::runtime_error("FeatureTracker::setMask: more points than the configured capacity");
-    vector<pair<int, pair<cv::Point2f, int>>> cnt_pts_id;
-    for (int i = 0; i < n; i++) cnt_pts_id.push_back(make_pair(track_cnt[i], make_pair(forw_pts[i], ids[i])));
-    sort(cnt_pts_id.begin(), cnt_pts_id.end(),
-         [](const pair<int, pair<cv::Point2f, int>>& a, const pair<int, pair<cv::Point2f, int>>& b) { return a.first > b.first; });
-    std::vector<float> xy((size_t)fe_capacity_ * 2, 0.f);
-    std::vector<int> cnt((size_t)fe_capacity_, 0), kept((size_t)fe_capacity_, 0);
-    for (int i = 0; i < n; ++i) { xy[2 * i] = cnt_pts_id[i].second.first.x; xy[2 * i + 1] = cnt_pts_id[i].second.first.y; cnt[i] = cnt_pts_id[i].first; }
+    std::vector<float> xy;
+    std::vector<int> cnt, kept((size_t)fe_capacity_, 0);
+    vg_pack::OrderCtx<FeatureTracker>::SortedList cnt_pts_id;
+    vg_pack::sorted_for_setmask(*this, fe_capacity_, xy, cnt, cnt_pts_id);
+    const int n = (int)cnt_pts_id.size();
     const uint8_t* base[1] = {FISHEYE ? fisheye_mask.data : nullptr};
     int nk = 0;
     chk(vg_fe_set_mask(vg_, xy.data(), cnt.data(), &n, base, MIN_DIST, kept.data(), &nk), vg_, "vg_fe_set_mask");
-    forw_pts.clear(); ids.clear(); track_cnt.clear();
-    for (int k = 0; k < nk; ++k) {
-        const auto& it = cnt_pts_id[kept[k]];
-        forw_pts.push_back(it.second.first); ids.push_back(it.second.second); track_cnt.push_back(it.first);
-    }
+    vg_pack::take_setmask_result(*this, cnt_pts_id, kept.data(), nk);
 }
 
 void FeatureTracker::addPoints() {                            // :71-79
@@ -112,58 +105,33 @@ void FeatureTracker::addPoints() {                            // :71-79
     }
 }
 
-// What readImage does with the statuses of a frame (:115-128, :193-198): forw_pts as the tracking left them, reduceVector by
-// `status && inBorder`, track_cnt++, reduceVector by findFundamentalMat's mask
-void FeatureTracker::applyStatuses(const vg_fe_frame_out& a, int n_in) {
-    forw_pts.resize(n_in);
-    for (int i = 0; i < n_in; i++) forw_pts[i] = cv::Point2f(a.forw_xy[2 * i], a.forw_xy[2 * i + 1]);
-    if (n_in > 0) {
-        vector<uchar> status(a.status_lk, a.status_lk + n_in);
-        reduceVector(prev_pts, status);
-        reduceVector(cur_pts, status);
-        reduceVector(forw_pts, status);
-        reduceVector(ids, status);
-        reduceVector(cur_un_pts, status);
-        reduceVector(track_cnt, status);
-    }
-    for (auto& n : track_cnt) n++;
-    if (a.ransac_ran) {
-        vector<uchar> status(a.status_f, a.status_f + a.n1);
-        reduceVector(prev_pts, status);
-        reduceVector(cur_pts, status);
-        reduceVector(forw_pts, status);
-        reduceVector(cur_un_pts, status);
-        reduceVector(ids, status);
-        reduceVector(track_cnt, status);
-    }
+typedef vg_pack::OrderCtx<FeatureTracker> OrderCtx;
+
+// readImage around the library call: the arguments of a tracker's frame ...
+static void frame_input(FeatureTracker& t, const cv::Mat& _img, vg_fe_frame_in& in, OrderCtx& ctx) {
+    vg_pack::fill_frame_in(t, _img, PUB_THIS_FRAME, EQUALIZE, MAX_CNT, MIN_DIST, F_THRESHOLD, FOCAL_LENGTH, in);
+    std::memcpy(in.intr, t.m_camera.p, sizeof(in.intr));                                // (the stream lifts with its vg_fe_set_camera camera)
+    in.base_mask = (FISHEYE && PUB_THIS_FRAME) ? t.fisheye_mask.data : nullptr;         // :38-41 (contiguous ROW x COL, readFeatureTrackerParameters)
+    ctx.t = &t; ctx.n_in = in.n;
+    in.order = vg_pack::order_callback<FeatureTracker>; in.user = &ctx;
 }
 
-namespace {
-struct OrderCtx {
-    FeatureTracker* t;
-    int n_in;
-    FeatureTracker::SortedList sorted;                     // setMask's cnt_pts_id (:43) with the list index in the place of the id
-};
-// The order of setMask's walk = the reference's sort call (:47-51): std::sort by track_cnt is not stable, the order among equal counts is
-// what the platform's std::sort makes of the sequence; its permutation depends on the comparisons only, and those look at the counts.
-int order_callback(void* user, const vg_fe_frame_out* after, int* order) {
-    OrderCtx* c = static_cast<OrderCtx*>(user);
-    // the survivors with their counts (:115-128, :193-198), formed on the side: the tracker's own vectors are only touched once the library
-    // call has returned VG_OK, so a frame that fails later leaves the tracker as it was
-    c->sorted.clear();
-    for (int i = 0, k = 0, idx = 0; i < c->n_in; i++) {
-        if (!after->status_lk[i]) continue;
-        const bool keep = !after->ransac_ran || after->status_f[k];
-        k++;
-        if (keep) c->sorted.push_back(make_pair(c->t->track_cnt[i] + 1, make_pair(cv::Point2f(after->forw_xy[2 * i], after->forw_xy[2 * i + 1]), idx++)));
-    }
-    if ((int)c->sorted.size() != after->n2) return 1;
-    sort(c->sorted.begin(), c->sorted.end(),
-         [](const pair<int, pair<cv::Point2f, int>>& a, const pair<int, pair<cv::Point2f, int>>& b) { return a.first > b.first; });
-    for (int q = 0; q < after->n2; q++) order[q] = c->sorted[q].second.second;
-    return 0;
+// ... and everything readImage does once the call has returned VG_OK (ctx.sorted: setMask's list as the order callback made it).
+// FeatureTrackerBatch runs the two for S trackers around ONE call.
+static void apply_frame(FeatureTracker& t, const cv::Mat& _img, const vg_fe_frame_out& out, const OrderCtx& ctx) {
+    if (t.forw_img.empty()) t.prev_img = t.cur_img = t.forw_img = _img;
+    else t.forw_img = _img;
+    vg_pack::apply_statuses(t, out, ctx.n_in);                               // only now: the call returned VG_OK
+    if (PUB_THIS_FRAME) vg_pack::apply_published(t, out, ctx.sorted);
+    if ((int)t.forw_pts.size() != out.n_final) throw std::runtime_error("FeatureTracker::readImage: list length differs from the device's");
+    t.prev_img = t.cur_img;                                                  // :160-166
+    t.prev_pts = t.cur_pts;
+    t.prev_un_pts = t.cur_un_pts;
+    t.cur_img = t.forw_img;
+    t.cur_pts = t.forw_pts;
+    vg_pack::lifted_points(t, out.un_xy);
+    t.prev_time = t.cur_time;
 }
-}  // namespace
 
 // ONE library call per frame (vg_fe_read_image): the frame and cur_pts go up in one block; CLAHE, pyramid, LK, the border test,
 // reduceVector and -- on a published frame -- rejectWithF, setMask's walk, goodFeaturesToTrack, addPoints and the lifting of
@@ -187,50 +155,11 @@ void FeatureTracker::readImage(const cv::Mat& _img, double _cur_time) {    // :8
     }
     if ((int)cur_pts.size() > fe_capacity_) throw std::runtime_error("FeatureTracker::readImage: more points than the configured capacity");
     vg_fe_frame_in in;
-    frameInput(_img, in);
-    OrderCtx ctx{this, in.n, {}};
-    in.order = order_callback; in.user = &ctx;
+    OrderCtx ctx;
+    frame_input(*this, _img, in, ctx);
     vg_fe_frame_out out;
     chk(vg_fe_read_image(vg_, &in, &out), vg_, "vg_fe_read_image");
-    applyFrame(_img, out, in.n, ctx.sorted);
-}
-
-void FeatureTracker::frameInput(const cv::Mat& _img, vg_fe_frame_in& in) const {
-    std::memset(&in, 0, sizeof(in));
-    in.struct_size = (int)sizeof(in);
-    in.img = _img.data; in.stride = (int)_img.step; in.equalize = EQUALIZE; in.publish = PUB_THIS_FRAME ? 1 : 0;
-    in.cur_xy = cur_pts.empty() ? nullptr : &cur_pts[0].x; in.n = (int)cur_pts.size();
-    in.max_cnt = MAX_CNT; in.min_dist = MIN_DIST; in.quality = 0.01; in.f_threshold = F_THRESHOLD; in.focal_length = FOCAL_LENGTH;
-    std::memcpy(in.intr, m_camera.p, sizeof(in.intr));                                  // (the stream lifts with its vg_fe_set_camera camera)
-    in.base_mask = (FISHEYE && PUB_THIS_FRAME) ? fisheye_mask.data : nullptr;           // :38-41 (contiguous ROW x COL, readFeatureTrackerParameters)
-}
-
-void FeatureTracker::applyFrame(const cv::Mat& _img, const vg_fe_frame_out& out, int n_in, const SortedList& sorted) {
-    if (forw_img.empty()) prev_img = cur_img = forw_img = _img;
-    else forw_img = _img;
-    applyStatuses(out, n_in);                                                // only now: the call returned VG_OK
-    if (PUB_THIS_FRAME) {
-        vector<cv::Point2f> kept_pts;                                        // setMask's outcome (:53-68): the kept points in walk order
-        vector<int> kept_ids, kept_cnt;
-        for (int k = 0; k < out.n_kept; k++) {
-            const auto& it = sorted[out.kept[k]];
-            kept_pts.push_back(it.second.first);
-            kept_ids.push_back(ids[it.second.second]);
-            kept_cnt.push_back(it.first);
-        }
-        forw_pts = kept_pts; ids = kept_ids; track_cnt = kept_cnt;
-        n_pts.clear();                                                       // :144-156
-        for (int k = 0; k < out.n_new; k++) n_pts.push_back(cv::Point2f(out.new_xy[2 * k], out.new_xy[2 * k + 1]));
-        addPoints();
-    }
-    if ((int)forw_pts.size() != out.n_final) throw std::runtime_error("FeatureTracker::readImage: list length differs from the device's");
-    prev_img = cur_img;                                                      // :160-166
-    prev_pts = cur_pts;
-    prev_un_pts = cur_un_pts;
-    cur_img = forw_img;
-    cur_pts = forw_pts;
-    liftedPoints(out.un_xy);
-    prev_time = cur_time;
+    apply_frame(*this, _img, out, ctx);
 }
 
 void FeatureTracker::rejectWithF() {                                       // feature_tracker.cpp:169-202
@@ -322,37 +251,7 @@ void FeatureTracker::undistortedPoints() {                                   // 
     std::vector<float> un((size_t)std::max(n, 1) * 2);
     const vg_fe_camera cam = m_camera.abi();
     if (n > 0) chk(vg_fe_lift(vg_, &cam, &cur_pts[0].x, n, un.data()), vg_, "vg_fe_lift");
-    liftedPoints(un.data());
-}
-
-// :262-304 given the lifted (x / z, y / z) pairs of cur_pts
-void FeatureTracker::liftedPoints(const float* un) {
-    cur_un_pts.clear();
-    cur_un_pts_map.clear();
-    const int n = (int)cur_pts.size();
-    for (int i = 0; i < n; i++) {
-        cur_un_pts.push_back(cv::Point2f(un[2 * i], un[2 * i + 1]));
-        cur_un_pts_map.insert(make_pair(ids[i], cv::Point2f(un[2 * i], un[2 * i + 1])));
-    }
-    if (!prev_un_pts_map.empty()) {
-        double dt = cur_time - prev_time;
-        pts_velocity.clear();
-        for (unsigned int i = 0; i < cur_un_pts.size(); i++) {
-            if (ids[i] != -1) {
-                auto it = prev_un_pts_map.find(ids[i]);
-                if (it != prev_un_pts_map.end()) {
-                    double v_x = (cur_un_pts[i].x - it->second.x) / dt;
-                    double v_y = (cur_un_pts[i].y - it->second.y) / dt;
-                    pts_velocity.push_back(cv::Point2f((float)v_x, (float)v_y));
-                } else
-                    pts_velocity.push_back(cv::Point2f(0, 0));
-            } else
-                pts_velocity.push_back(cv::Point2f(0, 0));
-        }
-    } else {
-        for (unsigned int i = 0; i < cur_pts.size(); i++) pts_velocity.push_back(cv::Point2f(0, 0));
-    }
-    prev_un_pts_map = cur_un_pts_map;
+    vg_pack::lifted_points(*this, un.data());
 }
 
 // ---- FeatureTrackerBatch: the node's loop over trackerData[i].readImage (feature_tracker_node.cpp:82-101) with one library call
@@ -381,13 +280,11 @@ void FeatureTrackerBatch::readImages(const vector<cv::Mat>& imgs, const vector<d
     vector<OrderCtx> ctx((size_t)S);
     for (int c = 0; c < S; c++) {
         if ((int)trackers[c].cur_pts.size() > fe_capacity_) throw std::runtime_error("FeatureTrackerBatch::readImages: more points than the configured capacity");
-        trackers[c].frameInput(imgs[c], in[c]);
-        ctx[c].t = &trackers[c]; ctx[c].n_in = in[c].n;
-        in[c].order = order_callback; in[c].user = &ctx[c];
+        frame_input(trackers[c], imgs[c], in[c], ctx[c]);
     }
     chk(vg_fe_read_image_batch(vg_, S, in.data(), out.data()), vg_, "vg_fe_read_image_batch");
     for (int c = 0; c < S; c++) {                                            // only now: the call returned VG_OK
         trackers[c].cur_time = stamps[c];
-        trackers[c].applyFrame(imgs[c], out[c], in[c].n, ctx[c].sorted);
+        apply_frame(trackers[c], imgs[c], out[c], ctx[c]);
     }
 }

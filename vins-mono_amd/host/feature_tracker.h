@@ -58,14 +58,6 @@ class FeatureTracker {
     void readIntrinsicParameter(const string& calib_file);   // PINHOLE or MEI section of the configuration file (host/yaml_config.h)
     void rejectWithF();
     void undistortedPoints();
-    // the two halves of readImage around the library call (public for the order callback; not part of the reference's interface)
-    void applyStatuses(const vg_fe_frame_out& after, int n_in);
-    void liftedPoints(const float* un_xy);
-    // readImage around the library call: the arguments of this tracker's frame, and everything readImage does once the call has returned
-    // VG_OK (`sorted`: setMask's list as the order callback made it).  FeatureTrackerBatch runs them for S trackers around ONE call.
-    typedef vector<pair<int, pair<cv::Point2f, int>>> SortedList;
-    void frameInput(const cv::Mat& _img, vg_fe_frame_in& in) const;
-    void applyFrame(const cv::Mat& _img, const vg_fe_frame_out& out, int n_in, const SortedList& sorted);
 
     cv::Mat mask;
     cv::Mat fisheye_mask;

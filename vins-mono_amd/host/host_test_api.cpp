@@ -7,12 +7,11 @@
 #include <stdexcept>
 #include "estimator.h"
 #include "feature_tracker.h"
+#include "vg_pack.h"
 
-extern "C" int vins_host_estimator_roundtrip(const vg_ba_problem* p, int margin_flag, double* pose_out /*K*7*/, double* sb_out /*K*9*/,
-                                             double* depth_out /*L*/, int* solve_flag_out /*L*/, int* prior_n, int* prior_nblocks,
-                                             int* prior_kind, int* prior_index, double* prior_J0, double* prior_r0, int* iters) {
-    if (p->K != WINDOW_SIZE + 1) return -1;
-    Estimator est;
+// The Estimator as the surrounding reference code would have left it before optimization(): the configuration globals, Ps / Rs / Vs /
+// Bas / Bgs, the extrinsics, td and pre_integrations[] (objects in pre[], owned by the caller) from a vg_ba_problem
+static void fill_state(Estimator& est, const vg_ba_problem* p, IntegrationBase* pre /*WINDOW_SIZE + 1*/) {
     ESTIMATE_EXTRINSIC = p->estimate_extrinsic; ESTIMATE_TD = p->estimate_td; NUM_ITERATIONS = p->max_iters;
     TR = p->tr; ROW_D = p->row; FOCAL_LENGTH_D = p->focal; G_NORM = p->g_norm;
     for (int i = 0; i <= WINDOW_SIZE; ++i) {
@@ -25,19 +24,19 @@ extern "C" int vins_host_estimator_roundtrip(const vg_ba_problem* p, int margin_
     est.tic[0] = Vector3d(p->ex_pose[0], p->ex_pose[1], p->ex_pose[2]);
     est.ric[0] = Quaterniond(p->ex_pose[6], p->ex_pose[3], p->ex_pose[4], p->ex_pose[5]).toRotationMatrix();
     est.td = p->td;
-    IntegrationBase pre[WINDOW_SIZE + 1];
     for (int k = 0; k < WINDOW_SIZE; ++k) {
-        const vg_imu_preint& m = p->imu[k];
-        IntegrationBase& q = pre[k + 1];
-        q.sum_dt = m.sum_dt;
-        q.delta_p = Vector3d(m.delta_p[0], m.delta_p[1], m.delta_p[2]); q.delta_v = Vector3d(m.delta_v[0], m.delta_v[1], m.delta_v[2]);
-        q.linearized_ba = Vector3d(m.linearized_ba[0], m.linearized_ba[1], m.linearized_ba[2]);
-        q.linearized_bg = Vector3d(m.linearized_bg[0], m.linearized_bg[1], m.linearized_bg[2]);
-        q.delta_q = Quaterniond(m.delta_q[3], m.delta_q[0], m.delta_q[1], m.delta_q[2]);
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) { q.jacobian(r, c) = m.jacobian[r * 15 + c]; q.covariance(r, c) = m.covariance[r * 15 + c]; }
-        est.pre_integrations[k + 1] = m.valid ? &q : nullptr;
+        vg_pack::preint_from_abi(pre[k + 1], p->imu[k]);
+        est.pre_integrations[k + 1] = p->imu[k].valid ? &pre[k + 1] : nullptr;
     }
+}
+
+extern "C" int vins_host_estimator_roundtrip(const vg_ba_problem* p, int margin_flag, double* pose_out /*K*7*/, double* sb_out /*K*9*/,
+                                             double* depth_out /*L*/, int* solve_flag_out /*L*/, int* prior_n, int* prior_nblocks,
+                                             int* prior_kind, int* prior_index, double* prior_J0, double* prior_r0, int* iters) {
+    if (p->K != WINDOW_SIZE + 1) return -1;
+    Estimator est;
+    IntegrationBase pre[WINDOW_SIZE + 1];
+    fill_state(est, p, pre);
     // features: the real ones interleaved with decoys the used_num / start_frame filter must drop
     for (int l = 0; l < p->L; ++l) {
         FeaturePerId f;
@@ -58,28 +57,12 @@ extern "C" int vins_host_estimator_roundtrip(const vg_ba_problem* p, int margin_
     }
     if (p->prior_n > 0) {
         // a prior as the previous optimization() would have left it: reference-typed members + block addresses
-        MarginalizationInfo* mi = new MarginalizationInfo();
-        mi->n = p->prior_n; mi->m = 0;
-        int off = 0, x0o = 0;
-        for (int b = 0; b < p->prior_nblocks; ++b) {
-            const int kind = p->prior_block_kind[b], idx = p->prior_block_index[b];
-            const int gs = kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 7), ls = kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 6);
-            mi->keep_block_size.push_back(gs);
-            mi->keep_block_idx.push_back(off);
-            double* d = new double[gs];
-            memcpy(d, p->prior_x0 + x0o, sizeof(double) * gs);
-            mi->keep_block_data.push_back(d);
-            est.last_marginalization_parameter_blocks.push_back(kind == VG_BLK_POSE ? est.para_Pose[idx] : kind == VG_BLK_SPEEDBIAS ? est.para_SpeedBias[idx]
-                                                                : kind == VG_BLK_EXPOSE ? est.para_Ex_Pose[0] : est.para_Td[0]);
-            off += ls; x0o += gs;
-        }
-        mi->linearized_jacobians.resize(p->prior_n, p->prior_n);
-        mi->linearized_residuals.resize(p->prior_n);
-        for (int r = 0; r < p->prior_n; ++r) {
-            mi->linearized_residuals(r) = p->prior_r0[r];
-            for (int c = 0; c < p->prior_n; ++c) mi->linearized_jacobians(r, c) = p->prior_J0[(size_t)r * p->prior_n + c];
-        }
-        est.last_marginalization_info = mi;
+        vg_ba_prior pr;
+        memset(&pr, 0, sizeof(pr));
+        pr.n = p->prior_n; pr.nblocks = p->prior_nblocks; pr.valid = 1;
+        pr.block_kind = const_cast<int*>(p->prior_block_kind); pr.block_index = const_cast<int*>(p->prior_block_index);
+        pr.J0 = const_cast<double*>(p->prior_J0); pr.r0 = const_cast<double*>(p->prior_r0); pr.x0 = const_cast<double*>(p->prior_x0);
+        vg_pack::install_prior(est, pr, 0);
     }
     est.marginalization_flag = margin_flag == VG_MARGIN_OLD ? Estimator::MARGIN_OLD : Estimator::MARGIN_SECOND_NEW;
     est.optimization();
@@ -136,31 +119,8 @@ static int relo_roundtrip(const vg_ba_problem* p, int relo_frame_local_index, co
                           double* relo_fixed, double* relative_t, double* relative_q, double* relative_yaw, double* drift_r, double* drift_t, bool no_match) {
     if (p->K != WINDOW_SIZE + 1 || p->relo_n <= 0) return -1;
     Estimator est;
-    ESTIMATE_EXTRINSIC = p->estimate_extrinsic; ESTIMATE_TD = p->estimate_td; NUM_ITERATIONS = p->max_iters;
-    TR = p->tr; ROW_D = p->row; FOCAL_LENGTH_D = p->focal; G_NORM = p->g_norm;
-    for (int i = 0; i <= WINDOW_SIZE; ++i) {
-        est.Ps[i] = Vector3d(p->pose[7 * i], p->pose[7 * i + 1], p->pose[7 * i + 2]);
-        est.Rs[i] = Quaterniond(p->pose[7 * i + 6], p->pose[7 * i + 3], p->pose[7 * i + 4], p->pose[7 * i + 5]).toRotationMatrix();
-        est.Vs[i] = Vector3d(p->speedbias[9 * i], p->speedbias[9 * i + 1], p->speedbias[9 * i + 2]);
-        est.Bas[i] = Vector3d(p->speedbias[9 * i + 3], p->speedbias[9 * i + 4], p->speedbias[9 * i + 5]);
-        est.Bgs[i] = Vector3d(p->speedbias[9 * i + 6], p->speedbias[9 * i + 7], p->speedbias[9 * i + 8]);
-    }
-    est.tic[0] = Vector3d(p->ex_pose[0], p->ex_pose[1], p->ex_pose[2]);
-    est.ric[0] = Quaterniond(p->ex_pose[6], p->ex_pose[3], p->ex_pose[4], p->ex_pose[5]).toRotationMatrix();
-    est.td = p->td;
     IntegrationBase pre[WINDOW_SIZE + 1];
-    for (int k = 0; k < WINDOW_SIZE; ++k) {
-        const vg_imu_preint& m = p->imu[k];
-        IntegrationBase& q = pre[k + 1];
-        q.sum_dt = m.sum_dt;
-        q.delta_p = Vector3d(m.delta_p[0], m.delta_p[1], m.delta_p[2]); q.delta_v = Vector3d(m.delta_v[0], m.delta_v[1], m.delta_v[2]);
-        q.linearized_ba = Vector3d(m.linearized_ba[0], m.linearized_ba[1], m.linearized_ba[2]);
-        q.linearized_bg = Vector3d(m.linearized_bg[0], m.linearized_bg[1], m.linearized_bg[2]);
-        q.delta_q = Quaterniond(m.delta_q[3], m.delta_q[0], m.delta_q[1], m.delta_q[2]);
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) { q.jacobian(r, c) = m.jacobian[r * 15 + c]; q.covariance(r, c) = m.covariance[r * 15 + c]; }
-        est.pre_integrations[k + 1] = m.valid ? &q : nullptr;
-    }
+    fill_state(est, p, pre);
     for (int l = 0; l < p->L; ++l) {
         FeaturePerId f;
         f.feature_id = 10 * l + 3; f.start_frame = p->lm_start[l]; f.estimated_depth = 1.0 / p->inv_depth[l];
@@ -246,12 +206,7 @@ extern "C" int vins_host_slide_second_new(int na, const double* smp_a, const dou
         est.marginalization_flag = Estimator::MARGIN_SECOND_NEW;
         est.slideWindow();
         const IntegrationBase* p = est.pre_integrations[WINDOW_SIZE - 1];
-        memset(merged, 0, sizeof(*merged));
-        merged->valid = 1; merged->sum_dt = p->sum_dt;
-        for (int k = 0; k < 3; ++k) { merged->delta_p[k] = p->delta_p(k); merged->delta_v[k] = p->delta_v(k); merged->linearized_ba[k] = p->linearized_ba(k); merged->linearized_bg[k] = p->linearized_bg(k); }
-        merged->delta_q[0] = p->delta_q.x(); merged->delta_q[1] = p->delta_q.y(); merged->delta_q[2] = p->delta_q.z(); merged->delta_q[3] = p->delta_q.w();
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) { merged->jacobian[r * 15 + c] = p->jacobian(r, c); merged->covariance[r * 15 + c] = p->covariance(r, c); }
+        vg_pack::preint_to_abi(*merged, p);
         *nsamples_out = (int)p->dt_buf.size();
         const int i = WINDOW_SIZE - 1;
         Quaterniond q(est.Rs[i]);

@@ -41,6 +41,7 @@
 #include "estimator.h"
 #include "feature_tracker.h"
 #include "resident_estimator.h"
+#include "vg_pack.h"
 
 // the front-end globals of a configuration file; the frames of the replay must have its image size, and there is no fisheye mask here
 static void replay_fe_config(const char* config, int w, int h) {
@@ -175,14 +176,7 @@ IntegrationBase* preintegrate(vg_handle* h, Reader& rd, int S, const double* bia
         p->acc_buf.push_back(Vector3d(smp[7 * i + 1], smp[7 * i + 2], smp[7 * i + 3]));
         p->gyr_buf.push_back(Vector3d(smp[7 * i + 4], smp[7 * i + 5], smp[7 * i + 6]));
     }
-    p->sum_dt = out.sum_dt;
-    p->delta_p = Vector3d(out.delta_p[0], out.delta_p[1], out.delta_p[2]);
-    p->delta_v = Vector3d(out.delta_v[0], out.delta_v[1], out.delta_v[2]);
-    p->linearized_ba = Vector3d(out.linearized_ba[0], out.linearized_ba[1], out.linearized_ba[2]);
-    p->linearized_bg = Vector3d(out.linearized_bg[0], out.linearized_bg[1], out.linearized_bg[2]);
-    p->delta_q = Quaterniond(out.delta_q[3], out.delta_q[0], out.delta_q[1], out.delta_q[2]);
-    for (int r = 0; r < 15; ++r)
-        for (int c = 0; c < 15; ++c) { p->jacobian(r, c) = out.jacobian[r * 15 + c]; p->covariance(r, c) = out.covariance[r * 15 + c]; }
+    vg_pack::preint_from_abi(*p, out);
     return p;
 }
 }  // namespace

@@ -1,28 +1,20 @@
 // resident_estimator.cpp — see resident_estimator.h.  Host code around vg_ba_seq_*: the IMU side of Estimator::processIMU
 // (estimator.cpp:83-117), the hand-over of an Estimator's window, and the per-frame packing of what processImage receives.
 #include "resident_estimator.h"
+#include "vg_pack.h"
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 
 struct ResidentEstimators::Window {
-    std::vector<double> pose, sb, ex, obs, depth, pJ0, pr0, px0;
+    std::vector<double> pose, sb, ex, obs, depth;
     std::vector<vg_imu_preint> imu;
-    std::vector<int> id, start, nobs, flag, pkind, pindex;
+    std::vector<int> id, start, nobs, flag;
+    vg_pack::PriorIn prior;
     vg_ba_problem prob;
     vg_ba_tracks tracks;
 };
-
-static void fill_preint(vg_imu_preint& m, const IntegrationBase* p) {
-    memset(&m, 0, sizeof(m));
-    if (!p) return;
-    m.valid = 1; m.sum_dt = p->sum_dt;
-    for (int k = 0; k < 3; ++k) { m.delta_p[k] = p->delta_p(k); m.delta_v[k] = p->delta_v(k); m.linearized_ba[k] = p->linearized_ba(k); m.linearized_bg[k] = p->linearized_bg(k); }
-    m.delta_q[0] = p->delta_q.x(); m.delta_q[1] = p->delta_q.y(); m.delta_q[2] = p->delta_q.z(); m.delta_q[3] = p->delta_q.w();
-    for (int r = 0; r < 15; ++r)
-        for (int c = 0; c < 15; ++c) { m.jacobian[r * 15 + c] = p->jacobian(r, c); m.covariance[r * 15 + c] = p->covariance(r, c); }
-}
 
 ResidentEstimators::ResidentEstimators(int n, int max_features, int max_new_obs)
     : est_(n), win_(n, nullptr), max_features_(max_features), max_new_obs_(max_new_obs) {
@@ -85,7 +77,7 @@ ResidentEstimators::Window* ResidentEstimators::pack(int i, Estimator& e, const 
     w->sb.assign(&e.para_SpeedBias[0][0], &e.para_SpeedBias[0][0] + 9 * K);
     w->ex.assign(&e.para_Ex_Pose[0][0], &e.para_Ex_Pose[0][0] + 7);
     w->imu.resize(K - 1);
-    for (int k = 0; k < WINDOW_SIZE; ++k) fill_preint(w->imu[k], k + 1 < WINDOW_SIZE ? e.pre_integrations[k + 1] : nullptr);
+    for (int k = 0; k < WINDOW_SIZE; ++k) vg_pack::preint_to_abi(w->imu[k], k + 1 < WINDOW_SIZE ? e.pre_integrations[k + 1] : nullptr);
     for (auto& it : e.f_manager.feature) {
         w->id.push_back(it.feature_id); w->start.push_back(it.start_frame); w->nobs.push_back((int)it.feature_per_frame.size());
         w->flag.push_back(it.solve_flag); w->depth.push_back(it.estimated_depth);
@@ -97,22 +89,7 @@ ResidentEstimators::Window* ResidentEstimators::pack(int i, Estimator& e, const 
     vg_ba_problem& pb = w->prob;
     memset(&pb, 0, sizeof(pb));
     pb.K = K; pb.pose = w->pose.data(); pb.speedbias = w->sb.data(); pb.ex_pose = w->ex.data(); pb.td = e.td; pb.imu = w->imu.data();
-    if (e.last_marginalization_info) {
-        MarginalizationInfo* mi = e.last_marginalization_info;
-        const int n = mi->n, nb = (int)mi->keep_block_size.size();
-        for (int b = 0; b < nb; ++b) {
-            int kind, index;
-            if (!e.block_of(e.last_marginalization_parameter_blocks[b], kind, index)) throw std::runtime_error("prior block address outside the para_* arrays");
-            w->pkind.push_back(kind); w->pindex.push_back(index);
-            w->px0.insert(w->px0.end(), mi->keep_block_data[b], mi->keep_block_data[b] + mi->keep_block_size[b]);
-        }
-        w->pJ0.resize((size_t)n * n);
-        for (int r = 0; r < n; ++r)
-            for (int c = 0; c < n; ++c) w->pJ0[(size_t)r * n + c] = mi->linearized_jacobians(r, c);
-        w->pr0.assign(mi->linearized_residuals.data(), mi->linearized_residuals.data() + n);
-        pb.prior_n = n; pb.prior_nblocks = nb; pb.prior_block_kind = w->pkind.data(); pb.prior_block_index = w->pindex.data();
-        pb.prior_J0 = w->pJ0.data(); pb.prior_r0 = w->pr0.data(); pb.prior_x0 = w->px0.data();
-    }
+    vg_pack::prior_to_problem(e, w->prior, pb);
     pb.estimate_extrinsic = ESTIMATE_EXTRINSIC ? 1 : 0; pb.estimate_td = ESTIMATE_TD ? 1 : 0; pb.max_iters = NUM_ITERATIONS;
     pb.focal = FOCAL_LENGTH_D; pb.tr = TR; pb.row = ROW_D; pb.g_norm = G_NORM; pb.max_solver_time_s = SOLVER_TIME;
     vg_ba_tracks& t = w->tracks;
@@ -149,12 +126,8 @@ void ResidentEstimators::handBack(int i, Estimator& e) {
     std::vector<double> pose(7 * K), sb(9 * K), ex(7);
     double td = 0;
     std::vector<vg_imu_preint> imu(K - 1);
-    const int cap = 6 * K + 32, capb = K + 8;
-    std::vector<int> pkind(capb), pindex(capb);
-    std::vector<double> pJ0((size_t)cap * cap), pr0(cap), px0(9 * capb);
-    vg_ba_prior pr;
-    memset(&pr, 0, sizeof(pr));
-    pr.cap = cap; pr.cap_blocks = capb; pr.block_kind = pkind.data(); pr.block_index = pindex.data(); pr.J0 = pJ0.data(); pr.r0 = pr0.data(); pr.x0 = px0.data();
+    vg_pack::PriorOut buf(K);
+    vg_ba_prior& pr = buf.pr;
     if (vg_ba_seq_export(vg_, i, pose.data(), sb.data(), ex.data(), &td, imu.data(), &pr) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_export: ") + vg_last_error(vg_));
     for (int k = 0; k < K; ++k) {
         const double* x = &pose[7 * k];
@@ -189,13 +162,7 @@ void ResidentEstimators::handBack(int i, Estimator& e) {
         // object is rebuilt with its sum_dt (and, for slot WINDOW_SIZE - 1, its samples); only a record that was never filled is absent.
         if (!m.valid && !(m.sum_dt > 0.0)) continue;
         IntegrationBase* p = new IntegrationBase();
-        p->sum_dt = m.sum_dt;
-        p->delta_p = Vector3d(m.delta_p[0], m.delta_p[1], m.delta_p[2]); p->delta_v = Vector3d(m.delta_v[0], m.delta_v[1], m.delta_v[2]);
-        p->linearized_ba = Vector3d(m.linearized_ba[0], m.linearized_ba[1], m.linearized_ba[2]);
-        p->linearized_bg = Vector3d(m.linearized_bg[0], m.linearized_bg[1], m.linearized_bg[2]);
-        p->delta_q = Quaterniond(m.delta_q[3], m.delta_q[0], m.delta_q[1], m.delta_q[2]);
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) { p->jacobian(r, c) = m.jacobian[r * 15 + c]; p->covariance(r, c) = m.covariance[r * 15 + c]; }
+        vg_pack::preint_from_abi(*p, m);
         if (k + 3 == K) {                                           // pre_integrations[WINDOW_SIZE - 1]: with the samples a later merge needs
             p->linearized_acc = o.prev.linearized_acc; p->linearized_gyr = o.prev.linearized_gyr;
             for (size_t q = 0; q + 6 < o.prev.samples.size(); q += 7) {
@@ -229,30 +196,7 @@ void ResidentEstimators::handBack(int i, Estimator& e) {
     e.last_marginalization_info = nullptr;
     e.last_marginalization_parameter_blocks.clear();
     e.prior_pending = false;
-    if (pr.valid && pr.n > 0) {
-        MarginalizationInfo* mi = new MarginalizationInfo();
-        mi->n = pr.n; mi->m = 0;
-        mi->linearized_jacobians.resize(pr.n, pr.n);
-        mi->linearized_residuals.resize(pr.n);
-        for (int r = 0; r < pr.n; ++r) {
-            mi->linearized_residuals(r) = pr0[r];
-            for (int c = 0; c < pr.n; ++c) mi->linearized_jacobians(r, c) = pJ0[(size_t)r * pr.n + c];
-        }
-        int off = 0, x0o = 0;
-        for (int b = 0; b < pr.nblocks; ++b) {
-            const int kind = pkind[b], idx = pindex[b];
-            const int gs = kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 7), ls = kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 6);
-            mi->keep_block_size.push_back(gs);
-            mi->keep_block_idx.push_back(off);
-            double* d = new double[gs];
-            memcpy(d, px0.data() + x0o, sizeof(double) * gs);
-            mi->keep_block_data.push_back(d);
-            e.last_marginalization_parameter_blocks.push_back(kind == VG_BLK_POSE ? e.para_Pose[idx] : kind == VG_BLK_SPEEDBIAS ? e.para_SpeedBias[idx]
-                                                              : kind == VG_BLK_EXPOSE ? e.para_Ex_Pose[0] : e.para_Td[0]);
-            off += ls; x0o += gs;
-        }
-        e.last_marginalization_info = mi;
-    }
+    if (pr.valid && pr.n > 0) vg_pack::install_prior(e, pr, 0);
 }
 
 void ResidentEstimators::begin() {

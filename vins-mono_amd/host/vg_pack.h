@@ -1,0 +1,338 @@
+// vg_pack.h — the packers between the classes' members and the C-ABI (include/vinsgpu.h), ONCE, for the project's classes
+// (estimator.h / feature_tracker.h on compat/) and for the drop-ins written against the reference's own headers (host/dropin/).
+//
+// Header-only, C++14, standard library + vinsgpu.h only: every function is a template over the class types (E an Estimator, IB an
+// IntegrationBase, T a FeatureTracker; the point type is taken from T's own lists), so both sets of types instantiate the same body.
+// Include it AFTER the class header.  Of the member types only x() / y() / z() / w(), operator(), rows() / cols(), resize(), data()
+// and the (w, x, y, z) quaternion constructor are used.  What the callers do differently on purpose (side tables, camera, gauge
+// transform of relo_Pose, configuration globals) stays in their own files.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <stdexcept>
+#include <type_traits>
+#include <utility>
+#include <vector>
+#include "vinsgpu.h"
+
+namespace vg_pack {
+
+// =================================================================================================================== back end
+
+// IntegrationBase -> vg_imu_preint (what IMUFactor reads); a null pointer = no factor for this pair (valid = 0, all zero)
+template <class IB> void preint_to_abi(vg_imu_preint& m, const IB* p) {
+    std::memset(&m, 0, sizeof(m));
+    if (!p) return;
+    m.valid = 1; m.sum_dt = p->sum_dt;
+    for (int k = 0; k < 3; ++k) { m.delta_p[k] = p->delta_p(k); m.delta_v[k] = p->delta_v(k); m.linearized_ba[k] = p->linearized_ba(k); m.linearized_bg[k] = p->linearized_bg(k); }
+    m.delta_q[0] = p->delta_q.x(); m.delta_q[1] = p->delta_q.y(); m.delta_q[2] = p->delta_q.z(); m.delta_q[3] = p->delta_q.w();
+    for (int r = 0; r < 15; ++r)                                // Eigen is column-major, the C-ABI row-major: convert explicitly
+        for (int c = 0; c < 15; ++c) { m.jacobian[r * 15 + c] = p->jacobian(r, c); m.covariance[r * 15 + c] = p->covariance(r, c); }
+}
+
+// vg_imu_preint -> the record fields of an IntegrationBase; the raw samples (dt_buf / acc_buf / gyr_buf, linearized_acc / _gyr) stay
+// with the callers that have them
+template <class IB> void preint_from_abi(IB& p, const vg_imu_preint& m) {
+    typedef typename std::decay<decltype(p.delta_q)>::type Quat;
+    p.sum_dt = m.sum_dt;
+    for (int k = 0; k < 3; ++k) { p.delta_p(k) = m.delta_p[k]; p.delta_v(k) = m.delta_v[k]; p.linearized_ba(k) = m.linearized_ba[k]; p.linearized_bg(k) = m.linearized_bg[k]; }
+    p.delta_q = Quat(m.delta_q[3], m.delta_q[0], m.delta_q[1], m.delta_q[2]);
+    for (int r = 0; r < 15; ++r)
+        for (int c = 0; c < 15; ++c) { p.jacobian(r, c) = m.jacobian[r * 15 + c]; p.covariance(r, c) = m.covariance[r * 15 + c]; }
+}
+
+// sizes of a parameter block: global (para_* doubles) and local (columns of the prior; the pose blocks lose one)
+inline int block_global_size(int kind) { return kind == VG_BLK_SPEEDBIAS ? 9 : (kind == VG_BLK_TD ? 1 : 7); }
+inline int local_size(int global_size) { return global_size == 7 ? 6 : global_size; }
+
+// (kind, frame index) of a parameter-block address inside para_Pose / para_SpeedBias / para_Ex_Pose / para_Td, and back
+template <class E> bool block_of(E& e, const double* addr, int& kind, int& index) {
+    const int frames = (int)(sizeof(e.para_Pose) / sizeof(e.para_Pose[0]));
+    for (int i = 0; i < frames; ++i) {
+        if (addr == e.para_Pose[i]) { kind = VG_BLK_POSE; index = i; return true; }
+        if (addr == e.para_SpeedBias[i]) { kind = VG_BLK_SPEEDBIAS; index = i; return true; }
+    }
+    if (addr == e.para_Ex_Pose[0]) { kind = VG_BLK_EXPOSE; index = 0; return true; }
+    if (addr == e.para_Td[0]) { kind = VG_BLK_TD; index = 0; return true; }
+    return false;
+}
+template <class E> double* block_addr(E& e, int kind, int index) {
+    return kind == VG_BLK_POSE ? e.para_Pose[index] : kind == VG_BLK_SPEEDBIAS ? e.para_SpeedBias[index] : kind == VG_BLK_EXPOSE ? e.para_Ex_Pose[0] : e.para_Td[0];
+}
+
+// The factor tables of optimization() instead of problem.AddResidualBlock (estimator.cpp:719-801)
+struct FactorTables {
+    std::vector<int> lm_start, lm_nobs, lm_off;     // per optimised landmark: first frame, observations, first row of obs
+    std::vector<double> obs;                        // rows of 7: point x y, uv, velocity, cur_td
+    std::vector<int> relo_lm;                       // relocalisation factors: landmark index ...
+    std::vector<double> relo_xy;                    // ... and matched point
+};
+template <class E> void collect_factors(E& e, int window_size, FactorTables& t) {
+    for (auto& it : e.f_manager.feature) {          // the filter of FeatureManager::getFeatureCount / getDepthVector
+        it.used_num = it.feature_per_frame.size();
+        if (!(it.used_num >= 2 && it.start_frame < window_size - 2)) continue;
+        t.lm_start.push_back(it.start_frame);
+        t.lm_nobs.push_back((int)it.feature_per_frame.size());
+        t.lm_off.push_back((int)t.obs.size() / 7);
+        for (auto& f : it.feature_per_frame) {
+            const double row[7] = {f.point.x(), f.point.y(), f.uv.x(), f.uv.y(), f.velocity.x(), f.velocity.y(), f.cur_td};
+            t.obs.insert(t.obs.end(), row, row + 7);
+        }
+    }
+    // relocalisation factors (:769-801): ProjectionFactor(first observation, matched point) on (para_Pose[start], relo_Pose, ex, depth)
+    // for every optimised landmark that started at or before the loop frame and has a match (match_points are sorted by feature id,
+    // like f_manager.feature)
+    if (!e.relocalization_info) return;
+    size_t retrive = 0;
+    int feature_index = -1;
+    for (auto& it : e.f_manager.feature) {
+        if (!(it.used_num >= 2 && it.start_frame < window_size - 2)) continue;
+        ++feature_index;
+        if (it.start_frame > e.relo_frame_local_index) continue;
+        while (retrive < e.match_points.size() && (int)e.match_points[retrive].z() < it.feature_id) ++retrive;
+        if (retrive < e.match_points.size() && (int)e.match_points[retrive].z() == it.feature_id) {
+            t.relo_lm.push_back(feature_index);
+            t.relo_xy.push_back(e.match_points[retrive].x());
+            t.relo_xy.push_back(e.match_points[retrive].y());
+            ++retrive;
+        }
+    }
+}
+
+// MarginalizationFactor(last_marginalization_info) on last_marginalization_parameter_blocks (:703-709) -> the prior fields of a
+// vg_ba_problem.  The blocks are identified by their para_* ADDRESSES, as in the reference; the C-ABI wants (kind, frame index).  The
+// columns of linearized_jacobians are addressed through keep_block_idx - m (marginalization_factor.cpp:343-378): they are gathered
+// into the block order of last_marginalization_parameter_blocks.  `b` owns what pb then points to.
+struct PriorIn {
+    std::vector<int> kind, index;
+    std::vector<double> J0, r0, x0;
+};
+template <class E> void prior_to_problem(E& e, PriorIn& b, vg_ba_problem& pb) {
+    if (!e.last_marginalization_info) return;
+    auto* mi = e.last_marginalization_info;
+    const int n = mi->n, nb = (int)mi->keep_block_size.size();
+    const int ncols = (int)mi->linearized_jacobians.cols();
+    b.J0.assign((size_t)n * n, 0.0);
+    int col = 0;
+    for (int k = 0; k < nb; ++k) {
+        int kind, index;
+        if (!block_of(e, e.last_marginalization_parameter_blocks[k], kind, index)) throw std::runtime_error("prior block address outside the para_* arrays");
+        b.kind.push_back(kind); b.index.push_back(index);
+        const int gs = mi->keep_block_size[k], ls = local_size(gs), src = mi->keep_block_idx[k] - mi->m;
+        b.x0.insert(b.x0.end(), mi->keep_block_data[k], mi->keep_block_data[k] + gs);
+        if (src < 0 || src + ls > ncols || col + ls > n) throw std::runtime_error("prior block outside linearized_jacobians");
+        for (int r = 0; r < n; ++r)
+            for (int c = 0; c < ls; ++c) b.J0[(size_t)r * n + col + c] = mi->linearized_jacobians(r, src + c);
+        col += ls;
+    }
+    if (col != n) throw std::runtime_error("prior: kept blocks do not cover the n columns");
+    b.r0.resize(n);
+    for (int r = 0; r < n; ++r) b.r0[r] = mi->linearized_residuals(r);
+    pb.prior_n = n; pb.prior_nblocks = nb;
+    pb.prior_block_kind = b.kind.data(); pb.prior_block_index = b.index.data();
+    pb.prior_J0 = b.J0.data(); pb.prior_r0 = b.r0.data(); pb.prior_x0 = b.x0.data();
+}
+
+// Download buffers of a vg_ba_prior for a window of K frames (x0 holds 9 doubles per block at most: speed-bias); `pr` is the view
+struct PriorOut {
+    std::vector<int> kind, index;
+    std::vector<double> J0, r0, x0;
+    vg_ba_prior pr;
+    explicit PriorOut(int K) : kind(K + 8), index(K + 8), J0((size_t)(6 * K + 32) * (6 * K + 32)), r0(6 * K + 32), x0(9 * (K + 8)) {
+        std::memset(&pr, 0, sizeof(pr));
+        pr.cap = 6 * K + 32; pr.cap_blocks = K + 8; pr.block_kind = kind.data(); pr.block_index = index.data();
+        pr.J0 = J0.data(); pr.r0 = r0.data(); pr.x0 = x0.data();
+    }
+    PriorOut(const PriorOut&) = delete;
+    PriorOut& operator=(const PriorOut&) = delete;
+};
+
+// last_marginalization_info = marginalization_info (estimator.cpp:926-929 / :992-996) from a vg_ba_prior: a new MarginalizationInfo
+// (n, m, Jacobian, residuals, keep_block_size / idx / data; every keep_block_data[b] is a new double[]) and the blocks' addresses in
+// the SLID window (addr_shift, :913-924 / :969-990: the device already re-labelled them).  The old MarginalizationInfo is deleted.
+template <class E> void install_prior(E& e, const vg_ba_prior& pr, int m) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(e.last_marginalization_info)>::type>::type Info;
+    Info* mi = new Info();
+    mi->n = pr.n; mi->m = m;
+    mi->linearized_jacobians.resize(pr.n, pr.n);
+    mi->linearized_residuals.resize(pr.n);
+    for (int r = 0; r < pr.n; ++r) {
+        mi->linearized_residuals(r) = pr.r0[r];
+        for (int c = 0; c < pr.n; ++c) mi->linearized_jacobians(r, c) = pr.J0[(size_t)r * pr.n + c];
+    }
+    std::vector<double*> blocks;
+    int off = 0, x0o = 0;
+    for (int b = 0; b < pr.nblocks; ++b) {
+        const int gs = block_global_size(pr.block_kind[b]);
+        mi->keep_block_size.push_back(gs);
+        mi->keep_block_idx.push_back(m + off);
+        double* d = new double[gs];
+        std::memcpy(d, pr.x0 + x0o, sizeof(double) * gs);
+        mi->keep_block_data.push_back(d);
+        blocks.push_back(block_addr(e, pr.block_kind[b], pr.block_index[b]));
+        off += local_size(gs); x0o += gs;
+    }
+    delete e.last_marginalization_info;
+    e.last_marginalization_info = mi;
+    e.last_marginalization_parameter_blocks = blocks;
+}
+
+// ================================================================================================================== front end
+
+// reduceVector (feature_tracker.cpp:13-29) for any element type
+template <class V> void reduce_vector(V& v, const std::vector<uint8_t>& status) {
+    int j = 0;
+    for (int i = 0; i < int(v.size()); i++)
+        if (status[i]) v[j++] = v[i];
+    v.resize(j);
+}
+
+template <class T> struct OrderCtx {
+    typedef typename std::decay<decltype(std::declval<T&>().forw_pts)>::type::value_type Point2f;
+    typedef std::vector<std::pair<int, std::pair<Point2f, int>>> SortedList;
+    T* t;
+    int n_in;
+    SortedList sorted;               // setMask's cnt_pts_id (:43), the third field holding the list index instead of the id
+};
+
+// The reference's sort call (:47-51): same element type, same comparator, same std::sort.  std::sort by track_cnt is not stable: the
+// order among equal counts is what the platform's std::sort makes of the sequence; the permutation depends on the outcomes of the
+// comparisons only, and those look at the counts (tests/test_fe_dropin.py holds it against the reference's node).
+template <class Point2f> void sort_by_count(std::vector<std::pair<int, std::pair<Point2f, int>>>& cnt_pts_id) {
+    using std::pair;
+    std::sort(cnt_pts_id.begin(), cnt_pts_id.end(),
+              [](const pair<int, pair<Point2f, int>>& a, const pair<int, pair<Point2f, int>>& b) { return a.first > b.first; });
+}
+
+// vg_fe_order_fn with user = OrderCtx<T>*: the order of setMask's walk
+template <class T> int order_callback(void* user, const vg_fe_frame_out* after, int* order) {
+    typedef typename OrderCtx<T>::Point2f Point2f;
+    OrderCtx<T>* c = static_cast<OrderCtx<T>*>(user);
+    // The survivors with their counts (:115-128, :193-198: track_cnt++ after the tracking), formed ON THE SIDE: the tracker's own vectors
+    // are only touched once the library call has returned VG_OK, so a frame that fails later (detection overflow, a HIP error) leaves
+    // the tracker as it was
+    c->sorted.clear();
+    for (int i = 0, k = 0, idx = 0; i < c->n_in; i++) {
+        if (!after->status_lk[i]) continue;
+        const bool keep = !after->ransac_ran || after->status_f[k];
+        k++;
+        if (keep) c->sorted.push_back(std::make_pair(c->t->track_cnt[i] + 1, std::make_pair(Point2f(after->forw_xy[2 * i], after->forw_xy[2 * i + 1]), idx++)));
+    }
+    if ((int)c->sorted.size() != after->n2) return 1;
+    sort_by_count(c->sorted);
+    for (int q = 0; q < after->n2; q++) order[q] = c->sorted[q].second.second;
+    return 0;
+}
+
+// What readImage does with the statuses of a frame (:115-128, :193-198): forw_pts as the tracking left them, reduceVector by
+// `status && inBorder`, track_cnt++, reduceVector by findFundamentalMat's mask
+template <class T> void apply_statuses(T& t, const vg_fe_frame_out& a, int n_in) {
+    typedef typename OrderCtx<T>::Point2f Point2f;
+    t.forw_pts.resize(n_in);
+    for (int i = 0; i < n_in; i++) t.forw_pts[i] = Point2f(a.forw_xy[2 * i], a.forw_xy[2 * i + 1]);
+    if (n_in > 0) {
+        const std::vector<uint8_t> status(a.status_lk, a.status_lk + n_in);
+        reduce_vector(t.prev_pts, status);
+        reduce_vector(t.cur_pts, status);
+        reduce_vector(t.forw_pts, status);
+        reduce_vector(t.ids, status);
+        reduce_vector(t.cur_un_pts, status);
+        reduce_vector(t.track_cnt, status);
+    }
+    for (auto& n : t.track_cnt) n++;
+    if (a.ransac_ran) {
+        const std::vector<uint8_t> status(a.status_f, a.status_f + a.n1);
+        reduce_vector(t.prev_pts, status);
+        reduce_vector(t.cur_pts, status);
+        reduce_vector(t.forw_pts, status);
+        reduce_vector(t.cur_un_pts, status);
+        reduce_vector(t.ids, status);
+        reduce_vector(t.track_cnt, status);
+    }
+}
+
+// A published frame after apply_statuses: setMask's outcome (:53-68), the kept points in the order of the walk (`sorted`: the list the
+// order callback made), then the new corners through addPoints() (:144-156)
+template <class T> void apply_published(T& t, const vg_fe_frame_out& out, const typename OrderCtx<T>::SortedList& sorted) {
+    typedef typename OrderCtx<T>::Point2f Point2f;
+    std::vector<Point2f> kept_pts;
+    std::vector<int> kept_ids, kept_cnt;
+    for (int k = 0; k < out.n_kept; k++) {
+        const auto& it = sorted[out.kept[k]];
+        kept_pts.push_back(it.second.first);
+        kept_ids.push_back(t.ids[it.second.second]);
+        kept_cnt.push_back(it.first);
+    }
+    t.forw_pts = kept_pts; t.ids = kept_ids; t.track_cnt = kept_cnt;
+    t.n_pts.clear();
+    for (int k = 0; k < out.n_new; k++) t.n_pts.push_back(Point2f(out.new_xy[2 * k], out.new_xy[2 * k + 1]));
+    t.addPoints();
+}
+
+// undistortedPoints() (:262-304) given the lifted (x / z, y / z) pairs of cur_pts: cur_un_pts, the map, the velocities
+template <class T> void lifted_points(T& t, const float* un) {
+    typedef typename OrderCtx<T>::Point2f Point2f;
+    t.cur_un_pts.clear();
+    t.cur_un_pts_map.clear();
+    const int n = (int)t.cur_pts.size();
+    for (int i = 0; i < n; i++) {
+        t.cur_un_pts.push_back(Point2f(un[2 * i], un[2 * i + 1]));
+        t.cur_un_pts_map.insert(std::make_pair(t.ids[i], Point2f(un[2 * i], un[2 * i + 1])));
+    }
+    if (!t.prev_un_pts_map.empty()) {
+        double dt = t.cur_time - t.prev_time;
+        t.pts_velocity.clear();
+        for (unsigned int i = 0; i < t.cur_un_pts.size(); i++) {
+            if (t.ids[i] != -1) {
+                auto it = t.prev_un_pts_map.find(t.ids[i]);
+                if (it != t.prev_un_pts_map.end()) {
+                    double v_x = (t.cur_un_pts[i].x - it->second.x) / dt;
+                    double v_y = (t.cur_un_pts[i].y - it->second.y) / dt;
+                    t.pts_velocity.push_back(Point2f((float)v_x, (float)v_y));
+                } else
+                    t.pts_velocity.push_back(Point2f(0, 0));
+            } else
+                t.pts_velocity.push_back(Point2f(0, 0));
+        }
+    } else {
+        for (unsigned int i = 0; i < t.cur_pts.size(); i++) t.pts_velocity.push_back(Point2f(0, 0));      // (as the reference: not cleared)
+    }
+    t.prev_un_pts_map = t.cur_un_pts_map;
+}
+
+// The arguments of one frame that every caller sets alike: the image, cur_pts and the configuration values (the reference's globals
+// PUB_THIS_FRAME, EQUALIZE, MAX_CNT, MIN_DIST, F_THRESHOLD, FOCAL_LENGTH, handed in by the caller whose header declares them).  intr,
+// base_mask and the order callback stay with the caller.
+template <class T, class Image>
+void fill_frame_in(T& t, const Image& img, bool publish, int equalize, int max_cnt, int min_dist, double f_threshold, double focal_length, vg_fe_frame_in& in) {
+    std::memset(&in, 0, sizeof(in));
+    in.struct_size = (int)sizeof(in);
+    in.img = img.data; in.stride = (int)img.step; in.equalize = equalize; in.publish = publish ? 1 : 0;
+    in.cur_xy = t.cur_pts.empty() ? nullptr : &t.cur_pts[0].x; in.n = (int)t.cur_pts.size();
+    in.max_cnt = max_cnt; in.min_dist = min_dist; in.quality = 0.01; in.f_threshold = f_threshold; in.focal_length = focal_length;
+}
+
+// setMask() (:36-69) up to the library call: cnt_pts_id sorted the reference's way (:43-51), packed as vg_fe_set_mask takes it (the
+// device's own sort by count is stable, i.e. the identity on an already sorted list)
+template <class T>
+void sorted_for_setmask(T& t, int capacity, std::vector<float>& xy, std::vector<int>& cnt, typename OrderCtx<T>::SortedList& cnt_pts_id) {
+    const int n = (int)t.forw_pts.size();
+    if (n > capacity) throw std::runtime_error("FeatureTracker::setMask: more points than the configured capacity");
+    for (int i = 0; i < n; i++) cnt_pts_id.push_back(std::make_pair(t.track_cnt[i], std::make_pair(t.forw_pts[i], t.ids[i])));
+    sort_by_count(cnt_pts_id);
+    xy.assign((size_t)capacity * 2, 0.f);
+    cnt.assign((size_t)capacity, 0);
+    for (int i = 0; i < n; ++i) { xy[2 * i] = cnt_pts_id[i].second.first.x; xy[2 * i + 1] = cnt_pts_id[i].second.first.y; cnt[i] = cnt_pts_id[i].first; }
+}
+// ... and after it (:53-68): the points the walk kept, in its order
+template <class T> void take_setmask_result(T& t, const typename OrderCtx<T>::SortedList& cnt_pts_id, const int* kept, int nk) {
+    t.forw_pts.clear(); t.ids.clear(); t.track_cnt.clear();
+    for (int k = 0; k < nk; ++k) {
+        const auto& it = cnt_pts_id[kept[k]];
+        t.forw_pts.push_back(it.second.first); t.ids.push_back(it.second.second); t.track_cnt.push_back(it.first);
+    }
+}
+
+}  // namespace vg_pack
