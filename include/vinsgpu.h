@@ -353,8 +353,8 @@ int vg_ba_reserve(vg_handle* h, int max_landmarks, int max_factors, int max_obs,
  * and the prior never leave HBM; per frame the host sends the new frame's observations (id + 7 doubles each) and EITHER its
  * state guess (what processIMU propagated) and the pre-integration of the new interval (vg_ba_seq_step_async) OR the raw IMU
  * samples since the frame before (vg_ba_seq_step_imu_async: processIMU runs on the device too, see below), and reads back the
- * states.  No per-frame packing, no re-upload of the window.  Relocalisation factors and the large-window path are not offered
- * in a sequence.                                                                                                            */
+ * states.  No per-frame packing, no re-upload of the window.  Relocalisation frames are taken by a sequence begun after
+ * vg_ba_seq_relo_reserve (below: vg_ba_seq_set_relo); the large-window path is not offered in a sequence.                    */
 typedef struct {
     int n_features;              /* f_manager.feature.size(), list order                                                     */
     const int* feature_id;       /* FeaturePerId::feature_id                                                                 */
@@ -423,7 +423,7 @@ int vg_ba_seq_get_tracks(vg_handle* h, int window, int cap, int* n_features, int
  *           vg_ba_optimize; n = 0: none; after a step that chose VG_MARGIN_SECOND_NEW the record of interval K-3 is still the
  *           un-merged one -- the merged record reaches the device with the next frame's imu_merged; a sequence in IMU mode holds the merged one already) -- together with vg_ba_seq_get_tracks this is everything the reference keeps in
  *           Ps / Rs / Vs / Bas / Bgs, pre_integrations[], f_manager.feature and last_marginalization_info: a host Estimator can
- *           take the window back (a relocalisation frame, which a sequence does not offer; a checkpoint; a failure re-start);
+ *           take the window back (a checkpoint; a failure re-start; a relocalisation frame needs no hand-back: vg_ba_seq_set_relo);
  *   import  replaces what slot `window` holds (same K and estimate_* options as the sequence; prior from the host or none) while
  *           the other windows stay where they are.  Any output pointer of export may be NULL. */
 int vg_ba_seq_export(vg_handle* h, int window, double* pose, double* speedbias, double* ex_pose, double* td, vg_imu_preint* imu,
@@ -490,6 +490,61 @@ int vg_ba_seq_imu_set(vg_handle* h, int window, const double* seed9);
  * pointer may be NULL).  VG_ERR_BAD_ARG without a sequence in IMU mode, or when the last step was not timed. */
 int vg_ba_seq_imu_timing(vg_handle* h, int on);
 int vg_ba_seq_imu_times(vg_handle* h, float* imu_kernel_ms, float* merge_kernel_ms);
+
+/* ---- Relocalisation frames of a resident sequence (added within ABI 12, nothing existing changed) ---------------------------------
+ * When the pose graph reports a loop, Estimator::setReloFrame (estimator.cpp:1128-1147) leaves match_points, relo_Pose and
+ * relo_frame_local_index for the NEXT optimization(), which adds one pose block and one ProjectionFactor per matched landmark
+ * (:769-801) and whose double2vector() forms the relative pose and the drift correction (:598-612).  A sequence does the same
+ * without handing its window back: the matches go up with the next step's staging, the factors are selected from the resident
+ * track table on the device (the reference's cursor walk, reproduced for track lists that are not ascending too), the loop pose
+ * is the K+1-th pose block of the window.
+ *   vg_ba_seq_relo_reserve  before vg_ba_seq_begin, like vg_ba_reserve: with 1 <= max_match <= 1024 the NEXT vg_ba_seq_begin lays out
+ *                           the loop-pose block and adds max_match to its factor and observation-row capacities; the reservation
+ *                           is consumed by that begin.  0 cancels it.  Without a reservation vg_ba_seq_begin builds the layout it
+ *                           always built.  Between relocalisation frames the block is idle: it holds the unit pose 0 0 0 0 0 0 1
+ *                           and no factor.  vg_ba_seq_begin refuses (VG_ERR_UNSUPPORTED) a K whose wider camera part leaves the
+ *                           single-workgroup pipeline, and keeps refusing windows that arrive with relo_n != 0.
+ *   vg_ba_seq_set_relo      between two frames: arms window `window` for the NEXT step only, whichever of vg_ba_seq_step_async,
+ *                           vg_ba_seq_step_imu_async and vg_vio_step_async that is (relocalization_info is consumed by one
+ *                           optimization()).  r == NULL disarms; arming twice keeps the second; vg_ba_seq_import of that window,
+ *                           vg_ba_seq_end and vg_ba_seq_begin disarm.  VG_ERR_BAD_ARG before anything is touched (the sequence
+ *                           stays usable): a sequence begun without a reservation, a wrong struct_size, frame outside 0 .. K-2,
+ *                           n_match outside 1 .. max_match, ids that are not strictly ascending, a number that is not finite.
+ *                           The call itself neither uploads nor synchronises; a step with no armed window uploads nothing extra.
+ *                           An armed window whose factors or rows exceed the capacities reports VG_ERR_UNSUPPORTED in
+ *                           info[VG_SEQ_STATUS] like every other capacity: the step is void, the relocalisation is consumed.
+ *   vg_ba_seq_get_relo      after the states of a step are down (vg_ba_batch_download_state; vg_ba_state::relo_pose returns the
+ *                           loop pose there too): the relocalisation outcome of that step for one window.  n_factors == 0 is
+ *                           legal (no matched landmark is in the problem): the input pose is carried through the gauge transform,
+ *                           which is what the reference computes.  The by-products are formed on the host, in double, from the
+ *                           downloaded states with the reference's expressions (Utility::R2ypr / ypr2R / normalizeAngle, degrees).
+ * info[VG_SEQ_N_FACTORS] counts the relocalisation factors too. */
+typedef struct vg_ba_relo_frame {
+    int struct_size;             /* sizeof(vg_ba_relo_frame)                                                                 */
+    int frame;                   /* relo_frame_local_index, 0 .. K-2: index into the window as it stands between two frames
+                                  * (what setReloFrame's loop over Headers[0 .. WINDOW_SIZE) finds; the sequence keeps no stamps) */
+    const double* pose;          /* 7: the initial relo_Pose; NULL: the resident pose of window frame `frame` at the start of the step */
+    int n_match;                 /* 1 .. max_match                                                                            */
+    const int* match_id;         /* strictly ascending feature ids (match_points[k].z())                                      */
+    const double* match_xy;      /* n_match x 2 normalised points in the loop frame                                           */
+    double prev_relo_t[3];
+    double prev_relo_r[9];       /* row-major                                                                                 */
+} vg_ba_relo_frame;
+typedef struct vg_ba_relo_result {
+    int struct_size;             /* sizeof(vg_ba_relo_result), set by the caller                                              */
+    int armed;                   /* 0 / 1: the window was armed for that step (0: everything below but pose is zero)          */
+    int n_factors;               /* relocalisation factors in the problem                                                     */
+    int frame;
+    double pose[7];              /* the gauge-fixed loop pose (relo_r as a quaternion x y z w, relo_t)                         */
+    double relo_relative_t[3];
+    double relo_relative_q[4];   /* x y z w                                                                                   */
+    double relo_relative_yaw;
+    double drift_correct_r[9];   /* row-major                                                                                 */
+    double drift_correct_t[3];
+} vg_ba_relo_result;
+int vg_ba_seq_relo_reserve(vg_handle* h, int max_match);
+int vg_ba_seq_set_relo(vg_handle* h, int window, const vg_ba_relo_frame* r);
+int vg_ba_seq_get_relo(vg_handle* h, int window, vg_ba_relo_result* out);
 
 /* Form of the prior factor the marginalization hands back (marginalization_factor.cpp:285-296 builds J0 = S^1/2 V^T,
  * r0 = S^-1/2 V^T b' from the eigen-decomposition A' = V S V^T of the kept system).  Everything downstream uses the factor
@@ -849,7 +904,9 @@ int vg_fe_tracks_set(vg_handle* h, int cam, const vg_fe_tracks_state* state);
  * vg_vio_end         ends the bridge; lists and sequence go on.
  * Mixing: vg_fe_tracks_step and vg_ba_seq_step_imu_async stay legal between two vg_vio_step_async calls (the same state).
  * vg_ba_seq_end, vg_ba_seq_begin, vg_ba_seq_imu_begin (it replaces the staging and may change max_samples), vg_fe_configure and
- * vg_fe_tracks_begin end the bridge: a later vg_vio_step_async is refused until vg_vio_begin is called again. */
+ * vg_fe_tracks_begin end the bridge: a later vg_vio_step_async is refused until vg_vio_begin is called again.
+ * Relocalisation: a publishing vg_vio_step_async honours a window armed with vg_ba_seq_set_relo (it shares the step: the request
+ * travels in the sample block's header); a frame that does not publish leaves the request armed for the next one that does. */
 typedef struct vg_vio_in {
     int struct_size;             /* sizeof(vg_vio_in)                                                                          */
     int n_samples;               /* IMU rows since the previous PUBLISHED frame, as estimator_node's getMeasurements pairs them */

@@ -80,6 +80,17 @@ class FrameImu(C.Structure):          # vg_ba_frame_imu
     _fields_ = [("n_samples", C.c_int), ("samples", _pd), ("n_obs", C.c_int), ("feature_id", _pi), ("obs", _pd)]
 
 
+class ReloFrame(C.Structure):         # vg_ba_relo_frame
+    _fields_ = [("struct_size", C.c_int), ("frame", C.c_int), ("pose", _pd), ("n_match", C.c_int), ("match_id", _pi), ("match_xy", _pd),
+                ("prev_relo_t", C.c_double * 3), ("prev_relo_r", C.c_double * 9)]
+
+
+class ReloResult(C.Structure):        # vg_ba_relo_result
+    _fields_ = [("struct_size", C.c_int), ("armed", C.c_int), ("n_factors", C.c_int), ("frame", C.c_int), ("pose", C.c_double * 7),
+                ("relo_relative_t", C.c_double * 3), ("relo_relative_q", C.c_double * 4), ("relo_relative_yaw", C.c_double),
+                ("drift_correct_r", C.c_double * 9), ("drift_correct_t", C.c_double * 3)]
+
+
 SEQ_INFO = ("flag", "n_features", "n_tracked", "n_parallax", "n_landmarks", "n_factors", "status", "n_after")
 
 
@@ -289,6 +300,10 @@ class Handle:
             L.vg_vio_begin.argtypes = [C.c_void_p, C.c_int]
             L.vg_vio_get_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, _pi, _pi, _pd]
             L.vg_vio_end.argtypes = [C.c_void_p]
+        if hasattr(L, "vg_ba_seq_set_relo"):              # (added within ABI 12)
+            L.vg_ba_seq_relo_reserve.argtypes = [C.c_void_p, C.c_int]
+            L.vg_ba_seq_set_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloFrame)]
+            L.vg_ba_seq_get_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloResult)]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -547,10 +562,14 @@ class Handle:
             ts[w].depth, ts[w].obs = _dp(a['depth']), _dp(a['obs'])
         tp = (C.POINTER(Tracks) * n)(*[C.pointer(ts[w]) for w in range(n)])
         cfg = SeqConfig(int(max_features), int(max_new_obs), int(max_landmarks), int(max_factors), float(init_depth), float(min_parallax))
+        self._seq_relo, reserved = False, getattr(self, "_relo_reserved", 0) > 0
+        self._relo_reserved = 0                           # (consumed by this begin, whatever comes of it)
         self._chk(self.lib.vg_ba_seq_begin(self.h, n, C.byref(cfg), arr, tp), "vg_ba_seq_begin")
         self._seq_n = n
+        self._seq_relo = reserved
         for p in self._packed:                            # size of the inverse-depth slab a state download fills
             p.L = (int(max_landmarks or max_features) + 15) // 16 * 16
+            p.has_relo = reserved                         # (the loop-pose block: seq_states returns relo_pose)
 
     @staticmethod
     def seq_pack_frames(frames):
@@ -584,7 +603,7 @@ class Handle:
         rc = self.ba_download_state_raw()
         if rc != VG_OK and not (allow_numeric_failure and rc == -4):
             self._chk(rc, "vg_ba_batch_download_state")
-        return [o.state_dict(False) for o in outs], [summary_dict(sm[i]) for i in range(len(outs))]
+        return [o.state_dict(getattr(self, "_seq_relo", False)) for o in outs], [summary_dict(sm[i]) for i in range(len(outs))]
 
     def seq_priors(self):
         """parity tap: the priors the last step's marginalization produced (None where the old one stays)."""
@@ -690,6 +709,41 @@ class Handle:
         a, b = C.c_float(), C.c_float()
         self._chk(self.lib.vg_ba_seq_imu_times(self.h, C.byref(a), C.byref(b)), "vg_ba_seq_imu_times")
         return float(a.value), float(b.value)
+
+    # ---- relocalisation frames of a resident sequence (include/vinsgpu.h vg_ba_seq_relo_reserve / set_relo / get_relo)
+    def seq_relo_reserve(self, max_match):
+        """Before seq_begin: the next sequence gets the loop-pose block and room for max_match (1 .. 1024) relocalisation factors;
+        0 cancels."""
+        self._chk(self.lib.vg_ba_seq_relo_reserve(self.h, int(max_match)), "vg_ba_seq_relo_reserve")
+        self._relo_reserved = int(max_match)
+
+    def seq_set_relo(self, w, relo, struct_size=None):
+        """Between two frames: arms window w for the next step.  relo = dict(frame, match_id (n,) ascending, match_xy (n, 2), optional
+        pose (7,) [None: the resident pose of that frame], optional prev_t (3,), prev_r (3, 3)); None disarms."""
+        if relo is None:
+            self._chk(self.lib.vg_ba_seq_set_relo(self.h, int(w), None), "vg_ba_seq_set_relo")
+            return
+        ids = np.ascontiguousarray(relo['match_id'], dtype=np.int32)
+        xy = np.ascontiguousarray(relo['match_xy'], dtype=np.float64).reshape(-1, 2)
+        pose = None if relo.get('pose') is None else np.ascontiguousarray(relo['pose'], dtype=np.float64).reshape(7)
+        r = ReloFrame()
+        r.struct_size = C.sizeof(ReloFrame) if struct_size is None else int(struct_size)
+        r.frame, r.n_match = int(relo['frame']), int(relo.get('n_match', len(ids)))
+        r.pose = _dp(pose) if pose is not None else None
+        r.match_id, r.match_xy = _ip(ids), _dp(xy)
+        r.prev_relo_t[:] = [float(x) for x in np.asarray(relo.get('prev_t', np.zeros(3)), float).ravel()]
+        r.prev_relo_r[:] = [float(x) for x in np.asarray(relo.get('prev_r', np.eye(3)), float).ravel()]
+        self._chk(self.lib.vg_ba_seq_set_relo(self.h, int(w), C.byref(r)), "vg_ba_seq_set_relo")
+
+    def seq_get_relo(self, w):
+        """After seq_states of a step: dict(armed, n_factors, frame, pose (7,), relative_t, relative_q (x y z w), relative_yaw [deg],
+        drift_r (3, 3), drift_t) of window w in that step."""
+        o = ReloResult()
+        o.struct_size = C.sizeof(ReloResult)
+        self._chk(self.lib.vg_ba_seq_get_relo(self.h, int(w), C.byref(o)), "vg_ba_seq_get_relo")
+        return dict(armed=int(o.armed), n_factors=int(o.n_factors), frame=int(o.frame), pose=np.array(o.pose[:]),
+                    relative_t=np.array(o.relo_relative_t[:]), relative_q=np.array(o.relo_relative_q[:]), relative_yaw=float(o.relo_relative_yaw),
+                    drift_r=np.array(o.drift_correct_r[:]).reshape(3, 3), drift_t=np.array(o.drift_correct_t[:]))
 
     def seq_end(self):
         self._chk(self.lib.vg_ba_seq_end(self.h), "vg_ba_seq_end")

@@ -179,7 +179,7 @@ static int build_layout(vg_handle* h, int nwin, const vg_ba_problem* const* in, 
     const vg_ba_problem* p0 = in[0];
     L.nwin = nwin;
     L.K = p0->K;
-    bool relo = false;
+    bool relo = h->ba.res_relo;                  // (a sequence that reserved the loop-pose block: vg_ba_seq_relo_reserve)
     int Lmax = 1, Fmax = 1, Omax = 1, Nmax = 0, NBmax = 0;
     for (int w = 0; w < nwin; ++w) {
         const vg_ba_problem* p = in[w];
@@ -1334,6 +1334,10 @@ static void seq_free(BaSeq& Q) {
     (void)hipFree(D.sp); (void)hipFree(D.in_i); (void)hipFree(D.in_d); (void)hipFree(D.info); (void)hipFree(D.imu_st);
     D.sp = nullptr; D.in_i = nullptr; D.in_d = nullptr; D.info = nullptr; D.imu_st = nullptr;
     D.imu_mode = 0; D.MS = 0;
+    (void)hipFree(D.relo_i); (void)hipFree(D.relo_d); (void)hipFree(D.relo_out);
+    D.relo_i = nullptr; D.relo_d = nullptr; D.relo_out = nullptr; D.MM = 0;
+    Q.relo.clear(); Q.relo_last.clear(); Q.relo_staged = false;      // (relo_reserve stays: it shapes the NEXT begin)
+    Q.h_relo_i.release(); Q.h_relo_d.release();
     Q.h_in_i.release(); Q.h_in_d.release(); Q.h_info.release();
     (void)hipFree(Q.vio_d); Q.vio_d = nullptr;
     Q.h_vio.release();
@@ -1381,6 +1385,14 @@ static int seq_check_tracks(vg_handle* h, const vg_ba_tracks* t, int FT, int K) 
     return VG_OK;
 }
 
+extern "C" int ba_seq_relo_max_match();
+extern "C" int vg_ba_seq_relo_reserve(vg_handle* h, int max_match) {
+    if (!h) return VG_ERR_BAD_ARG;
+    if (max_match < 0 || max_match > ba_seq_relo_max_match()) { h->err = "vg_ba_seq_relo_reserve: max_match outside 0 .. 1024"; return VG_ERR_BAD_ARG; }
+    h->ba.seq.relo_reserve = max_match;
+    return VG_OK;
+}
+
 extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* cfg, const vg_ba_problem* const* windows,
                                const vg_ba_tracks* const* tracks) {
     VG_RANGE("vg_ba_seq_begin");
@@ -1409,14 +1421,18 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     seq_free(Q);
+    const int MM = Q.relo_reserve;                               // vg_ba_seq_relo_reserve: consumed by this begin
+    Q.relo_reserve = 0;
     // the batch layout, the states, the pre-integrations and the first prior go the ordinary way (the windows' own landmark
     // tables are packed too and overwritten by the first step)
     const int keep_res[4] = {B.res_L, B.res_F, B.res_O, B.res_N};     // (the sequence's capacities hold for this layout only)
-    B.res_L = std::max(B.res_L, Lres); B.res_F = std::max(B.res_F, Fres); B.res_O = std::max(B.res_O, Fres + Lres);
+    B.res_L = std::max(B.res_L, Lres); B.res_F = std::max(B.res_F, Fres + MM); B.res_O = std::max(B.res_O, Fres + Lres + MM);
     B.res_N = std::max(B.res_N, 6 * K + 9 * 2 + 6 + 1);
+    B.res_relo = MM > 0;                                         // the loop-pose block: Kp = K + 1, idle (unit pose, no factor) until a window is armed
     std::vector<int> flags(nwin, VG_MARGIN_OLD);
     int rc = vg_ba_batch_upload(h, nwin, windows, flags.data());
     B.res_L = keep_res[0]; B.res_F = keep_res[1]; B.res_O = keep_res[2]; B.res_N = keep_res[3];
+    B.res_relo = false;
     if (rc) return rc;
     if (B.L.big) { h->err = "vg_ba_seq_begin: window too wide for the single-workgroup pipeline"; B.uploaded = false; return VG_ERR_UNSUPPORTED; }
     std::fill(B.nL.begin(), B.nL.end(), std::min(B.L.Lcap, up(Lres, 16)));   // (state downloads: vg_ba_state::inv_depth, if given, takes
@@ -1442,6 +1458,17 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
     HIPCHK(h, hipMalloc((void**)&D.in_d, (size_t)nwin * D.id_stride * sizeof(double)));
     HIPCHK(h, hipMalloc((void**)&D.info, (size_t)nwin * VG_SEQ_INFO_INTS * sizeof(int)));
     HIPCHK(h, hipMemsetAsync(D.info, 0, (size_t)nwin * VG_SEQ_INFO_INTS * sizeof(int), h->stream));
+    D.MM = MM;
+    if (MM) {
+        HIPCHK(h, hipMalloc((void**)&D.relo_i, (size_t)nwin * MM * sizeof(int)));
+        HIPCHK(h, hipMalloc((void**)&D.relo_d, (size_t)nwin * (8 + 2 * MM) * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&D.relo_out, (size_t)nwin * 4 * sizeof(int)));
+        HIPCHK(h, hipMemsetAsync(D.relo_i, 0, (size_t)nwin * MM * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(D.relo_d, 0, (size_t)nwin * (8 + 2 * MM) * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(D.relo_out, 0, (size_t)nwin * 4 * sizeof(int), h->stream));
+        Q.relo.assign(nwin, BaSeq::Relo());
+        Q.relo_last.assign(nwin, BaSeq::Relo());
+    }
     // track tables and prior block tables
     std::vector<int> ti((size_t)nwin * D.fi_stride, 0), sp((size_t)nwin * D.sp_stride, 0);
     std::vector<double> td((size_t)nwin * D.fd_stride, 0.0);
@@ -1463,6 +1490,40 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
 
 struct SeqBridge { const int* tk_hdr; const int* msg_id; const double* msg_obs; int cap, smp_stride; };
 static int seq_launch_step(vg_handle* h, const SeqDev& D, const SeqBridge* bridge = nullptr);
+
+// what the staging header of window w says about relocalisation in this step: n_match (0: idle), frame, 1 when a pose was given
+static void seq_relo_header(const BaSeq& Q, int w, int* i3) {
+    i3[0] = i3[1] = i3[2] = 0;
+    if (w >= (int)Q.relo.size() || !Q.relo[w].armed) return;
+    i3[0] = (int)Q.relo[w].id.size(); i3[1] = Q.relo[w].frame; i3[2] = Q.relo[w].has_pose ? 1 : 0;
+}
+// the matches of the armed windows into the pinned staging (the caller has waited for the previous step's copies); the requests are
+// consumed here: relo_last keeps them for vg_ba_seq_get_relo
+static int seq_relo_stage(vg_handle* h) {
+    BaSeq& Q = h->ba.seq;
+    const int MM = Q.D.MM;
+    Q.relo_staged = false;
+    if (!MM) return VG_OK;
+    bool any = false;
+    for (const BaSeq::Relo& r : Q.relo) any = any || r.armed;
+    if (any) {
+        const size_t ds = 8 + 2 * (size_t)MM;
+        HIPCHK(h, Q.h_relo_i.resize((size_t)Q.nwin * MM));
+        HIPCHK(h, Q.h_relo_d.resize((size_t)Q.nwin * ds));
+        for (int w = 0; w < Q.nwin; ++w) {
+            const BaSeq::Relo& r = Q.relo[w];
+            if (!r.armed) continue;                              // (the kernel reads the rows of armed windows only)
+            memcpy(Q.h_relo_i.data() + (size_t)w * MM, r.id.data(), sizeof(int) * r.id.size());
+            double* d = Q.h_relo_d.data() + (size_t)w * ds;
+            memcpy(d, r.pose, sizeof(r.pose));
+            memcpy(d + 8, r.xy.data(), sizeof(double) * r.xy.size());
+        }
+        Q.relo_staged = true;
+    }
+    Q.relo_last.swap(Q.relo);
+    for (BaSeq::Relo& r : Q.relo) r.armed = false;
+    return VG_OK;
+}
 
 extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* const* frames) {
     VG_RANGE("vg_ba_seq_step_async");
@@ -1502,7 +1563,8 @@ extern "C" int vg_ba_seq_step_async(vg_handle* h, int nwin, const vg_ba_frame* c
         int* i = Q.h_in_i.data() + (size_t)w * D.ii_stride;
         double* d = Q.h_in_d.data() + (size_t)w * D.id_stride;
         i[0] = f->n_obs; i[1] = f->imu_merged ? 1 : 0; i[2] = f->imu_new->valid; i[3] = f->imu_merged ? f->imu_merged->valid : 0;
-        i[4] = i[5] = i[6] = i[7] = 0;
+        i[4] = 0;
+        seq_relo_header(Q, w, i + 5);
         memcpy(i + 8, f->feature_id, sizeof(int) * f->n_obs);
         memcpy(d, f->pose, 7 * 8); memcpy(d + 7, f->speedbias, 9 * 8);
         put_imu(d + 16, *f->imu_new);
@@ -1519,6 +1581,13 @@ static int seq_launch_step(vg_handle* h, const SeqDev& D, const SeqBridge* bridg
     BaBatch& B = h->ba;
     BaSeq& Q = B.seq;
     hipError_t e;
+    const int rrc = seq_relo_stage(h);
+    if (rrc) return rrc;
+    if (Q.relo_staged) {                                         // the matches of the armed windows, in front of the staging that arms them
+        HIPCHK(h, hipMemcpyAsync(D.relo_i, Q.h_relo_i.data(), Q.h_relo_i.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(D.relo_d, Q.h_relo_d.data(), Q.h_relo_d.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        Q.relo_staged = false;
+    }
     if (bridge) {
         HIPCHK(h, hipMemcpyAsync(Q.vio_d, Q.h_vio.data(), Q.h_vio.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipEventRecord(h->ev_join, h->stream));
@@ -1631,7 +1700,8 @@ extern "C" int vg_ba_seq_step_imu_async(vg_handle* h, int nwin, const vg_ba_fram
         int* i = Q.h_in_i.data() + (size_t)w * D.ii_stride;
         double* d = Q.h_in_d.data() + (size_t)w * D.id_stride;
         i[0] = f->n_obs; i[1] = i[2] = i[3] = 0;
-        i[4] = f->n_samples; i[5] = i[6] = i[7] = 0;
+        i[4] = f->n_samples;
+        seq_relo_header(Q, w, i + 5);
         memcpy(i + 8, f->feature_id, sizeof(int) * f->n_obs);
         memcpy(d, f->samples, sizeof(double) * 7 * f->n_samples);
         for (int k = 0; k < f->n_obs; ++k) { memcpy(d + D.rows_off + (size_t)k * 8, f->obs + (size_t)k * 7, 7 * 8); d[D.rows_off + (size_t)k * 8 + 7] = 0.0; }
@@ -1709,7 +1779,9 @@ extern "C" int vg_vio_step_async(vg_handle* h, int n, const vg_vio_in* in, vg_vi
     for (int w = 0; w < n; ++w) {
         double* d = Q.h_vio.data() + (size_t)w * sstride;
         memset(d, 0, sizeof(double) * sstride);
-        memcpy(d, &in[w].n_samples, sizeof(int));
+        int hdr[4] = {in[w].n_samples, 0, 0, 0};                  // (ba_seq_bridge_kernel: n_samples | the relocalisation request)
+        seq_relo_header(Q, w, hdr + 1);
+        memcpy(d, hdr, sizeof(hdr));
         memcpy(d + 8, in[w].samples, sizeof(double) * 7 * in[w].n_samples);
     }
     SeqBridge br;
@@ -1784,6 +1856,121 @@ extern "C" int vg_ba_seq_imu_set(vg_handle* h, int window, const double* seed9) 
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(Q.D.imu_st + (size_t)window * SEQ_IMU_ST, seed9, 9 * sizeof(double), hipMemcpyHostToDevice));
+    return VG_OK;
+}
+
+// ---- relocalisation frames (include/vinsgpu.h vg_ba_seq_set_relo / vg_ba_seq_get_relo) -----------------------------------------
+extern "C" int vg_ba_seq_set_relo(vg_handle* h, int window, const vg_ba_relo_frame* r) {
+    if (!h) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_ba_seq_set_relo: ") + why; return VG_ERR_BAD_ARG; };
+    if (!Q.active || window < 0 || window >= Q.nwin) return refuse("no such window of a running sequence");
+    if (!Q.D.MM) return refuse("the sequence was begun without vg_ba_seq_relo_reserve");
+    if (!r) { Q.relo[window].armed = false; return VG_OK; }
+    if (r->struct_size != (int)sizeof(vg_ba_relo_frame)) return refuse("vg_ba_relo_frame::struct_size is not sizeof(vg_ba_relo_frame)");
+    if (r->frame < 0 || r->frame > Q.D.K - 2) return refuse("frame outside 0 .. K-2");
+    if (r->n_match < 1 || r->n_match > Q.D.MM) return refuse("n_match outside 1 .. max_match of vg_ba_seq_relo_reserve");
+    if (!r->match_id || !r->match_xy) return refuse("match arrays are missing");
+    for (int k = 1; k < r->n_match; ++k) if (r->match_id[k] <= r->match_id[k - 1]) return refuse("match ids must be strictly ascending");
+    bool fin = true;
+    for (int k = 0; k < 2 * r->n_match; ++k) fin = fin && std::isfinite(r->match_xy[k]);
+    for (int k = 0; k < 7 && r->pose; ++k) fin = fin && std::isfinite(r->pose[k]);
+    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(r->prev_relo_t[k]);
+    for (int k = 0; k < 9; ++k) fin = fin && std::isfinite(r->prev_relo_r[k]);
+    if (!fin) return refuse("a number is not finite");
+    BaSeq::Relo& q = Q.relo[window];
+    q.armed = true; q.frame = r->frame; q.has_pose = r->pose != nullptr;
+    if (r->pose) memcpy(q.pose, r->pose, sizeof(q.pose));
+    memcpy(q.prev_t, r->prev_relo_t, sizeof(q.prev_t));
+    memcpy(q.prev_r, r->prev_relo_r, sizeof(q.prev_r));
+    q.id.assign(r->match_id, r->match_id + r->n_match);
+    q.xy.assign(r->match_xy, r->match_xy + 2 * (size_t)r->n_match);
+    return VG_OK;
+}
+
+// Utility::R2ypr / ypr2R / normalizeAngle (vins_estimator/src/utility/utility.h:70-143), degrees, on row-major 3x3 arrays: the
+// expressions of host/estimator.cpp double2vector() for the one-window path, without its matrix library
+static void relo_R2ypr(const double* R, double* ypr) {
+    const double y = atan2(R[3], R[0]);
+    const double p = atan2(-R[6], R[0] * cos(y) + R[3] * sin(y));
+    const double r = atan2(R[2] * sin(y) - R[5] * cos(y), -R[1] * sin(y) + R[4] * cos(y));
+    ypr[0] = y / M_PI * 180.0; ypr[1] = p / M_PI * 180.0; ypr[2] = r / M_PI * 180.0;
+}
+static double relo_normalize_angle(double a) {
+    return a > 0 ? a - 360.0 * std::floor((a + 180.0) / 360.0) : a + 360.0 * std::floor((-a + 180.0) / 360.0);
+}
+static void relo_q2R(const double* q, double* R) {              // Quaterniond(w, x, y, z).normalized().toRotationMatrix(), q = x y z w
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double x = q[0] / n, y = q[1] / n, z = q[2] / n, w = q[3] / n;
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+                 tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+static void relo_R2q(const double* m, double* q) {              // Quaterniond(Matrix3d), x y z w
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = std::sqrt(t + 1.0);
+        q[3] = 0.5 * t; t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[i * 4]) i = 2;
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        t = std::sqrt(m[i * 4] - m[j * 4] - m[k * 4] + 1.0);
+        q[i] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[k * 3 + j] - m[j * 3 + k]) * t;
+        q[j] = (m[j * 3 + i] + m[i * 3 + j]) * t;
+        q[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
+    }
+}
+
+extern "C" int vg_ba_seq_get_relo(vg_handle* h, int window, vg_ba_relo_result* out) {
+    if (!h || !out) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_ba_seq_get_relo: ") + why; return VG_ERR_BAD_ARG; };
+    if (!Q.active || window < 0 || window >= Q.nwin) return refuse("no such window of a running sequence");
+    if (!Q.D.MM) return refuse("the sequence was begun without vg_ba_seq_relo_reserve");
+    if (out->struct_size != (int)sizeof(vg_ba_relo_result)) return refuse("vg_ba_relo_result::struct_size is not sizeof(vg_ba_relo_result)");
+    if (!B.solved_recorded) return refuse("no step has run");
+    const BaLayout& L = B.L;
+    const int K = L.K;
+    // the window's poses as the last step solved them (gauge-fixed by the epilogue, the loop pose with them) and what the build kernel
+    // recorded, on the second stream behind the solve like vg_ba_batch_download_state: the marginalization and the slide go on
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamWaitEvent(h->aux, h->ev_fork, 0));
+    std::vector<double> pose(7 * (size_t)L.Kp);
+    int ro[4];
+    HIPCHK(h, hipMemcpyAsync(pose.data(), B.P.out + (size_t)window * L.ostride + L.oo_pose, pose.size() * sizeof(double), hipMemcpyDeviceToHost, h->aux));
+    HIPCHK(h, hipMemcpyAsync(ro, Q.D.relo_out + (size_t)window * 4, sizeof(ro), hipMemcpyDeviceToHost, h->aux));
+    HIPCHK(h, hipStreamSynchronize(h->aux));
+    memset((char*)out + sizeof(int), 0, sizeof(*out) - sizeof(int));
+    memcpy(out->pose, pose.data() + 7 * K, 7 * sizeof(double));
+    const BaSeq::Relo& q = Q.relo_last[window];
+    out->armed = ro[0] && q.armed ? 1 : 0;
+    if (!out->armed) return VG_OK;
+    out->n_factors = ro[1]; out->frame = ro[2];
+    // double2vector() (estimator.cpp:598-612): Ps / Rs are the downloaded states, relo_r / relo_t the downloaded loop pose
+    double relo_r[9], Rf[9], ypr_prev[3], ypr_relo[3], ypr_f[3];
+    relo_q2R(out->pose + 3, relo_r);
+    relo_q2R(pose.data() + 7 * out->frame + 3, Rf);
+    const double* relo_t = out->pose;
+    const double* Pf = pose.data() + 7 * out->frame;
+    relo_R2ypr(q.prev_r, ypr_prev); relo_R2ypr(relo_r, ypr_relo); relo_R2ypr(Rf, ypr_f);
+    const double yaw = (ypr_prev[0] - ypr_relo[0]) / 180.0 * M_PI;  // ypr2R(Vector3d(drift_correct_yaw, 0, 0)): Rz only, pitch = roll = 0
+    double* dr = out->drift_correct_r;
+    dr[0] = cos(yaw); dr[1] = -sin(yaw); dr[2] = 0; dr[3] = sin(yaw); dr[4] = cos(yaw); dr[5] = 0; dr[6] = 0; dr[7] = 0; dr[8] = 1;
+    double rel[9];
+    for (int r = 0; r < 3; ++r) {
+        out->drift_correct_t[r] = q.prev_t[r] - (dr[3 * r] * relo_t[0] + dr[3 * r + 1] * relo_t[1] + dr[3 * r + 2] * relo_t[2]);
+        out->relo_relative_t[r] = relo_r[r] * (Pf[0] - relo_t[0]) + relo_r[3 + r] * (Pf[1] - relo_t[1]) + relo_r[6 + r] * (Pf[2] - relo_t[2]);
+        for (int c = 0; c < 3; ++c) rel[3 * r + c] = relo_r[r] * Rf[c] + relo_r[3 + r] * Rf[3 + c] + relo_r[6 + r] * Rf[6 + c];
+    }
+    relo_R2q(rel, out->relo_relative_q);
+    out->relo_relative_yaw = relo_normalize_angle(ypr_f[0] - ypr_relo[0]);
     return VG_OK;
 }
 
@@ -1916,6 +2103,7 @@ extern "C" int vg_ba_seq_import(vg_handle* h, int window, const vg_ba_problem* p
     sp[0] = ref.n; sp[1] = ref.nb;
     for (int b = 0; b < ref.nb; ++b) { sp[2 + b] = ref.kind[b]; sp[2 + (K + 4) + b] = ref.idx[b]; }
     HIPCHK(h, hipMemcpy(D.sp + (size_t)window * D.sp_stride, sp.data(), sp.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (window < (int)Q.relo.size()) Q.relo[window].armed = false;   // (a relocalisation frame armed for the window that was replaced)
     // the track table the next step reads
     std::vector<int> ti(D.fi_stride, 0);
     std::vector<double> td(D.fd_stride, 0.0);

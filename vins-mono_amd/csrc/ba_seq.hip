@@ -14,7 +14,10 @@
 //   ba_seq_build_kernel  what optimization() walks f_manager.feature for (estimator.cpp:719-764) and vector2double() (:486-528):
 //                        the landmark list (used_num >= 2 && start_frame < WINDOW_SIZE - 2, list order), inverse depths,
 //                        observation rows, the factor list and its (anchor, target)-sorted slot table, the prior's block table --
-//                        exactly the tables csrc/ba_host.hip pack_window builds on the host for an uploaded window.
+//                        exactly the tables csrc/ba_host.hip pack_window builds on the host for an uploaded window.  In a window
+//                        armed with a relocalisation frame (vg_ba_seq_set_relo) also what optimization() adds for
+//                        relocalization_info (:769-801): the walk over match_points, one factor per matched landmark against
+//                        the loop pose, block K of the window.
 //   [ the solve pipeline and the marginalization kernel of ba_pipeline.hip / ba_marg.hip, unchanged ]
 //   ba_seq_slide_kernel  double2vector's setDepth (feature_manager.cpp:141-159), slideWindow() (estimator.cpp:1005-1126: state and
 //                        pre-integration shift for both flags), FeatureManager::removeBackShiftDepth / removeFront
@@ -43,6 +46,7 @@
 #define SEQ_FT_MAX 1024           // tracks per window (LDS tables of the kernels)
 #define SEQ_NIN_MAX 1024          // observations per frame
 #define SEQ_L_MAX 1024            // landmarks in the problem
+#define SEQ_MM_MAX 1024           // matched points of a relocalisation frame
 #define SEQ_IMU 472               // doubles per pre-integration record (= BA_IMU_STRIDE)
 #define SEQ_IN_POSE 0
 #define SEQ_IN_SB 7
@@ -229,6 +233,9 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
     __shared__ int s_ls[SEQ_L_MAX], s_ln[SEQ_L_MAX], s_feat[SEQ_L_MAX];
     __shared__ int s_fbeg[SEQ_L_MAX + 1], s_off[SEQ_L_MAX + 1];
     __shared__ int s_pair[BA_MAX_K * BA_MAX_K + 1];
+    __shared__ int s_mid[SEQ_MM_MAX];          // relocalisation frame: ids of the matched points,
+    __shared__ int s_lid[SEQ_L_MAX];           // feature id of landmark l,
+    __shared__ int s_rel[SEQ_L_MAX];           // its match (rank among the matched landmarks << 10 | index in the match list) or -1
     __shared__ int s_misc[4];
     const BaLayout& L = *Lp;
     const int w = blockIdx.x, tid = threadIdx.x, K = S.K, WS = K - 1, Kp = L.Kp;
@@ -239,6 +246,12 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
     const int* sp = S.sp + (size_t)w * S.sp_stride;
     const int n = T.hdr[0];
     const int margin = ia[L.io_hdr + H_MARGIN];
+    // ---- relocalisation frame of this step (staging header [5 .. 7]; a sequence without the loop-pose block never looks)
+    const int* ii = S.in_i + (size_t)w * S.ii_stride;
+    int n_match = (Kp > K && S.MM) ? ii[5] : 0;
+    if (n_match < 0 || n_match > S.MM) n_match = 0;                        // (the host refuses such a request)
+    const int relo_frame = n_match ? ii[6] : 0;
+    for (int k = tid; k < n_match; k += SEQ_NT) s_mid[k] = S.relo_i[(size_t)w * S.MM + k];
     __syncthreads();
     // ---- clear the tables a host pack would have zero-filled (the IMU validity flags and the owner task list stay)
     for (int k = tid; k < BA_HDR_INTS; k += SEQ_NT) ia[L.io_hdr + k] = 0;
@@ -258,18 +271,33 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
     for (int f = tid; f < n; f += SEQ_NT) {
         const int l = nL ? s_lm[f] : -1;
         T.lm[f] = l;
-        if (l >= 0) { s_ls[l] = T.start[f]; s_ln[l] = T.nobs[f]; s_feat[l] = f; }
+        if (l >= 0) { s_ls[l] = T.start[f]; s_ln[l] = T.nobs[f]; s_feat[l] = f; s_lid[l] = T.id[f]; }
     }
     __syncthreads();
     if (tid == 0) {
-        int fb = 0, ob = 0;
-        for (int l = 0; l < nL; ++l) { s_fbeg[l] = fb; s_off[l] = ob; fb += s_ln[l] - 1; ob += s_ln[l]; }
+        // the offsets of every landmark's factors and rows; beside them the reference's walk over match_points (estimator.cpp:776-799):
+        // landmarks in list order, only those anchored at or before the loop frame; the cursor moves on while the match id is below the
+        // feature id, an equal id takes the match and moves on.  Past the end means "no more matches" (the reference reads past the end
+        // there; oracle/ref_stubs/ref_driver.cpp defines that memory as ids no feature has).  With ids ascending along the list this
+        // is set membership; along a list that is not ascending, matches are skipped exactly as the reference skips them.
+        int fb = 0, ob = 0, cursor = 0, nrel = 0;
+        for (int l = 0; l < nL; ++l) {
+            int r = -1;
+            if (n_match && s_ls[l] <= relo_frame) {
+                const int id = s_lid[l];
+                while (cursor < n_match && s_mid[cursor] < id) ++cursor;
+                if (cursor < n_match && s_mid[cursor] == id) { r = (nrel << 10) | cursor; ++cursor; ++nrel; }
+            }
+            s_rel[l] = r;
+            s_fbeg[l] = fb; s_off[l] = ob; fb += s_ln[l] - 1 + (r >= 0 ? 1 : 0); ob += s_ln[l];
+        }
         s_fbeg[nL] = fb; s_off[nL] = ob;
-        s_misc[1] = fb; s_misc[2] = ob;
+        s_misc[1] = fb; s_misc[2] = ob; s_misc[3] = nrel;
     }
     __syncthreads();
-    int F = s_misc[1], nobs_tot = s_misc[2];
-    if (F > L.Fcap || nobs_tot > L.Ocap) { nL = 0; F = 0; nobs_tot = 0; status = VG_ERR_UNSUPPORTED; }
+    int F = s_misc[1], nobs_tot = s_misc[2], n_relo = s_misc[3];
+    if (F > L.Fcap || nobs_tot + n_relo > L.Ocap) { nL = 0; F = 0; nobs_tot = 0; n_relo = 0; status = VG_ERR_UNSUPPORTED; }
+    const bool armed = n_match != 0;                                      // (a void step consumes the relocalisation frame too)
     // ---- per landmark: start frame, first factor, inverse depth (vector2double: 1 / estimated_depth, :519-522), observation rows,
     //      factors (first observation -> every later one, :732-763)
     for (int l = tid; l < nL; l += SEQ_NT) {
@@ -282,6 +310,16 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
             ia[L.io_fac_i + q] = s; ia[L.io_fac_j + q] = s + k; ia[L.io_fac_lm + q] = l;
             ia[L.io_fac_oi + q] = o; ia[L.io_fac_oj + q] = o + k;
         }
+        if (s_rel[l] >= 0) {                                              // ProjectionFactor(first observation, matched point) on
+            const int q = fb + no - 1, rank = s_rel[l] >> 10, m = s_rel[l] & 1023;      // (para_Pose[start], relo_Pose, ex, depth): behind
+            const int row = nobs_tot + rank;                              // the landmark's window factors, its row behind the window's rows
+            ia[L.io_fac_i + q] = s; ia[L.io_fac_j + q] = K; ia[L.io_fac_lm + q] = l;
+            ia[L.io_fac_oi + q] = o; ia[L.io_fac_oj + q] = row;
+            const double* xy = S.relo_d + (size_t)w * (8 + 2 * S.MM) + 8 + 2 * m;
+            double* d = di + L.do_obs + (size_t)row * BA_OBS_STRIDE;
+            d[0] = xy[0]; d[1] = xy[1];
+            for (int c = 2; c < BA_OBS_STRIDE; ++c) d[c] = 0.0;
+        }
     }
     if (tid == 0) ia[L.io_lm_fbeg + nL] = F;
     for (int l = nL + tid; l < L.Lcap; l += SEQ_NT) di[L.do_lam + l] = 0.0;
@@ -293,12 +331,20 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
         const int f = s_feat[lo], j = row - s_off[lo];
         di[L.do_obs + (size_t)row * BA_OBS_STRIDE + c] = (c < 7) ? T.obs[((size_t)f * K + j) * 8 + c] : 0.0;
     }
-    for (int e = nobs_tot * 8 + tid; e < L.Ocap * BA_OBS_STRIDE; e += SEQ_NT) di[L.do_obs + e] = 0.0;
+    for (int e = (nobs_tot + n_relo) * 8 + tid; e < L.Ocap * BA_OBS_STRIDE; e += SEQ_NT) di[L.do_obs + e] = 0.0;
+    // ---- the loop pose, block K: relo_Pose as given, or the resident pose of the loop frame as this step found it (the add kernel
+    //      writes slot K - 1 only); the unit pose while the window is not armed, every step, as pack_window writes it
+    if (Kp > K && tid < 7) {
+        double v = tid == 6 ? 1.0 : 0.0;
+        if (armed) v = ii[7] ? S.relo_d[(size_t)w * (8 + 2 * S.MM) + tid] : di[L.do_pose + 7 * relo_frame + tid];
+        di[L.do_pose + 7 * K + tid] = v;
+    }
     // ---- slot table: records sorted by (anchor, target) pair, landmark order inside a pair (pack_window)
+    //      (target K is the loop pose: a landmark has a factor there when the walk gave it a match, not by its length)
     for (int p = tid; p < Kp * Kp; p += SEQ_NT) {
-        const int i = p / Kp, d = p % Kp - i;
+        const int i = p / Kp, j = p % Kp, d = j - i;
         int c = 0;
-        if (d > 0) for (int l = 0; l < nL; ++l) c += (s_ls[l] == i && s_ln[l] > d) ? 1 : 0;
+        if (d > 0) for (int l = 0; l < nL; ++l) c += (s_ls[l] == i && (j < K ? s_ln[l] > d : s_rel[l] >= 0)) ? 1 : 0;
         s_pair[p] = c;
     }
     __syncthreads();
@@ -310,10 +356,11 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
     __syncthreads();
     for (int p = tid; p <= Kp * Kp; p += SEQ_NT) ia[L.io_pair_ptr + p] = s_pair[p];
     for (int p = tid; p < Kp * Kp; p += SEQ_NT) {
-        const int i = p / Kp, d = p % Kp - i;
+        const int i = p / Kp, j = p % Kp, d = j - i;
         if (d <= 0) continue;
         int cursor = s_pair[p];
-        for (int l = 0; l < nL; ++l) if (s_ls[l] == i && s_ln[l] > d) ia[L.io_fac_slot + s_fbeg[l] + d - 1] = cursor++;
+        for (int l = 0; l < nL; ++l)
+            if (s_ls[l] == i && (j < K ? s_ln[l] > d : s_rel[l] >= 0)) ia[L.io_fac_slot + s_fbeg[l] + (j < K ? d : s_ln[l]) - 1] = cursor++;
     }
     if (tid == 0) {
         // wavefront owner tasks (pack_window): every block except the diagonal pose blocks and the blocks among ex / td
@@ -341,6 +388,10 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_build_kernel(const B
         hdr[H_L] = nL; hdr[H_F] = F; hdr[H_NPRIOR] = pn; hdr[H_NBLK] = pnb; hdr[H_MAXIT] = S.max_iters; hdr[H_NCHUNK] = 1;
         hdr[H_MARGIN] = margin; hdr[H_STATUS] = 0; hdr[H_MARGMODE] = S.marg_mode;
         info[VG_SEQ_N_LANDMARKS] = nL; info[VG_SEQ_N_FACTORS] = F; info[VG_SEQ_STATUS] = status;
+        if (S.MM) {
+            int* ro = S.relo_out + (size_t)w * 4;
+            ro[0] = armed ? 1 : 0; ro[1] = n_relo; ro[2] = armed ? relo_frame : 0; ro[3] = 0;
+        }
     }
 }
 
@@ -599,7 +650,7 @@ extern "C" __global__ __launch_bounds__(64) void ba_seq_imu_seed_kernel(const Ba
 // ---------------------------------------------------------------------------------------------------------------------------
 // vg_vio_step_async: the message the front end's commit kernel (fe_tk_commit_kernel, fe_frame.hip) left in HBM for stream w goes to
 // where ba_seq_add_kernel reads the frame of window w, in front of ba_seq_imu_kernel.  One workgroup per stream / window.
-//   ints     ii[0] = n_msg, ii[4] = n_samples, the rest of the header 0; ids behind it (16-byte copies when max_points is a multiple of 4:
+//   ints     ii[0] = n_msg, ii[4] = n_samples, ii[5 .. 7] = the relocalisation request (vg_ba_seq_set_relo; 0 without one), the rest of the header 0; ids behind it (16-byte copies when max_points is a multiple of 4:
 //            the streams' id lists are max_points ints apart)
 //   doubles  the samples from the step's packed upload to the front of the staging; the rows [x y z u v vx vy] -> [x y z u v vx vy 0]
 //            at rows_off: 64 rows at a time through LDS -- 224 16-byte loads of the packed 7-double rows (two scalar loads where the
@@ -618,7 +669,8 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_bridge_kernel(SeqDev
     const int ns_in = *(const int*)sw;
     const int ns = ns_in < 0 ? 0 : (ns_in > S.MS ? S.MS : ns_in);         // (the host refuses such a frame)
     const int nin = n_msg < 0 ? 0 : (n_msg > S.NIN ? S.NIN : n_msg);
-    if (tid < 8) ii[tid] = tid == 0 ? n_msg : (tid == 4 ? ns_in : 0);
+    // (ints 1 .. 3 of the sample block's header: the relocalisation request of this step, zero in every other step)
+    if (tid < 8) ii[tid] = tid == 0 ? n_msg : (tid == 4 ? ns_in : (tid >= 5 ? ((const int*)sw)[tid - 4] : 0));
     // ---- samples: 7 ns doubles, pairs (an odd count takes the zero the host padded with; rows_off >= up8(7 MS))
     for (int k = tid; k < (7 * ns + 1) >> 1; k += SEQ_NT) ((double2*)idd)[k] = ((const double2*)(sw + 8))[k];
     // ---- ids
@@ -684,6 +736,7 @@ extern "C" hipError_t ba_seq_launch_slide(const BaLayout& L, const BaLayout* dL,
     hipLaunchKernelGGL(ba_seq_slide_kernel, dim3(L.nwin), dim3(SEQ_NT), 0, stream, dL, P, S, cur);
     return hipGetLastError();
 }
+extern "C" int ba_seq_relo_max_match() { return SEQ_MM_MAX < 1024 ? SEQ_MM_MAX : 1024; }     // (a match index takes 10 bits of s_rel)
 extern "C" int ba_seq_limits(int* ft_max, int* nin_max, int* hdr_ints, int* in_rows_off) {
     if (ft_max) *ft_max = SEQ_FT_MAX;
     if (nin_max) *nin_max = SEQ_NIN_MAX;

@@ -44,6 +44,12 @@ struct SeqDev {
     double noise[4];                 // ACC_N GYR_N ACC_W GYR_W
     double* imu_st;                  // [nwin][SEQ_IMU_ST]: acc_0 gyr_0 g (9) | the measurement in front of the last frame's samples (6) | - |
                                      //                     state guess the last step propagated: pose (7) at 16, speedbias (9) at 23
+    // ---- relocalisation frames (vg_ba_seq_relo_reserve); all zero in a sequence begun without a reservation.  Whether window w is armed
+    //      for this step travels in its staging header: ints [5] = n_match (0: idle), [6] = frame, [7] = 1 when relo_d holds the pose
+    int MM;                          // max_match
+    int* relo_i;                     // [nwin][MM]: match ids, ascending
+    double* relo_d;                  // [nwin][8 + 2 MM]: relo_Pose (7) | - | match_xy
+    int* relo_out;                   // [nwin][4]: armed, relocalisation factors in the problem, frame, -  (ba_seq_build_kernel)
 };
 #define SEQ_IMU_ST 32
 struct BaSeq {
@@ -63,6 +69,19 @@ struct BaSeq {
     bool vio_staged = false;         // in_i / in_d hold what the last step's bridge kernel staged (vg_vio_get_frame)
     double* vio_d = nullptr;         // [nwin][8 + up8(7 MS)]
     PinnedBuf<double> h_vio;
+    // ---- relocalisation frames: vg_ba_seq_set_relo keeps the request on the host; the next step stages and uploads it
+    struct Relo {
+        bool armed = false, has_pose = false;
+        int frame = 0;
+        double pose[7] = {0, 0, 0, 0, 0, 0, 1}, prev_t[3] = {0, 0, 0}, prev_r[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        std::vector<int> id;
+        std::vector<double> xy;
+    };
+    int relo_reserve = 0;            // vg_ba_seq_relo_reserve: max_match of the NEXT vg_ba_seq_begin
+    std::vector<Relo> relo, relo_last;   // per window: armed for the next step / what the last step consumed (vg_ba_seq_get_relo)
+    PinnedBuf<int> h_relo_i;
+    PinnedBuf<double> h_relo_d;
+    bool relo_staged = false;        // h_relo_i / h_relo_d hold this step's matches: they go up with the staging
 };
 
 struct BaBatch {
@@ -87,6 +106,7 @@ struct BaBatch {
     int marg_mode = 0;               // vg_ba_set_marg_mode: VG_MARG_SQRT (default) / VG_MARG_EIGEN
     int imu_info_mode = 0;           // vg_ba_set_imu_info_mode: VG_IMU_INFO_FACTOR (default) / VG_IMU_INFO_REFERENCE
     int res_L = 0, res_F = 0, res_O = 0, res_N = 0;   // vg_ba_reserve: capacities every layout is built for at least
+    bool res_relo = false;           // vg_ba_seq_begin after vg_ba_seq_relo_reserve: the layout gets the loop-pose block (Kp = K + 1)
     int fused_min = -1;              // vg_ba_set_fused_min_windows (-1: environment VG_BA_FUSED_MIN, else 32; 0: never)
     bool no_env = false;             // handle made by vg_create_config: no environment variable shapes its behaviour
     int pack_threads = 0;            // host threads sharing the packing of a batch (0: environment VG_PACK_THREADS, else 8)

@@ -321,6 +321,36 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
     if (device_imu) resp->useDeviceImu();
     // VINS_REPLAY_TIMING=1: per frame "T,<frame>,<ms in processIMU>,<ms in solve()>" on stderr (tests/manual/gpu_seq_imu.py)
     const bool timing = getenv("VINS_REPLAY_TIMING") != nullptr;
+    // VINS_REPLAY_RELO=<file>: relocalisation records, text: "frame estimator stamp n_match  prev_relo_t (3)  prev_relo_r (9, row-major)"
+    // followed by n_match lines "x y feature_id".  Before that frame of the file setReloFrame() is called for the estimator
+    // (ResidentEstimators::useRelocalisation), and after its solve() the by-products go to <out>.relo, one line per record:
+    // frame,estimator,found,n_factors,local_index,relo_Pose (7),relo_relative_t (3),relo_relative_q (x y z w),relo_relative_yaw,
+    // drift_correct_r (9),drift_correct_t (3)
+    struct ReloRec { int frame, est; double stamp; Vector3d t; Matrix3d r; std::vector<Vector3d> match; bool found = false; };
+    std::vector<ReloRec> relo;
+    if (const char* rl_env = getenv("VINS_REPLAY_RELO")) {
+        FILE* rf = fopen(rl_env, "r");
+        if (!rf) { perror("relocalisation records"); return 2; }
+        ReloRec q;
+        int n = 0, max_match = 1;
+        double t[3], r[9];
+        while (fscanf(rf, "%d %d %lf %d %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf", &q.frame, &q.est, &q.stamp, &n, &t[0], &t[1], &t[2], &r[0], &r[1], &r[2],
+                      &r[3], &r[4], &r[5], &r[6], &r[7], &r[8]) == 16) {
+            q.t = Vector3d(t[0], t[1], t[2]);
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) q.r(a, b) = r[3 * a + b];
+            q.match.clear();
+            for (int k = 0; k < n; ++k) {
+                double x, y; int id;
+                if (fscanf(rf, "%lf %lf %d", &x, &y, &id) != 3) { fprintf(stderr, "relocalisation records: short match list\n"); return 2; }
+                q.match.push_back(Vector3d(x, y, id));
+            }
+            max_match = std::max(max_match, n);
+            relo.push_back(q);
+        }
+        fclose(rf);
+        resp->useRelocalisation(max_match);
+    }
+    std::vector<std::vector<double>> stamps0(N);
     for (int i = 0; i < N; ++i) {
         // the estimator as the reference's code would hold it between two frames, then handed over
         Estimator est;
@@ -332,6 +362,7 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
             FrameInit fr;
             rd.d(&fr.t, 1); rd.d(fr.pose, 7); rd.d(fr.sb, 9);
             set_frame(est, k, fr);
+            stamps0[i].push_back(fr.t);
         }
         for (int k = 0; k + 2 < K; ++k) est.pre_integrations[k + 1] = preintegrate(h, rd, S, bias, noise);
         rd.d(last, 6);
@@ -376,9 +407,11 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
             }
         }
         resp->handOver(i, est, Vector3d(last[0], last[1], last[2]), Vector3d(last[3], last[4], last[5]));
+        for (int k = 0; k <= WINDOW_SIZE; ++k) (*resp)[i].Headers[k] = stamps0[i][k];
         for (int k = 0; k <= WINDOW_SIZE; ++k) { delete est.pre_integrations[k]; est.pre_integrations[k] = nullptr; }
     }
     resp->begin();
+    FILE* orelo = relo.empty() ? nullptr : fopen((std::string(out) + ".relo").c_str(), "w");
     // VINS_REPLAY_KERNEL_TIMES=1 (with the IMU on the device): per frame "K,<frame>,<ms in ba_seq_imu_kernel>,<ms in ba_seq_merge_kernel>"
     // on stderr, from HIP events; asking for them waits for the merge, so such a run is not one to take host times from
     const bool kernel_times = device_imu && getenv("VINS_REPLAY_KERNEL_TIMES") != nullptr;
@@ -389,6 +422,8 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
     for (int w = 0; w < W; ++w) {
         std::vector<double> stamp(N);
         double imu_ms = 0;
+        for (ReloRec& q : relo)
+            if (q.frame == w) q.found = resp->setReloFrame(q.est, q.stamp, 0, q.match, q.t, q.r);
         for (int i = 0; i < N; ++i) {
             rd.d(&stamp[i], 1);
             rd.d(smp.data(), S * 7);
@@ -412,7 +447,7 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
                 image = fe.next();
                 fe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             }
-            resp->processImage(i, image);
+            resp->processImage(i, image, stamp[i]);
         }
         const auto t_solve = std::chrono::steady_clock::now();
         resp->solve();
@@ -432,14 +467,26 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
                     (int)e.marginalization_flag, e.n_features, e.status, e.failure_occur ? 1 : 0);
             if (frames) fprintf(o, "t,%d,%.3f,%.3f\n", i, fe_ms, solve_ms);      // vio: wall time of readImage / of processImage's solve, ms
         }
+        for (const ReloRec& q : relo) {
+            if (q.frame != w) continue;
+            const ResidentEstimators::One& e = (*resp)[q.est];
+            fprintf(orelo, "%d,%d,%d,%d,%d", w, q.est, q.found ? 1 : 0, q.found ? e.relo_n_factors : 0, q.found ? e.relo_frame_local_index : -1);
+            for (int k = 0; k < 7; ++k) fprintf(orelo, ",%.12g", e.relo_Pose[k]);
+            fprintf(orelo, ",%.12g,%.12g,%.12g", e.relo_relative_t.x(), e.relo_relative_t.y(), e.relo_relative_t.z());
+            fprintf(orelo, ",%.12g,%.12g,%.12g,%.12g,%.12g", e.relo_relative_q.x(), e.relo_relative_q.y(), e.relo_relative_q.z(), e.relo_relative_q.w(), e.relo_relative_yaw);
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) fprintf(orelo, ",%.12g", e.drift_correct_r(a, b));
+            fprintf(orelo, ",%.12g,%.12g,%.12g\n", e.drift_correct_t.x(), e.drift_correct_t.y(), e.drift_correct_t.z());
+        }
         if (w == handback_frame) {
             std::unique_ptr<ResidentEstimators> next(new ResidentEstimators(N, 512, 512));
             if (device_imu) next->useDeviceImu();
+            if (!relo.empty()) { int mm = 1; for (const ReloRec& q : relo) mm = std::max(mm, (int)q.match.size()); next->useRelocalisation(mm); }
             std::vector<std::unique_ptr<Estimator>> back;
             for (int i = 0; i < N; ++i) {
                 back.emplace_back(new Estimator());
                 resp->handBack(i, *back[i]);
                 next->handOver(i, *back[i], (*resp)[i].acc_0, (*resp)[i].gyr_0);
+                for (int k = 0; k <= WINDOW_SIZE; ++k) (*next)[i].Headers[k] = (*resp)[i].Headers[k];
             }
             next->begin();
             next->reseed(0, *back[0], (*resp)[0].acc_0, (*resp)[0].gyr_0);
@@ -462,6 +509,7 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
             fprintf(stderr, "A,%d,%.3g\n", i, worst);
         }
     fclose(o);
+    if (orelo) fclose(orelo);
     fclose(rd.f);
     vg_destroy(h);
     return 0;

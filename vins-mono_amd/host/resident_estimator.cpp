@@ -53,6 +53,35 @@ void ResidentEstimators::useDeviceImu(int max_samples) {
     max_samples_ = max_samples;
 }
 
+void ResidentEstimators::useRelocalisation(int max_match) {
+    if (begun_) throw std::runtime_error("useRelocalisation() after begin()");
+    if (max_match < 1 || max_match > 1024) throw std::runtime_error("useRelocalisation(): max_match outside 1 .. 1024");
+    max_match_ = max_match;
+}
+
+bool ResidentEstimators::setReloFrame(int i, double frame_stamp, int frame_index, const std::vector<Vector3d>& match_points, const Vector3d& relo_t,
+                                      const Matrix3d& relo_r) {
+    if (!begun_ || !max_match_) throw std::runtime_error("setReloFrame(): useRelocalisation() before begin() reserves the loop-pose block");
+    One& o = est_[i];
+    o.relo_frame_stamp = frame_stamp; o.relo_frame_index = frame_index;
+    int found = -1;
+    for (int k = 0; k < WINDOW_SIZE; ++k) if (frame_stamp == o.Headers[k]) found = k;      // (estimator.cpp:1136-1145: the last match counts)
+    if (found < 0) return false;
+    std::vector<int> id;
+    std::vector<double> xy;
+    for (const Vector3d& m : match_points) { id.push_back((int)m.z()); xy.push_back(m.x()); xy.push_back(m.y()); }
+    vg_ba_relo_frame r;
+    memset(&r, 0, sizeof(r));
+    r.struct_size = (int)sizeof(r); r.frame = found;
+    r.pose = nullptr;                                               // relo_Pose = para_Pose[found] (:1142-1143): the resident pose of that frame
+    r.n_match = (int)id.size(); r.match_id = id.data(); r.match_xy = xy.data();
+    for (int k = 0; k < 3; ++k) r.prev_relo_t[k] = relo_t(k);
+    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) r.prev_relo_r[3 * a + b] = relo_r(a, b);
+    if (vg_ba_seq_set_relo(vg_, i, &r) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_set_relo: ") + vg_last_error(vg_));
+    o.relo_frame_local_index = found; o.relocalization_info = true;
+    return true;
+}
+
 void ResidentEstimators::deviceImuTiming(bool on) {
     if (!begun_ || !device_imu_) throw std::runtime_error("deviceImuTiming(): the IMU state is not on the device");
     if (vg_ba_seq_imu_timing(vg_, on ? 1 : 0) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_timing: ") + vg_last_error(vg_));
@@ -209,6 +238,7 @@ void ResidentEstimators::begin() {
     vg_ba_seq_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.max_features = max_features_; cfg.max_new_obs = max_new_obs_; cfg.init_depth = INIT_DEPTH; cfg.min_parallax = MIN_PARALLAX;
+    if (max_match_ && vg_ba_seq_relo_reserve(vg_, max_match_) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_relo_reserve: ") + vg_last_error(vg_));
     if (vg_ba_seq_begin(vg_, size(), &cfg, pb.data(), tr.data()) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_begin: ") + vg_last_error(vg_));
     for (Window*& w : win_) { delete w; w = nullptr; }
     if (device_imu_) {
@@ -255,6 +285,11 @@ void ResidentEstimators::processImage(int i, const Image& image) {
         for (int k = 0; k < 7; ++k) o.rows.push_back(p(k, 0));
     }
     o.have_frame = true;
+}
+
+void ResidentEstimators::processImage(int i, const Image& image, double stamp) {
+    processImage(i, image);
+    est_[i].Headers[WINDOW_SIZE] = stamp;                           // Headers[frame_count] = header (estimator.cpp:133)
 }
 
 void ResidentEstimators::solve() {
@@ -372,6 +407,25 @@ void ResidentEstimators::finishStep() {
             o.Ps[k] = P[from]; o.Rs[k] = R[from]; o.Vs[k] = V[from]; o.Bas[k] = Ba[from]; o.Bgs[k] = Bg[from];
         }
         o.last_R = o.Rs[WINDOW_SIZE]; o.last_P = o.Ps[WINDOW_SIZE]; o.last_R0 = o.Rs[0]; o.last_P0 = o.Ps[0];      // :205-208
+        if (o.marginalization_flag == Estimator::MARGIN_OLD) for (int k = 0; k < WINDOW_SIZE; ++k) o.Headers[k] = o.Headers[k + 1];      // :1021
+        else o.Headers[WINDOW_SIZE - 1] = o.Headers[WINDOW_SIZE];                                                                    // :1062
+        o.relo_solved = o.relocalization_info;
+        if (o.relocalization_info) {
+            // the relative pose between the two loop frames and the drift correction (double2vector, estimator.cpp:598-612), formed
+            // inside the library from the downloaded states
+            vg_ba_relo_result r;
+            memset(&r, 0, sizeof(r));
+            r.struct_size = (int)sizeof(r);
+            if (vg_ba_seq_get_relo(vg_, i, &r) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_get_relo: ") + vg_last_error(vg_));
+            memcpy(o.relo_Pose, r.pose, sizeof(o.relo_Pose));
+            o.relo_n_factors = r.n_factors;
+            o.relo_relative_t = Vector3d(r.relo_relative_t[0], r.relo_relative_t[1], r.relo_relative_t[2]);
+            o.relo_relative_q = Quaterniond(r.relo_relative_q[3], r.relo_relative_q[0], r.relo_relative_q[1], r.relo_relative_q[2]);
+            o.relo_relative_yaw = r.relo_relative_yaw;
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) o.drift_correct_r(a, b) = r.drift_correct_r[3 * a + b];
+            o.drift_correct_t = Vector3d(r.drift_correct_t[0], r.drift_correct_t[1], r.drift_correct_t[2]);
+            o.relocalization_info = false;
+        }
         {
             const double* e = st[i].ex_pose;
             const double qn = std::sqrt(e[3] * e[3] + e[4] * e[4] + e[5] * e[5] + e[6] * e[6]);

@@ -40,6 +40,19 @@ class ResidentEstimators {
         bool failure_occur = false;
         Vector3d last_P, last_P0;
         Matrix3d last_R, last_R0;
+        // Headers[k].stamp.toSec() of the window (estimator.h:95): set by the caller after handOver() for the frames handed over, by
+        // processImage(i, image, stamp) for every further frame, shifted with the window; what setReloFrame() resolves its stamp against
+        double Headers[WINDOW_SIZE + 1] = {};
+        // relocalisation (estimator.h:125-138).  setReloFrame() arms the next solve(); after it the by-products of double2vector()
+        // (estimator.cpp:598-612) are here, relo_Pose is the gauge-fixed loop pose and relo_n_factors the factors the problem held
+        bool relocalization_info = false;
+        int relo_frame_local_index = 0, relo_n_factors = 0;
+        double relo_frame_stamp = 0, relo_Pose[7] = {0, 0, 0, 0, 0, 0, 1}, relo_relative_yaw = 0;
+        int relo_frame_index = 0;
+        Matrix3d drift_correct_r;
+        Vector3d drift_correct_t, relo_relative_t;
+        Quaterniond relo_relative_q;
+        bool relo_solved = false;             // the LAST solve() carried a relocalisation frame for this estimator
         // ---- internal
         Interval cur, prev;                   // pre_integrations[WINDOW_SIZE] (running) and [WINDOW_SIZE - 1] (may take cur's samples, estimator.cpp:1069-1085)
         bool merge_pending = false;
@@ -68,15 +81,23 @@ class ResidentEstimators {
     // measurement taps in that mode (vg_ba_seq_imu_timing / _times): device time of the IMU kernel and of the merge of the last solve(), ms
     void deviceImuTiming(bool on);
     void deviceImuTimes(float& imu_kernel_ms, float& merge_kernel_ms);
+    // Opt-in, before begin(): the windows get the loop-pose block and room for max_match (1 .. 1024) relocalisation factors
+    // (vg_ba_seq_relo_reserve), and setReloFrame() may be called between two frames.
+    void useRelocalisation(int max_match);
+    // Estimator::setReloFrame (estimator.cpp:1128-1147) of estimator i: the stamp is looked up in Headers[0 .. WINDOW_SIZE); where it is
+    // found, the NEXT solve() carries the loop pose (initially the pose of that frame) and one factor per matched landmark
+    // (match_points[k] = x, y, feature id; ids ascending), selected on the device (vg_ba_seq_set_relo).  Returns whether it was found.
+    bool setReloFrame(int i, double frame_stamp, int frame_index, const std::vector<Vector3d>& match_points, const Vector3d& relo_t, const Matrix3d& relo_r);
     void begin();                             // vg_ba_seq_begin once every estimator has been handed over
     // The way back, between two frames: window i of the running sequence into the members of a host Estimator (Ps / Rs / Vs / Bas /
     // Bgs, ric / tic / td, pre_integrations[1 .. WINDOW_SIZE - 1] -- the last one with its raw samples --, f_manager.feature,
-    // last_marginalization_info + parameter blocks): vg_ba_seq_export + vg_ba_seq_get_tracks.  For a relocalisation frame (not
-    // offered in a sequence), a checkpoint, a re-start after failureDetection().  The device keeps its copy; reseed() replaces it.
+    // last_marginalization_info + parameter blocks): vg_ba_seq_export + vg_ba_seq_get_tracks.  For a checkpoint or a re-start after
+    // failureDetection().  The device keeps its copy; reseed() replaces it.
     void handBack(int i, Estimator& e);
     void reseed(int i, Estimator& e, const Vector3d& acc_0, const Vector3d& gyr_0);     // vg_ba_seq_import: estimator i only
     void processIMU(int i, double dt, const Vector3d& linear_acceleration, const Vector3d& angular_velocity);
     void processImage(int i, const Image& image);
+    void processImage(int i, const Image& image, double stamp);      // with header.stamp.toSec(): Headers[WINDOW_SIZE] of the mirror
     void solve();                             // one frame for every estimator (all must have received their image)
     One& operator[](int i) { return est_[i]; }
     int size() const { return (int)est_.size(); }
@@ -91,6 +112,7 @@ class ResidentEstimators {
     bool begun_ = false;
     bool device_imu_ = false;
     int max_samples_ = 512;
+    int max_match_ = 0;
     void stepFromHost();                      // solve(): the host-fed step (pre-integration + propagated guess from here)
     void finishStep();                        // solve(): download, mirror, sample buffers
 };
