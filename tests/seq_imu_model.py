@@ -6,9 +6,16 @@ state and the record of interval K-3, seq_imu_get the resident measurement; afte
 seq_export the records.  Expected values are computed in NumPy from the device's OWN exported state (seq_model._propagate for the
 guess, synth.preintegrate for the records) and once more on the device through Handle.imu_preintegrate.  Bound for records and
 guess: 1e-11 x max|expected| per field, the bound of the same arithmetic chain in tests/test_ba_gpu.py
-(test_imu_preintegration_on_device); linearisation biases, valid flags and acc_0 / gyr_0 are compared exactly."""
+(test_imu_preintegration_on_device); linearisation biases, valid flags and acc_0 / gyr_0 are compared exactly.
+
+On top of that every record is held in its OWN scale (tests/imu_ref.py): record_error against the 80-bit restatement of the same
+samples <= M * E64 per field, M the one of tests/test_imu_scale.py.  E64 is the sequence's: what the float64 oracle loses on these
+very inputs, and no less than the yardstick of the case table (a single record's e64 is one draw of the rounding noise; the table
+is what M was measured against).  The merged record of a MARGIN_SECOND_NEW slide is checked against the 80-bit continuation of the
+device's own exported record K-3 and against the 80-bit integration of the concatenated sample list."""
 import numpy as np
 
+import imu_ref as R80
 import seq_model as M
 from seq_model import NEW, OLD, _propagate
 from vins_mono_amd import synth
@@ -47,11 +54,26 @@ def _close(got, want, where, worst, kind):
     assert d <= BOUND * scale, (where, kind, d / scale)
 
 
-def check_record(got, want, where, worst, kind):
+def ref80_of(smp, ba=None, bg=None, noise=R80.NOISE, start=None):
+    """(80-bit reference, E64 per kind) of one record: integrated from the identity at ba / bg, or continued from `start`"""
+    ref = R80.integrate(smp, ba, bg, noise, start=start)
+    e64, table = R80.e64_of(smp, ba, bg, noise, start=start, ref=ref), R80.yardstick()
+    return ref, {k: max(e64[k], table[k]) for k in R80.KINDS}
+
+
+def check_record(got, want, where, worst, kind, ref80=None, sum_dt_exact=True):
+    """ref80: what ref80_of returned for the samples `want` was integrated from"""
     assert got is not None, where
     _close([got['sum_dt']], [want['sum_dt']], where + ('sum_dt',), worst, kind)
     for key in REC_FIELDS:
         _close(got[key], want[key], where + (key,), worst, kind)
+    if ref80 is not None:
+        ref, E64 = ref80
+        err = R80.record_error(got, ref)
+        assert err['lin_ba'] == 0.0 and err['lin_bg'] == 0.0 and (err['sum_dt'] == 0.0 or not sum_dt_exact), (where, kind, err)
+        for key, k in R80.KIND_OF.items():
+            worst.note(kind + ', ' + k + ' / E64', err[key] / E64[k])
+            assert err[key] <= R80.M * E64[k], (where, kind, key, err[key], E64[k])
 
 
 def begin(h, srcs, K, min_parallax, max_features=128, max_samples=20, wins=None):
@@ -102,7 +124,7 @@ def step_checked(h, K, frames, hist, noise, g_norm, worst, step=0, allow_numeric
         want = synth.preintegrate(smp, ba_, bg_, *noise)
         flag = info[w]['flag']
         fresh = after['imu'][K - 3] if flag == OLD else after['imu'][K - 2]
-        check_record(fresh, want, where + ('new',), worst, 'record')
+        check_record(fresh, want, where + ('new',), worst, 'record', ref80_of(smp, ba_, bg_, noise))
         check_record(fresh, h.imu_preintegrate([smp], [(ba_, bg_)], noise)[0], where + ('new, vg_imu_preintegrate',), worst, 'record_vs_vg_imu_preintegrate')
         assert np.array_equal(fresh['lin_ba'], ba_) and np.array_equal(fresh['lin_bg'], bg_), where
         if flag == OLD:
@@ -115,7 +137,9 @@ def step_checked(h, K, frames, hist, noise, g_norm, worst, step=0, allow_numeric
             hist[w] = hist[w] + smp[1:]
             wantm = synth.preintegrate(hist[w], old['lin_ba'], old['lin_bg'], *noise)
             merged = after['imu'][K - 3]
-            check_record(merged, wantm, where + ('merged',), worst, 'merged_record')
+            # (the list's sum_dt starts with whatever the caller's first record held: only the continuation's is exact)
+            check_record(merged, wantm, where + ('merged',), worst, 'merged_record', ref80_of(hist[w], old['lin_ba'], old['lin_bg'], noise), sum_dt_exact=False)
+            check_record(merged, wantm, where + ('merged, continued',), worst, 'merged_continued', ref80_of(smp, noise=noise, start=old))
             check_record(merged, h.imu_preintegrate([hist[w]], [(old['lin_ba'], old['lin_bg'])], noise)[0], where + ('merged, vg_imu_preintegrate',), worst,
                          'merged_vs_vg_imu_preintegrate')
             assert np.array_equal(merged['lin_ba'], old['lin_ba']) and np.array_equal(merged['lin_bg'], old['lin_bg']), where
