@@ -10,10 +10,26 @@
 #include <vector>
 
 // dynamic LDS windows of the kernel sources (each `extern __shared__ ... name[]` needs one definition)
-thread_local __attribute__((aligned(16))) char ba_smem[160 * 1024];
-thread_local __attribute__((aligned(16))) char bp_smem[160 * 1024];
-thread_local __attribute__((aligned(16))) char mg_smem[160 * 1024];
-thread_local __attribute__((aligned(16))) unsigned char sel_smem[160 * 1024];
+#define SIMT_LDS_WINDOW (160 * 1024)
+thread_local __attribute__((aligned(16))) char ba_smem[SIMT_LDS_WINDOW];
+thread_local __attribute__((aligned(16))) char bp_smem[SIMT_LDS_WINDOW];
+thread_local __attribute__((aligned(16))) char mg_smem[SIMT_LDS_WINDOW];
+thread_local __attribute__((aligned(16))) unsigned char sel_smem[SIMT_LDS_WINDOW];
+// A window is as large as a CU's LDS whatever the launch asked for, so a carve that outgrows its request would run clean here and
+// fault on hardware: launch() fills every window behind the request with a pattern and aborts if a kernel changed it.
+static const unsigned char kLdsGuard = 0xA5;
+static void lds_guard(size_t lds_bytes, bool check) {
+    struct { const char* name; unsigned char* p; } win[] = {{"ba_smem", (unsigned char*)ba_smem}, {"bp_smem", (unsigned char*)bp_smem},
+                                                          {"mg_smem", (unsigned char*)mg_smem}, {"sel_smem", sel_smem}};
+    for (auto& w : win) {
+        if (!check) { memset(w.p + lds_bytes, kLdsGuard, SIMT_LDS_WINDOW - lds_bytes); continue; }
+        for (size_t b = lds_bytes; b < SIMT_LDS_WINDOW; ++b)
+            if (w.p[b] != kLdsGuard) {
+                fprintf(stderr, "simt: a kernel wrote %s at byte %zu, behind the %zu bytes of dynamic LDS of its launch\n", w.name, b, lds_bytes);
+                abort();
+            }
+    }
+}
 
 // ---- fiber switch.  glibc's swapcontext saves / restores the signal mask with a system call on every switch (half of the run time
 //      of the emulated tests was kernel time); a fiber here only needs its callee-saved registers and its stack pointer.
@@ -157,7 +173,8 @@ long long clock() {
 }
 
 void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>& body) {
-    if (lds_bytes > 160 * 1024) { fprintf(stderr, "simt: %zu bytes of dynamic LDS requested\n", lds_bytes); abort(); }
+    if (lds_bytes > SIMT_LDS_WINDOW) { fprintf(stderr, "simt: %zu bytes of dynamic LDS requested\n", lds_bytes); abort(); }
+    lds_guard(lds_bytes, false);
     const char* ord = getenv("SIMT_ORDER");
     const int order = !ord ? 0 : (!strcmp(ord, "reverse") ? 1 : (!strcmp(ord, "shuffle") ? 2 : 0));
     const int nthr = (int)(block.x * block.y * block.z);
@@ -210,6 +227,7 @@ void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>
         }
     }
     B = nullptr; cur = nullptr;
+    lds_guard(lds_bytes, true);
 }
 }  // namespace simt
 

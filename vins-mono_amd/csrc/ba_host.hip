@@ -16,7 +16,7 @@
 #include <string>
 #include <thread>
 #include <vector>
-#include "ba_layout.h"
+#include "ba_layout_fn.h"
 #include "vg_handle.h"
 #include "../../include/vinsgpu.h"
 
@@ -177,8 +177,6 @@ static void build_asm_plan(const BaLayout& L, std::vector<AsmPlanEntry>& plan) {
 static int build_layout(vg_handle* h, int nwin, const vg_ba_problem* const* in, const PriorRef* pr, BaLayout& L) {
     memset(&L, 0, sizeof(L));
     const vg_ba_problem* p0 = in[0];
-    L.nwin = nwin;
-    L.K = p0->K;
     bool relo = h->ba.res_relo;                  // (a sequence that reserved the loop-pose block: vg_ba_seq_relo_reserve)
     int Lmax = 1, Fmax = 1, Omax = 1, Nmax = 0, NBmax = 0;
     for (int w = 0; w < nwin; ++w) {
@@ -200,253 +198,24 @@ static int build_layout(vg_handle* h, int nwin, const vg_ba_problem* const* in, 
         NBmax = std::max(NBmax, pr[w].nb);
     }
     Lmax = std::max(Lmax, h->ba.res_L); Fmax = std::max(Fmax, h->ba.res_F); Omax = std::max(Omax, h->ba.res_O);      // vg_ba_reserve
-    if (h->ba.res_N > Nmax) { Nmax = h->ba.res_N; NBmax = std::max(NBmax, L.K + 4); }
-    L.Kp = L.K + (relo ? 1 : 0);
-    L.e = p0->estimate_extrinsic ? 1 : 0;
-    L.t = p0->estimate_td ? 1 : 0;
-    L.Rc = 6 * L.Kp + 6 * L.e + L.t;
-    L.RcPad = up(L.Rc + 1, 16);                  // + the augmented rhs row / column
-    L.R = L.Rc + 9 * L.K;
-    L.Rpad = up(L.R + 1, 8);
-    L.Lcap = up(Lmax, 16);
-    L.Fcap = up(Fmax, 16);
-    L.Ocap = up(Omax, 8);
-    L.Ncap = up(std::max(Nmax, 1), 8);
-    L.NBcap = up(std::max(NBmax, 1), 8);
-    L.REC = 28 + 12 * L.e + 2 * L.t;
-    L.nst = up(7 * L.Kp + 9 * L.K + 8, 2);
-    L.imu_info = h->ba.imu_info_mode;
-    // one workgroup solves a window out of LDS while the camera part fits its tiling; wider windows (and windows the
-    // caller shards over ranks) take the large-window path
-    L.big = (L.RcPad > 96 || L.Rc > 127 || L.K + 1 > BA_MAX_K || h->ba.force_large) ? 1 : 0;
-    if (L.big && L.Rc + 10 > 256) { h->err = "camera part wider than the large-window solve kernel's tiling"; return VG_ERR_UNSUPPORTED; }
-    // ---- workgroups per window
-    L.nbf = (L.Fcap + BA_LIN_NT - 1) / BA_LIN_NT;
-    // IMU / prior linearisation: spread over workgroups only while all of them fit the chip at once (latency mode)
-    {
-        const int nsplit = (L.K - 1 + BA_IMU_GROUP - 1) / BA_IMU_GROUP;
-        const bool split = (long)nwin * (nsplit + 1) <= 256;
-        L.igs = split ? BA_IMU_GROUP : L.K - 1;
-        L.nig = split ? nsplit : 1;
-        L.nprw = split ? 1 : 0;
-        L.pro_split = split ? 1 : 0;                   // (ba_prologue_kernel: its pieces side by side, see the kernel)
-    }
-    L.nbl = L.nbf + L.nig + L.nprw;
-    {
-        const int nb = L.Kp + L.e + L.t;
-        L.ntask = nb * (nb + 1) / 2;
-        const int per = BA_ACC_NT / 64;
-        const int ng = L.e + L.t, nglob = ng * (ng + 1) / 2;      // blocks among ex / td: they visit EVERY factor
-        // diagonal pose blocks get a workgroup each, the ex / td blocks share one (if present), wavefront tasks after them
-        L.nba = L.Kp + (ng ? 1 : 0) + (L.ntask - L.Kp - nglob + (L.Lcap + 63) / 64 + per - 1) / per;
-    }
-    // ---- LDS carve of the solve kernel (large-window path: only S, red and 1/L_jj are LDS offsets, the others are
-    //      offsets into the HBM scratch at so_bigm)
-    int bigm_doubles = 0;
-    {
-        // XC leading dimension: rows p and p+1 of an MFMA operand read must fall on different halves of the 64 banks
-        int ldc = L.RcPad;
-        if ((2 * ldc) % 64 != 32) ldc += 16;
-        L.ldc = ldc;
-        int o = 0, ob = 0;
-        int& oo = L.big ? ob : o;                    // where the movable arrays are carved from
-        L.l_S = o; o += up((L.Rc + 1) * (L.Rc + 2) / 2, 2);
-        L.l_XC = 0; L.l_ring = 0; L.l_pinv = 0;
-        if (L.big) { L.l_XC = oo; oo += up(9 * L.K, 8) * ldc; }    // (large path: two k-steps per trip of schur_chain_big)
-        else {
-            // single-workgroup path (round 5): the coupling rows are not held for the whole solve any more (100 rows x ldc = 64 KB of
-            // the former 134 KB carve).  Two slots of 18 rows -- the block pair being eliminated and the pair before it -- are all the
-            // chain elimination reads; finished rows are parked in HBM (so_xp) for the back substitution.  The staged landmark tile
-            // of the Schur sweep (l_wd) and the small scratch uses of `wd` alias the ring: they are only live outside the chain.
-            L.l_ring = o; o += 36 * ldc;
-        }
-        L.l_D = oo; oo += up(81 * L.K, 2);
-        L.l_E = oo; oo += up(81 * L.K, 2);
-        L.l_dinv = oo; oo += up(9 * L.K, 2);
-        L.l_vec = oo; oo += 9 * L.Rpad;
-        L.l_red = o; o += 32;
-        if (L.big) { L.l_wd = oo; oo += up(std::max(9 * L.K, 162), 2); }
-        else L.l_wd = L.l_ring;                                    // [RcPad][32 + 1] <= 36 ldc;  SV_NT, 9 K, 162 doubles of scratch likewise
-        L.l_z = oo; oo += up(36 * L.K, 2);
-        if (L.big) { L.l_pmap = oo; oo += up(L.Ncap, 4) / 2; }
-        else { L.l_pmap = 0; L.l_pinv = o; o += up(L.R, 4) / 2; }
-        if (L.big) { L.l_di = o; o += up(L.Rc + 1, 2); L.l_cz = o; o += 6 * 96; }
-        L.l_Sg = 0;
-        if (L.big) { L.l_Sg = oo; oo += up((L.Rc + 1) * (L.Rc + 2) / 2, 2); }      // S between the halves of the reduced solve
-        L.lds_solve = o * 8;
-        bigm_doubles = ob;
-        if (!L.big && L.Rc + 10 - 64 > 32) { h->err = "solve kernel: more column tasks than three wavefronts"; return VG_ERR_UNSUPPORTED; }
-        if (!L.big && 36 * ldc < std::max(std::max(L.RcPad * 33, 2 * SV_NT), std::max(9 * L.K, 162))) { h->err = "solve kernel: scratch does not fit the coupling-row ring"; return VG_ERR_UNSUPPORTED; }
-        if (L.lds_solve > 160 * 1024) { h->err = "solve kernel LDS carve exceeds 160 KB"; return VG_ERR_UNSUPPORTED; }
-        const int nib = std::min(std::min(L.K - 1, BA_IMU_BATCH), L.igs);
-        L.lds_lin = 8 * std::max(up(nib * 225, 2) + nib * 480, 5 * L.Ncap);
-        L.lds_pro = 8 * BA_NW * (L.imu_info ? 512 : 256);      // imu_sqrt_info / imu_sqrt_info_ref: scratch per wavefront
-        if (8 * L.Ncap * L.Ncap <= 128 * 1024) L.lds_pro = std::max(L.lds_pro, 8 * L.Ncap * L.Ncap);   // J0 staged in LDS when it fits
-        if (L.lds_lin > 128 * 1024) { h->err = "prior too large for the linearisation kernel"; return VG_ERR_UNSUPPORTED; }
-        // fused projection kernel (ba_linacc_proj_kernel): LDS = staged records [la_chf][33] | pair blocks [Kp (Kp - 1) / 2][90] |
-        // keys [la_chf] + chunk starts [64] (ints)
-        {
-            static const bool env_off = getenv("VG_BA_FUSED") && !strcmp(getenv("VG_BA_FUSED"), "0");       // (development switches:
-            const bool off = env_off && !h->ba.no_env;                                                          //  plain vg_create() only)
-            // few windows: the chip is empty and the separate kernels spread a window over many workgroups (single window: 28 us per
-            // round against 52 us for the one fused workgroup); from a few dozen windows on the fused kernel wins
-            static const int env_min = getenv("VG_BA_FUSED_MIN") ? atoi(getenv("VG_BA_FUSED_MIN")) : 32;
-            const int la_min_windows = h->ba.fused_min >= 0 ? (h->ba.fused_min ? h->ba.fused_min : 1 << 30) : (env_min ? env_min : 1 << 30);
-            const int npair = L.Kp * (L.Kp - 1) / 2;
-            // (the per-round kernel reports 8 KB of fixed group segment -- its non-inlined phases -- next to the dynamic LDS: 160 KB in all)
-            const int avail = (160 * 1024 - 8192 - 512) / 8;
-            const int nstl = up(7 * L.Kp + 9 * L.K + 8, 2);                                   // the staged state (round 6)
-            int chf = (int)((avail - nstl - npair * 90 - 34 - (64 + 82 + 8 * 80) / 2) / 34.0);      // per factor: record 33 doubles + key + position (2 ints)
-            chf = std::min(chf & ~1, 512);
-            L.la_on = (!off && L.nwin >= la_min_windows && !L.big && !L.e && !L.t && L.Kp <= 13 && chf >= 96 && (L.Fcap + chf - 17) / (chf - 16) <= 62) ? 1 : 0;
-            L.la_chf = chf; L.la_chq = chf - 16;
-            L.la_P = up(chf * 33, 2);
-            L.la_key = L.la_P + up(npair * 90, 2);
-            L.la_x = up(L.la_key + (2 * chf + 64 + 82 + 8 * 80 + 1) / 2 + 2, 2);
-            L.lds_linacc = (L.la_x + nstl) * 8;
-        }
-        // which build of the per-round solve kernel: 4 wavefronts per window (two windows per CU, the batch) or 8 (ba_solve_w8.hip: a
-        // few windows on an otherwise empty chip).  Below 32 windows -- where the factor side is in its latency
-        // mode as well -- the second window per CU does not exist and the wavefront slots go to the same window.
-        {
-            static const int env_max = getenv("VG_BA_SOLVE_W8_BELOW") ? atoi(getenv("VG_BA_SOLVE_W8_BELOW")) : -1;      // (development switch:
-            const int below = (env_max >= 0 && !h->ba.no_env) ? env_max : 32;                                             //  plain vg_create() only)
-            L.sv_w8 = (!L.big && L.nwin < below) ? 1 : 0;
-            // (the 8-wavefront build stages the landmark tile of its Schur phase, [RcPad][32 + 1] doubles, behind the carve -- the ring it
-            //  aliases in the 4-wavefront kernel is live beside it there; a shape that leaves no room keeps the 4-wavefront kernel)
-            L.l_wd8 = L.lds_solve / 8;
-            L.lds_solve_w8 = L.lds_solve + 8 * L.RcPad * 33;
-            if (L.lds_solve_w8 > 160 * 1024) L.sv_w8 = 0;
-        }
-    }
-    if (L.big) {
-        const int nt = (L.Rc + 1 + 15) / 16;
-        L.nts = nt * (nt + 1) / 2;
-        const int ntri = L.Rc * (L.Rc + 1) / 2;
-        L.rb1_T = up(ntri + L.Rc, 2);
-        L.rb1_scal = L.rb1_T + up((L.Rc + 1) * (L.Rc + 2) / 2, 2);
-        L.rb1_len = L.rb1_scal + RB1_NSCAL;
-    }
-    // ---- int arrays
-    int o = 0;
-    L.io_hdr = o; o += BA_HDR_INTS;
-    L.io_lm_start = o; o += L.Lcap;
-    L.io_lm_fbeg = o; o += L.Lcap + 8;
-    L.io_fac_i = o; o += L.Fcap;
-    L.io_fac_j = o; o += L.Fcap;
-    L.io_fac_lm = o; o += L.Fcap;
-    L.io_fac_oi = o; o += L.Fcap;
-    L.io_fac_oj = o; o += L.Fcap;
-    L.io_fac_slot = o; o += L.Fcap;
-    L.io_pair_ptr = o; o += up(L.Kp * L.Kp + 1, 8);
-    L.io_task_list = o; o += up(L.ntask, 8);
-    L.io_imu_valid = o; o += up(L.K, 8);
-    L.io_pb_kind = o; o += L.NBcap;
-    L.io_pb_idx = o; o += L.NBcap;
-    L.io_pb_col = o; o += L.NBcap;
-    L.io_pb_off = o; o += L.NBcap;
-    L.io_pb_x0off = o; o += L.NBcap;
-    L.istride = up(o, 8);
-    // ---- double inputs
-    o = 0;
-    L.do_pose = o; o += up(7 * L.Kp, 2);
-    L.do_sb = o; o += up(9 * L.K, 2);
-    L.do_ex = o; o += 8;
-    L.do_td = o; o += 2;
-    L.do_lam = o; o += L.Lcap;
-    L.do_obs = o; o += L.Ocap * BA_OBS_STRIDE;
-    L.do_imu = o; o += (L.K - 1) * BA_IMU_STRIDE;
-    L.do_par = o; o += P_NPAR;
-    L.dstride = up(o, 8);
-    // ---- prior factor: a buffer of its own whose layout depends on K alone as long as the prior is one the marginalization
-    //      can have produced (n <= 6K + 25, <= K + 4 blocks) -- so that a prior can stay where it is between frames
-    L.pld = std::max(up(6 * L.K + 9 * 2 + 6 + 1, 8), L.Ncap);
-    L.po_x0 = 0;
-    L.po_r0 = 9 * std::max(up(L.K + 4, 8), L.NBcap);
-    L.po_J0 = L.po_r0 + L.pld;
-    L.pstride = up(L.po_J0 + L.pld * L.pld, 8);
-    // ---- scratch
-    o = 0;
-    L.so_ctl = o; o += C_NCTL;
-    L.so_part = o; o += up(L.nbl, 8);
-    L.so_x = o; o += 2 * L.nst;
-    L.so_lam = o; o += 2 * L.Lcap;
-    L.so_imuU = o; o += up((L.K - 1) * 225, 2);
-    L.so_Hp = o; o += L.Ncap * L.Ncap;
-    L.so_J0t = o; o += L.Ncap * L.Ncap;
-    L.so_rec = o; o += L.Fcap * L.REC;
-    L.so_sc = o; o += L.Rpad;
-    L.so_sl = o; o += L.Lcap;
-    L.so_dg = o; o += L.Rpad + L.Lcap;
-    L.so_gt = o; o += L.Rpad + L.Lcap;
-    L.so_gn = o; o += L.Rpad + L.Lcap;
-    L.so_yl = o; o += L.Lcap;
-    L.so_lsc = o; o += L.Lcap;
-    L.so_xp = 0;
-    if (!L.big) { L.so_xp = o; o += up(9 * L.K, 4) * L.ldc; }
-    if (L.big) {
-        L.so_bigm = o; o += up(bigm_doubles, 8);
-        L.so_dgl = o; o += 2 * L.Lcap;
-        L.so_gtl = o; o += 2 * L.Lcap;
-    }
-    {
-        int b = 0;
-        L.bo_Sp = b; b += up(L.Rc * (L.Rc + 1) / 2, 2);
-        L.bo_gp = b; b += L.RcPad;
-        L.bo_h = b; b += L.Lcap;
-        L.bo_b = b; b += L.Lcap;
-        L.bo_Wt = b; b += L.RcPad * L.Lcap;
-        L.bo_imuJ = b; b += (L.K - 1) * 512;       // per factor: 465 lower Hessian entries + 30 gradient entries
-        L.bo_pr = b; b += L.Ncap;
-        L.bo_gpr = b; b += L.Ncap;
-        L.buf_stride = up(b, 8);
-    }
-    L.so_buf = o; o += 2 * L.buf_stride;
-    L.sstride = up(o, 8);
-    // gather plan of assemble_small behind the device copy of this struct (build_asm_plan)
-    L.pl_off = (int)((sizeof(BaLayout) + 255) / 256 * 256);
-    L.pl_n = L.big ? 0 : L.Rc * (L.Rc + 1) / 2 + L.Rpad + 2 * 81 * L.K;
-    // ---- outputs
-    o = 0;
-    L.oo_pose = o; o += up(7 * L.Kp, 2);
-    L.oo_sb = o; o += up(9 * L.K, 2);
-    L.oo_ex = o; o += 8;
-    L.oo_td = o; o += 2;
-    L.oo_lam = o; o += L.Lcap;
-    L.oo_sum = o; o += BA_SUM_DOUBLES;
-    L.oo_trace = o; o += 5 * VG_MAX_ITERS + 16;
-    L.ostride = up(o, 8);
-    L.oi_stride = up(4 + VG_MAX_ITERS, 8);
-    // ---- marginalization: kept dimension <= 6K + 2*9 + 6 + 1; blocks <= K + 4.  Both paths: the kernel's LDS tables are
-    //      sized for BA_MAX_K_LARGE frames; a kept block wider than the LDS tile is factored in global memory.
-    L.mcap = up(6 * L.K + 9 * 2 + 6 + 1, 8);
-    if (L.mcap > 256) { h->err = "kept dimension of the marginalization beyond the kernel's tables"; return VG_ERR_UNSUPPORTED; }
-    const int mcap = L.mcap;
-    L.mo_J0 = 0;
-    L.mo_r0 = mcap * mcap;
-    L.mo_x0 = L.mo_r0 + mcap;
-    L.mo_stride = up(L.mo_x0 + (L.K + 4) * 9, 8);
-    L.mi_stride = up(8 + 2 * (L.K + 4) + 16, 8);   // + 16 phase stamps (BA_PROFILE builds)
-    L.mg_posmax = up(mcap + 15 + L.Lcap, 2);
-    {
-        // LDS of the marginalization kernel: [eigM ld^2][eigV ld^2][cs 2 ld][red 16][state][ints 256]
-        const int nstm = up(16 * L.K + 8 + 1, 2);
-        L.mg_cs = up(std::max(std::max(2 * mcap, 3 * (L.mg_posmax / 2 + 2)), 2 * (3 * ((mcap + 2) / 2) + 2) + 2), 2);   // generic: one table
-                                                     // of 3*half doubles; fast path: two (double-buffered)
-        L.mg_cs = std::max(L.mg_cs, std::max(up(5 * mcap + 8, 2), up(L.Lcap + 512, 2)));   // vh_eig: running diagonal, norms, eigenvalues, flags; Amm block elimination: Lcap + 2 x 256
-        const int fixed = 32 + nstm + BA_MARG_LDS_INTS / 2 + L.mg_cs;
-        int ld = mcap + 1;                           // big enough for the kept part; also used for Amm when m <= ld.  ODD:
-                                                     // the symmetric-storage Jacobi walks columns (stride ld doubles) and
-                                                     // an even stride folds them onto a few LDS banks (96 -> one bank)
-        while (2 * ld * ld + fixed > 160 * 1024 / 8) ld -= 2;
-        L.mg_ld = ld;
-        L.mg_lds_bytes = (2 * ld * ld + fixed) * 8;
-        if (ld < 8) { h->err = "marginalization LDS carve failed"; return VG_ERR_UNSUPPORTED; }
-        const long pm = L.mg_posmax;
-        long sdoubles = pm * pm + pm + (long)L.Fcap * 42 + 2 * pm * (mcap + 1) + 2 * pm * pm + 2L * mcap * mcap + 2 * L.Ncap + 480 + L.Lcap + 64 + L.Lcap / 2 + 8;
-        L.ms_stride = (int)up((int)sdoubles, 8);
-    }
-    return VG_OK;
+    if (h->ba.res_N > Nmax) { Nmax = h->ba.res_N; NBmax = std::max(NBmax, p0->K + 4); }
+    // the switches of the fused projection kernel and of the 8-wavefront solve build (development switches in the environment: plain
+    // vg_create() only)
+    static const bool env_off = getenv("VG_BA_FUSED") && !strcmp(getenv("VG_BA_FUSED"), "0");
+    static const int env_min = getenv("VG_BA_FUSED_MIN") ? atoi(getenv("VG_BA_FUSED_MIN")) : 32;
+    static const int env_max = getenv("VG_BA_SOLVE_W8_BELOW") ? atoi(getenv("VG_BA_SOLVE_W8_BELOW")) : -1;
+    const int never = 1 << 30;
+    BaShape s;
+    s.nwin = nwin; s.K = p0->K; s.relo = relo ? 1 : 0;
+    s.e = p0->estimate_extrinsic ? 1 : 0; s.t = p0->estimate_td ? 1 : 0;
+    s.Lmax = Lmax; s.Fmax = Fmax; s.Omax = Omax; s.Nmax = Nmax; s.NBmax = NBmax;
+    s.imu_info_mode = h->ba.imu_info_mode; s.force_large = h->ba.force_large ? 1 : 0;
+    s.fused_min = (env_off && !h->ba.no_env) ? never : h->ba.fused_min >= 0 ? (h->ba.fused_min ? h->ba.fused_min : never) : (env_min ? env_min : never);
+    s.w8_below = (env_max >= 0 && !h->ba.no_env) ? env_max : 32;
+    const char* err = "";
+    const int rc = ba_layout_from_shape(s, L, &err);
+    if (rc) h->err = err;
+    return rc;
 }
 
 // ---- packing of one window ------------------------------------------------------------------------

@@ -111,8 +111,8 @@ struct BaLayout {
     int mo_J0, mo_r0, mo_x0, mo_stride;       // doubles
     int mi_stride;                            // ints: [valid, n, m, nblocks, kind[NBcap], idx[NBcap]]
     int ms_stride;                            // marginalization scratch doubles per window
-    int mcap, mg_ld, mg_posmax, mg_cs, mg_lds_bytes; // kept-dimension capacity, LDS eig leading dim, max (m+n)
-    // ---- LDS carve of the solve kernel (offsets in doubles)
+    int mcap, mg_ld, mg_posmax, mg_cs, mg_lds_bytes; // kept-dimension capacity, LDS eig leading dim, max (m+n), doubles of `cs` (MargCs), bytes of the carve (MargLds)
+    // ---- LDS carve of the solve kernel (offsets in doubles; the ring's size and what aliases it: SolveRing, ba_carve.h)
     int l_S, l_XC, l_D, l_E, l_dinv, l_vec, l_red, l_wd, l_z, l_pmap, ldc, lds_solve;
     // single-workgroup path: l_ring = two slots of 18 coupling rows [2][18][ldc] (the block pair being eliminated and the pair before
     // it; l_wd aliases it: the staged landmark tile is only needed after the chain), l_pinv = reduced column -> prior index (R ints)
@@ -120,9 +120,10 @@ struct BaLayout {
     // gather plan of assemble_small (single-workgroup path): pl_n entries of four ints, pl_off bytes behind the start of the device
     // copy of this struct (built by the host with the layout: it depends on nothing else)
     int pl_off, pl_n;
-    int lds_lin, lds_pro;                     // dynamic LDS bytes of the linearisation / prologue kernels
+    int lds_lin, lds_pro;                     // dynamic LDS bytes of the linearisation / prologue kernels (LinLds / ProLds)
     // ---- fused projection kernel (ba_linacc_proj_kernel): eligible windows (la_on), landmarks per chunk by first factor index
-    //      (la_chq), staged-record capacity (la_chf = la_chq + 16), LDS offsets (doubles) of the pair blocks and of the key table
+    //      (la_chq), staged-record capacity (la_chf = la_chq + 16), LDS offsets (doubles) of the pair blocks and of the key table: the
+    //      P / key / x / end of the carve LinaccLds (ba_carve.h), which the kernel evaluates for the int tables behind `key`
     int la_on, la_chq, la_chf, la_P, la_key, la_x, lds_linacc;      // (la_x: the state of the linearisation point, staged once per launch)
     // ---- host only: the batch is solved by ba_solve_w8_kernel (8 wavefronts per window) instead of ba_solve_kernel (4): few windows
     int sv_w8;
@@ -159,3 +160,5 @@ struct BaPtrs {
 
 // parameter slots at do_par
 enum { P_FOCAL = 0, P_TR, P_ROW, P_GNORM, P_MAXTIME, P_NPAR = 8 };
+
+#include "ba_carve.h"             // the LDS / scratch carves of the kernels and the constants they are cut by

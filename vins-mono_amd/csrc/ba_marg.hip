@@ -1029,31 +1029,32 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
 #define MPROF(i) do { } while (0)
 #endif
 
-    // ---- LDS carve: [eigM ld*ld][eigV ld*ld][cs 2*ld][red 16][x state][ints]
+    // ---- LDS carve (MargLds, ba_carve.h)
     const int ld = L.mg_ld;
-    double* eM = MG_LDS;
-    double* eV = eM + ld * ld;
-    double* cs = eV + ld * ld;
-    double* red = cs + L.mg_cs;
-    double* x = red + 32;
-    const int nst = (7 * K + 9 * K + 8 + 1) & ~1;
-    int* li = (int*)(x + nst);
+    const MargLds lds = marg_lds(K, ld, L.mg_cs);
+    double* eM = MG_LDS + lds.eM;
+    double* eV = MG_LDS + lds.eV;
+    double* cs = MG_LDS + lds.cs;
+    double* red = MG_LDS + lds.red;
+    double* x = MG_LDS + lds.x;
+    int* li = (int*)(MG_LDS + lds.ints);
     MgMap mp;
     mp.pose = li + MGI_POSE; mp.sb = li + MGI_SB; mp.misc = li + MGI_MISC;
     // ---- global scratch carve
     const int posmax = L.mg_posmax;
-    double* A = c.ms;                        // posmax x posmax
-    double* bv = A + (size_t)posmax * posmax;
-    double* rec = bv + posmax;               // Fcap x 42 projection records
-    double* T1 = rec + (size_t)L.Fcap * 42;  // posmax x (mcap+1)
-    double* T2 = T1 + (size_t)posmax * (mcap + 1);
-    double* gM = T2 + (size_t)posmax * (mcap + 1);   // staging / eig fallback (posmax^2) x 2
-    double* gV = gM + (size_t)posmax * posmax;
-    double* g2M = gV + (size_t)posmax * posmax;      // second-eig fallback (mcap^2) x 2
-    double* g2V = g2M + (size_t)mcap * mcap;
-    double* prv = g2V + (size_t)mcap * mcap;         // prior residual (Ncap) + dx (Ncap)
-    mp.lm = (int*)(prv + 2 * L.Ncap + 480);
-    mp.l0 = mp.lm + L.Lcap;
+    const MargScratch ms = marg_scratch(posmax, L.Fcap, mcap, L.Ncap, L.Lcap);      // (MargScratch, ba_carve.h)
+    double* A = c.ms + ms.A;                 // posmax x posmax
+    double* bv = c.ms + ms.bv;
+    double* rec = c.ms + ms.rec;             // Fcap x MG_REC projection records
+    double* T1 = c.ms + ms.T1;               // posmax x (mcap+1)
+    double* T2 = c.ms + ms.T2;
+    double* gM = c.ms + ms.gM;               // staging / eig fallback (posmax^2) x 2
+    double* gV = c.ms + ms.gV;
+    double* g2M = c.ms + ms.g2M;             // second-eig fallback (mcap^2) x 2
+    double* g2V = c.ms + ms.g2V;
+    double* prv = c.ms + ms.prv;             // prior residual (Ncap) + dx (Ncap)
+    mp.lm = (int*)(c.ms + ms.lm);
+    mp.l0 = (int*)(c.ms + ms.l0);
 
     // ---- state after the gauge fix (what vector2double() repacks at estimator.cpp:831 / :942)
     for (int k = c.tid; k < 7 * K; k += MG_NT) x[k] = outp[L.oo_pose + k];
@@ -1291,9 +1292,9 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
         const int ncam = 6 * K + 7;
         // LDS: [records cap x 42 doubles][jof cap ints][sorted list cap ints][landmark of a factor cap ints][compact factor offsets n0 + 1 ints] ... [partial tiles]
         const int cfb_ints = (n0 + 2) & ~1;
-        const int cap = (4 * ld * ld - cfb_ints - 2 * MG_T0W * 256) / 87;      // (both eigen-solver tiles: 4 ld^2 ints) 84 ints of record + jof + list entry + landmark
+        const int cap = (4 * ld * ld - cfb_ints - 2 * MG_T0W * 256) / (2 * MG_REC + 3);      // (both eigen-solver tiles: 4 ld^2 ints) 84 ints of record + jof + list entry + landmark
         double* recL = eM;
-        int* jofL = (int*)(recL + (size_t)cap * 42);         // [cap] target frame or -2
+        int* jofL = (int*)(recL + (size_t)cap * MG_REC);         // [cap] target frame or -2
         int* slist = jofL + cap;                             // [cap] compact ids sorted by target frame (stable)
         int* kofL = slist + cap;                             // [cap] frame-0 landmark (index into l0) of a compact factor
         int* cfb = kofL + cap;                               // [n0 + 1] compact factor offsets
@@ -1349,14 +1350,14 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 jofL[cf] = j;
                 const double* oi = c.di + L.do_obs + c.ia[L.io_fac_oi + f] * BA_OBS_STRIDE;
                 const double* oj = c.di + L.do_obs + c.ia[L.io_fac_oj + f] * BA_OBS_STRIDE;
-                double R[42];
+                double R[MG_REC];
                 double Jtd[2] = {0, 0};
                 if (L.t) proj_eval<true, true, true>(x, x + 7 * j, ex, lam[l], oi, oj, ex[7], c.focal, c.tr, c.row, R, R + 2, R + 14, R + 26, R + 38, Jtd);
                 else proj_eval<false, true, true>(x, x + 7 * j, ex, lam[l], oi, oj, 0.0, c.focal, c.tr, c.row, R, R + 2, R + 14, R + 26, R + 38, Jtd);
                 R[40] = Jtd[0]; R[41] = Jtd[1];
                 const double sq = sqrt(1.0 / (1.0 + R[0] * R[0] + R[1] * R[1]));   // Cauchy: rho'' < 0 branch (:46-50)
 #pragma unroll
-                for (int q = 0; q < 42; ++q) recL[(size_t)cf * 42 + q] = R[q] * sq;
+                for (int q = 0; q < MG_REC; ++q) recL[(size_t)cf * MG_REC + q] = R[q] * sq;
             }
             __syncthreads();
             MPROF(9);
@@ -1407,7 +1408,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
 #pragma unroll
                     for (int u = 0; u < 4; ++u) { const int qq = q + 2 * u + msel; cf[u] = sl_[qq < qb ? qq : qa]; }
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = recl[vg_mul24(cf[u], 42) + offa_c];
+                    for (int u = 0; u < 4; ++u) v[u] = recl[vg_mul24(cf[u], MG_REC) + offa_c];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) { const int qq = q + 2 * u + msel; v[u] = (qq < qb && offa >= 0) ? v[u] : 0.0; }
 #pragma unroll
@@ -1427,7 +1428,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
 #pragma unroll
                         for (int u = 0; u < 4; ++u) { const int qq = q + 2 * u + msel; cf[u] = sl_[qq < q1 ? qq : q0]; }
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) { const int ro = vg_mul24(cf[u], 42); va[u] = recl[ro + offa_c]; vb[u] = recl[ro + offb_c]; }
+                        for (int u = 0; u < 4; ++u) { const int ro = vg_mul24(cf[u], MG_REC); va[u] = recl[ro + offa_c]; vb[u] = recl[ro + offb_c]; }
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int qq = q + 2 * u + msel;
@@ -1475,7 +1476,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 const int cf = wk / 6, kk = wk - 6 * cf;
                 const int j = jofL[cf];
                 if (j < 0 || mp.pose[j] < 0) continue;
-                const lds_d* R = recl + vg_mul24(cf, 42);
+                const lds_d* R = recl + vg_mul24(cf, MG_REC);
                 const double v = R[14 + kk] * R[38] + R[20 + kk] * R[39];
                 const int cl = lmb + kofL[cf], ca = mp.pose[j] + kk;
                 Ag[(size_t)cl * posmax + ca] = v; Ag[(size_t)ca * posmax + cl] = v;
@@ -1492,7 +1493,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 double sacc = 0.0;
                 const int fb = cfb[k] - cbase, fe = cfb[k + 1] - cbase;
                 for (int cf = fb; cf < fe; ++cf) {
-                    const lds_d* R = recl + vg_mul24(cf, 42);
+                    const lds_d* R = recl + vg_mul24(cf, MG_REC);
                     const double v = R[o0] * R[38] + R[o1] * R[39];
                     sacc += jofL[cf] >= 0 ? v : 0.0;
                 }
@@ -2114,7 +2115,7 @@ extern "C" hipError_t ba_launch_marg(const BaLayout& L, const BaLayout* dL, cons
         if (e != hipSuccess) return e;
         std::lock_guard<std::mutex> lock(mu);
         if (!(dev >= 0 && dev < 64 && ((done_mask >> dev) & 1ull))) {
-            e = hipFuncSetAttribute((const void*)ba_marg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            e = hipFuncSetAttribute((const void*)ba_marg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_CU_LDS);
             if (e != hipSuccess) return e;
             if (dev >= 0 && dev < 64) done_mask |= 1ull << dev;
         }

@@ -289,7 +289,7 @@ NOINL void imu_sqrt_info_ref(const Ctx& c_in, int fbeg, int fend) {
 #pragma clang fp contract(off)
     const Ctx c = c_in;
     const BaLayout L = *c.Lp;
-    double* A = LDSB + c.wave * 512;
+    double* A = LDSB + c.wave * PRO_WS_REF;
     double* V = A + 240;
     double* Pm = V + 240;
     const int nimu = fend < L.K - 1 ? fend : L.K - 1;      // this workgroup's factors: [fbeg, fend) in passes of BA_NW
@@ -301,7 +301,7 @@ NOINL void imu_sqrt_info_ref(const Ctx& c_in, int fbeg, int fend) {
         const bool row = act && i < 15;
         const double* cov = c.di + L.do_imu + f * BA_IMU_STRIDE + IM_COV;
         if (act)
-            for (int k = c.lane; k < 225; k += 64) A[k] = cov[k];
+            for (int k = c.lane; k < IMU_U; k += 64) A[k] = cov[k];
         if (row) Pm[i] = (double)i;
         __syncthreads();
         for (int k = 0; k < 15; ++k) {                 // LU in place, row pivoting: the first row of the largest magnitude
@@ -358,7 +358,7 @@ NOINL void imu_sqrt_info_ref(const Ctx& c_in, int fbeg, int fend) {
             }
             __syncthreads();
         }
-        double* Uo = c.sc + L.so_imuU + f * 225;        // sqrt_info = L^T (upper), zeros below the diagonal
+        double* Uo = c.sc + L.so_imuU + f * IMU_U;        // sqrt_info = L^T (upper), zeros below the diagonal
         if (row)
             for (int r = 0; r < 15; ++r) Uo[r * 15 + i] = (i >= r) ? A[i * 15 + r] : 0.0;
         __syncthreads();
@@ -372,7 +372,7 @@ NOINL void imu_sqrt_info(const Ctx& c_in, int fbeg, int fend) {
     // registers, a pivot column reaches the other rows through v_readlane, and nothing in between waits for the workgroup (it used
     // to be three workgroup barriers and an LDS round trip per column, 45 per pass).  Same operations on the same operands in the same
     // order: the factor is the one the LDS form produced.
-    lds_d* A = AS_LDS(LDSB + c.wave * 256);          // 15x15 scratch per wavefront (the factor, for the column solves below)
+    lds_d* A = AS_LDS(LDSB + c.wave * PRO_WS);          // 15x15 scratch per wavefront (the factor, for the column solves below)
     const int nimu = fend < L.K - 1 ? fend : L.K - 1;      // this workgroup's factors: [fbeg, fend) in passes of BA_NW
     const glb_i* valid = AS_GLB_CI(c.ia + L.io_imu_valid);
     const int li = c.lane < 15 ? c.lane : 14;
@@ -401,7 +401,7 @@ NOINL void imu_sqrt_info(const Ctx& c_in, int fbeg, int fend) {
         }
         __builtin_amdgcn_wave_barrier();
         // X = U^-1 (upper): lane = column j, back-substitute upward
-        glb_d* Uo = AS_GLB(c.sc + L.so_imuU + f * 225);
+        glb_d* Uo = AS_GLB(c.sc + L.so_imuU + f * IMU_U);
         if (c.lane < 15) {
             const int j = c.lane;
             double x[15];
@@ -546,19 +546,20 @@ NOINL double imu_pass(const Ctx& c_in, const double* x_, double* imuJ_, int fbeg
     glb_d* imuJ = AS_GLB(imuJ_);
     const glb_d* gU = AS_GLB_C(c.sc + L.so_imuU);
     const int nb = fend - fbeg < BA_IMU_BATCH ? fend - fbeg : BA_IMU_BATCH;      // factors per pass (one pass per workgroup normally)
-    double* Us = LDSB;                                      // [nb][225]
-    double* panels = Us + ((nb * 225 + 1) & ~1);            // [nb][15][32]
+    const LinLds lds = lin_lds(nb, 0);                      // (LinLds: U [nb][IMU_U] | panels [nb][15][32])
+    double* Us = LDSB + lds.U;
+    double* panels = LDSB + lds.panels;
     double cost = 0.0;
     const int per = nb > BA_NW ? 2 : 1;
     const int half = c.lane >> 5, hl = c.lane & 31;
     for (int f0 = fbeg; f0 < nimu; f0 += nb) {
         const int nf = nimu - f0 < nb ? nimu - f0 : nb;
-        for (int k0 = c.tid; k0 < nf * 225; k0 += 8 * BA_NT) {      // (the loads of a thread issued together, then the LDS stores)
+        for (int k0 = c.tid; k0 < nf * IMU_U; k0 += 8 * BA_NT) {      // (the loads of a thread issued together, then the LDS stores)
             double uv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { const int k = k0 + u * BA_NT; uv[u] = k < nf * 225 ? gU[f0 * 225 + k] : 0.0; }
+            for (int u = 0; u < 8; ++u) { const int k = k0 + u * BA_NT; uv[u] = k < nf * IMU_U ? gU[f0 * IMU_U + k] : 0.0; }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { const int k = k0 + u * BA_NT; if (k < nf * 225) Us[k] = uv[u]; }
+            for (int u = 0; u < 8; ++u) { const int k = k0 + u * BA_NT; if (k < nf * IMU_U) Us[k] = uv[u]; }
         }
         __syncthreads();
         const int fl = c.wave * per + half;                 // factor of this (half-)wavefront inside the pass
@@ -571,8 +572,8 @@ NOINL double imu_pass(const Ctx& c_in, const double* x_, double* imuJ_, int fbeg
             for (int k = 0; k < 7; ++k) { pi[k] = x[7 * f + k]; pj[k] = x[7 * (f + 1) + k]; }
 #pragma unroll
             for (int k = 0; k < 9; ++k) { si[k] = x[7 * L.Kp + 9 * f + k]; sj[k] = x[7 * L.Kp + 9 * (f + 1) + k]; }
-            const double* U = Us + fl * 225;
-            double* panel = panels + fl * 480;
+            const double* U = Us + fl * IMU_U;
+            double* panel = panels + fl * IMU_PANEL;
             ImuCtx ic;
             imu_ctx<JAC>(pre, pi, si, pj, sj, c.gnorm, ic);
             double raw[15];
@@ -603,7 +604,7 @@ NOINL double imu_pass(const Ctx& c_in, const double* x_, double* imuJ_, int fbeg
                 const int ff = t / 3, tile = t - 3 * ff;
                 if (!valid[f0 + ff]) continue;                 // (uniform)
                 const int tm = tile > 0 ? 1 : 0, tn = tile > 1 ? 1 : 0;
-                const lds_d* panel = AS_LDS_C(panels + ff * 480);
+                const lds_d* panel = AS_LDS_C(panels + ff * IMU_PANEL);
                 double av[4], bv[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -641,8 +642,9 @@ NOINL double prior_pass(const Ctx& c_in, const double* x, double* pr_, double* g
     const Ctx c = c_in;                       // local copies: fields read through the references would be re-loaded (flat_load +
     const BaLayout L = *c.Lp;                 // full s_waitcnt) after every store that might alias them
     if (c.nprior == 0) return 0.0;
-    lds_d* dx = AS_LDS(lds_);
-    lds_d* part = dx + L.Ncap;
+    const LinLds lds = lin_lds(0, L.Ncap);    // (LinLds: dx [Ncap] | part [4 Ncap])
+    lds_d* dx = AS_LDS(lds_) + lds.dx;
+    lds_d* part = AS_LDS(lds_) + lds.part;
     glb_d* pr = AS_GLB(pr_);
     glb_d* gpr = AS_GLB(gpr_);
     const glb_i* kind = AS_GLB_CI(c.ia + L.io_pb_kind);
@@ -731,8 +733,9 @@ NOINL double prior_pass(const Ctx& c_in, const double* x, double* pr_, double* g
 DEV double prior_staged(const Ctx& c, const BaLayout& L, const double* x, double* pr_, double* gpr_, double* lds_) {
     const int n = c.nprior, ld = n + 1;
     lds_d* Jl = AS_LDS(lds_);
-    lds_d* dx = Jl + ((n * ld + 1) & ~1);
-    lds_d* part = dx + L.Ncap;
+    const LinLds lds = lin_lds(0, L.Ncap);    // (dx | part as in prior_pass, behind the J0 copy)
+    lds_d* dx = Jl + ((n * ld + 1) & ~1) + lds.dx;
+    lds_d* part = Jl + ((n * ld + 1) & ~1) + lds.part;
     glb_d* pr = AS_GLB(pr_);
     glb_d* gpr = AS_GLB(gpr_);
     const glb_i* kind = AS_GLB_CI(c.ia + L.io_pb_kind);
@@ -1221,13 +1224,7 @@ extern "C" __global__ __launch_bounds__(BA_ACC_NT) void ba_accumulate_kernel(con
 // Afterwards the diagonal blocks are summed from the pair blocks in a fixed order and Sp / gp go to the linearisation buffer: what
 // reaches HBM is Sp, gp, h, b, Wt and one cost partial -- the 42-double records (101.7 MB written + 87.9 MB read back per
 // 256-window launch, profiles/r03s_pmc_hbm.txt) are gone, and so is one launch per round.
-#define LA_NT BA_NT                // (imu_pass / prior_pass are written for BA_NT threads)
-#define LA_RS 33                  // doubles per staged record: rows at 0 and 16, odd stride (conflict-free b64 stores by thread)
-#define LA_NPW 6                  // wavefronts that own pair blocks; the other two of the workgroup take the landmark sums
-#define LA_MAXP 13                // pairs per pair wavefront: Kp (Kp - 1) / 2 <= 78 for Kp <= 13
-#define LA_QCAP 80                // pairs a window can have (78 for Kp = 13), padded
-static_assert(LA_QCAP <= 128, "the pair prefix of ba_linacc_proj_kernel takes two pairs per lane of one wavefront");
-#define LA_PAIR 90                // kept doubles of a pair block: ii 21 | jj 21 | ji 36 (row = target's column, col = anchor's) | gi 6 | gj 6
+// (LA_NT, LA_RS, LA_NPW, LA_MAXP, LA_QCAP, LA_PAIR and the LDS carve LinaccLds: ba_carve.h)
 // pairs (i, j), i < j, enumerated by distance d = j - i first: q = (d - 1) Kp - (d - 1) d / 2 + i.  The pairs of one distance -- and the
 // near-diagonal ones carry most factors -- are consecutive, so q mod LA_NPW deals them evenly to the pair wavefronts.
 // inclusive prefix sum over the 64 lanes of a wavefront: four row_shr steps inside the rows of sixteen, the row totals through SGPRs
@@ -1252,13 +1249,14 @@ __device__ __forceinline__ void linacc_body(const BaLayout* __restrict__ Lp, con
     const double* lam = c.sc + L.so_lam + which * L.Lcap;
     glb_d* buf = AS_GLB(lin_buf(c, which));
     const glb_i* ia = AS_GLB_CI(c.ia);
-    lds_d* rec = AS_LDS(LDSB);
+    const LinaccLds lds = linacc_lds(L.K, L.Kp, L.la_chf, L.Ncap);      // (its P / key / x travel in the layout: la_P, la_key, la_x)
+    lds_d* rec = AS_LDS(LDSB + lds.rec);
     lds_d* Pb = AS_LDS(LDSB + L.la_P);
     lds_i* key = (lds_i*)(LDSB + L.la_key);          // (anchor << 4 | target) of the factor a chunk thread evaluated
-    lds_i* lstart = key + L.la_chf;                   // [64] first landmark of every chunk
-    lds_i* posx = lstart + 64;                        // [la_chf] where that thread's record was staged (records are grouped by pair)
-    lds_i* pstart = posx + L.la_chf;                  // [LA_QCAP + 1] first record of every pair in the chunk
-    lds_i* wcnt = pstart + LA_QCAP + 2;               // [LA_NT / 64][LA_QCAP] factors of pair q evaluated by wavefront w
+    lds_i* lstart = key + lds.i_lstart;               // [LA_NCH] first landmark of every chunk
+    lds_i* posx = key + lds.i_posx;                   // [la_chf] where that thread's record was staged (records are grouped by pair)
+    lds_i* pstart = key + lds.i_pstart;               // [LA_QCAP + 1] first record of every pair in the chunk
+    lds_i* wcnt = key + lds.i_wcnt;                   // [LA_NT / 64][LA_QCAP] factors of pair q evaluated by wavefront w
     __shared__ double red[2 * (LA_NT / 64)];
     const int Kp = L.Kp, npair = Kp * (Kp - 1) / 2, chq = L.la_chq;
     const int nL = c.nL;
@@ -2150,8 +2148,6 @@ DEV bool cf_store(const ChainFac& f, int lane, P Dk, P dinvk) {
 // (k, k-1) lives in the slot E_k: for a TOP block k it holds Xe_k = L_k^-1 E_k as [p][c] (p = row of X_k, c = column sb_k-1), for
 // a BOTTOM block k-1 it holds L_k-1^-1 E_k^T as [p][c] too (c = column sb_k; the large-window path keeps [c][p]); X in HBM.  Returns this thread's share of the coupling part of
 // t^T H~ t; *flag (m.red + 24) = 0 on a non-positive pivot.
-#define SCHUR_LW 32                               // landmarks per staged tile
-#define SCHUR_LD (SCHUR_LW + 1)
 #define SCHUR_PF ((96 * SCHUR_LW + SV_NT - 1) / SV_NT)
 // SCHUR_TPW = 16x16 tiles of S per wavefront: 15 tiles (RcPad = 80) over four wavefronts = 4, 21 tiles (RcPad = 96) = 6
 template <int SCHUR_TPW>
@@ -2165,7 +2161,7 @@ NOINL double chain_schur(const Ctx& c_in, const SolveLds& m_in, const double* bu
     lds_d* const E = AS_LDS(m.E);
     lds_d* const dinv = AS_LDS(m.dinv);
     lds_d* const ring = AS_LDS(m.ring);            // rows 0..8: top block of the step, rows 9..17: bottom block
-    lds_d* const stage = ring + 18 * ldc;          // [2][9][18]: the IMU part of the raw coupling rows of the NEXT step's two blocks
+    lds_d* const stage = ring + solve_ring(K, RcPad, ldc).stage;         // [2][9][18]: the IMU part of the raw coupling rows of the NEXT step's two blocks
     lds_d* const wd = AS_LDS(m.wd);                // (aliases the ring: used after the chain)
     const lds_d* g = AS_LDS_C(m.vec + V_G * L.Rpad);
     const lds_d* sc = AS_LDS_C(m.vec + V_SC * L.Rpad);
@@ -2528,7 +2524,7 @@ NOINL double chain_schur_split(const Ctx& c_in, const SolveLds& m_in, const doub
     lds_d* const E = AS_LDS(m.E);
     lds_d* const dinv = AS_LDS(m.dinv);
     lds_d* const ring = AS_LDS(m.ring);            // rows 0..8: top block of the step, rows 9..17: bottom block
-    lds_d* const stage = ring + 18 * ldc;          // [2][9][18]: the IMU part of the raw coupling rows of the NEXT step's two blocks
+    lds_d* const stage = ring + solve_ring(K, RcPad, ldc).stage;         // [2][9][18]: the IMU part of the raw coupling rows of the NEXT step's two blocks
     lds_d* const wd = AS_LDS(LDSB + L.l_wd8);      // (its own tile behind the carve: the ring is live beside it)
     const lds_d* g = AS_LDS_C(m.vec + V_G * L.Rpad);
     const lds_d* sc = AS_LDS_C(m.vec + V_SC * L.Rpad);
@@ -3427,7 +3423,7 @@ __device__ __forceinline__ void solve_body(const BaLayout* __restrict__ Lp, cons
                     // (every pass of 64 landmarks has its own SV_NT partial sums in the scratch: ONE barrier for all passes, and the
                     //  loads of a pass are not fenced behind the previous pass's reduction)
                     const int npass = (nL + SV_NT / 4 - 1) / (SV_NT / 4);
-                    const bool own_slots = npass * SV_NT <= 36 * L.ldc;
+                    const bool own_slots = npass * SV_NT <= solve_ring(L.K, L.RcPad, L.ldc).size;
                     for (int ps = 0; ps < npass; ++ps) {
                         const int l0 = ps * (SV_NT / 4);
                         const int l = l0 + (c.tid & (SV_NT / 4 - 1)), qd = c.tid / (SV_NT / 4);
@@ -4569,7 +4565,7 @@ extern "C" __global__ __launch_bounds__(BA_NT) void ba_eval_factors_kernel(const
         const int f = w / 31, col = w % 31;
         if (!c.ia[L.io_imu_valid + f]) continue;
         const double* pre = c.di + L.do_imu + f * BA_IMU_STRIDE;
-        const double* U = c.sc + L.so_imuU + f * 225;
+        const double* U = c.sc + L.so_imuU + f * IMU_U;
         ImuCtx ic;
         imu_ctx<true>(pre, st_pose(L, x, f), st_sb(L, x, f), st_pose(L, x, f + 1), st_sb(L, x, f + 1), c.gnorm, ic);
         double raw[15];
@@ -4616,15 +4612,15 @@ static hipError_t set_lds_attrs() {
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(mu);
     if (dev >= 0 && dev < 64 && ((done_mask >> dev) & 1ull)) return hipSuccess;
-    e = hipFuncSetAttribute((const void*)ba_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_solve_w8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_solve_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_solve_big_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_prologue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_linacc_proj_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+    e = hipFuncSetAttribute((const void*)ba_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_CU_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_solve_w8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_CU_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_solve_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_CU_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_solve_big_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_CU_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_prologue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_CU_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_linacc_proj_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_LDS_MAX_LINACC);
     // (these two also hold a few statically allocated LDS words: static + dynamic must stay within 160 KB)
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_linearize_imu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_eval_factors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_linearize_imu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_LDS_MAX_LIN);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ba_eval_factors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BA_LDS_MAX_LIN);
     if (e == hipSuccess && dev >= 0 && dev < 64) done_mask |= 1ull << dev;
     return e;
 }
@@ -4659,7 +4655,7 @@ extern "C" hipError_t ba_launch_solve(const BaLayout& L, const BaLayout* dL, con
     if (ev) { e = hipEventRecord(ev[nev++], stream); if (e != hipSuccess) return e; }
     const bool forked = fk && fk->aux && !ev && !L.la_on;
     int nk = 0;
-    LAUNCH(ba_prologue_kernel, dim3(L.nwin, L.pro_split ? 1 + (L.K - 1 + BA_NW - 1) / BA_NW + 2 : 1), dim3(BA_NT), L.lds_pro, dL, P);
+    LAUNCH(ba_prologue_kernel, dim3(L.nwin, pro_grid_y(L.pro_split, L.K)), dim3(BA_NT), L.lds_pro, dL, P);
     if (kinds) kinds[nk++] = 0;
     for (int r = 0; r <= rounds; ++r) {
         const int cost_only = r == rounds ? 1 : 0;
@@ -4716,7 +4712,7 @@ extern "C" hipError_t ba_launch_solve_big(const BaLayout& L, const BaLayout* dL,
     } while (0)
 #define KIND(k) do { if (kinds) kinds[nk++] = (k); } while (0)
     // (profiling: the all-reduce sits in the gap before the kernel that consumes it and is counted with that kernel)
-    LAUNCH(ba_prologue_kernel, dim3(L.nwin, L.pro_split ? 1 + (L.K - 1 + BA_NW - 1) / BA_NW + 2 : 1), dim3(BA_NT), L.lds_pro, dL, P); KIND(0);
+    LAUNCH(ba_prologue_kernel, dim3(L.nwin, pro_grid_y(L.pro_split, L.K)), dim3(BA_NT), L.lds_pro, dL, P); KIND(0);
     // `rounds` = max_iters + slack: a failed factorisation retries in the NEXT round (the new T needs the collective), so a solve
     // can need more rounds than iterations.  Usually it does not: once the nominal number of rounds has been issued the host
     // looks at the windows' DONE flags (one strided 8-byte-per-window copy + a stream synchronisation) before every further
