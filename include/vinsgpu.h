@@ -31,7 +31,7 @@ extern "C" {
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
-                             * vg_vio_begin / _step_async / _get_frame / _end) */
+                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -118,6 +118,69 @@ int vg_imu_preintegrate(vg_handle* h, int n_intervals, const int* sample_off, co
  * depth[l] = svd_V[2] / svd_V[3] of the 2n x 4 DLT system, or init_depth (INIT_DEPTH) when that is < 0.1 (:245-254). */
 int vg_triangulate(vg_handle* h, int K, const double* Ps, const double* Rs, const double* tic, const double* ric, int L,
                    const int* start, const int* nobs, const int* obs_off, const double* points, double init_depth, double* depth);
+
+/* ---- Initialisation: visual-inertial alignment, batched (added within ABI 12, nothing existing changed) -----------------------------
+ * VisualIMUAlignment (initial/initial_aligment.cpp:3-207: solveGyroscopeBias, LinearAlignment, RefineGravity) and the state change of
+ * Estimator::visualInitialAlign that follows it (estimator.cpp:376-435) for n_windows independent windows in one synchronous call: one
+ * upload, one kernel (one workgroup per window, FP64), one download.  A window is one all_image_frame map: F ImageFrames in stamp order
+ * with their SfM poses and the raw IMU rows between them; the F - 1 records are integrated on the device through the per-sample body
+ * of vg_imu_preintegrate, first with (ba0, bg0), then again with (0, bg0 + delta_bg).
+ *
+ * The reference is followed, quirks included:
+ *   - the re-propagation passes a ZERO accelerometer bias (repropagate(Vector3d::Zero(), Bgs[0]), :35), whatever ba0 was;
+ *   - A and b of LinearAlignment are multiplied by 1000, the scale column holds (T_j - T_i) / 100, so s = x[n - 1] / 100;
+ *     it fails (VG_ALIGN_FAILED_LINEAR) when | |g| - g_norm | > 1 or s < 0; nothing after it is computed then, g_lin / s_lin are returned;
+ *   - RefineGravity clears its A and b ONCE before its four passes, not per pass, and multiplies them by 1000 at the end of every pass:
+ *     pass k solves the sum of the passes so far, the older ones weighted 1000^(k - j);
+ *   - TangentBasis compares the normalised gravity with (0, 0, 1) exactly; g0 <- normalised(g0 + lxly dg) g_norm after every pass;
+ *     s = x[n - 1] / 100 afterwards, s < 0 gives VG_ALIGN_FAILED_REFINE;
+ *   - Vs[k] = R[key[k]] * x.segment<3>(3 k): the reference indexes x by the KEY-FRAME counter kv, not by the frame's position in
+ *     all_image_frame (estimator.cpp:406-415); with non-key frames in front of a key frame that is another frame's velocity.
+ * Deviations:
+ *   - the solves are an unpivoted LDL^T where the reference calls Eigen's pivoted ldlt() (the systems are symmetric positive
+ *     semi-definite); a pivot that is not a positive finite number gives VG_ALIGN_NUMERIC for that window only, as does F < 4
+ *     (6 (F - 1) rows for 3 F + 4 unknowns: singular by count; delta_bg, bg and the records are still returned);
+ *   - R0 = g2R(g) uses Quaterniond::FromTwoVectors in its regular branch; when g is so close to -z that Eigen would take its SVD
+ *     branch (1 + g.z / |g| < 1e-12) the window gets VG_ALIGN_NUMERIC.
+ * Window stage (n_key > 0 and status OK): Rs[k] = R[key[k]], Ps[k] = s T[key[k]] - Rs[k] tic - (s T[key[0]] - Rs[0] tic), Vs as
+ * above; R0 = g2R(g) with the yaw of R0 Rs[0] removed; g_w = R0 g; Ps, Rs, Vs <- R0 ...  Clearing the depths, triangulate with a
+ * zero tic and estimated_depth *= s (:386-397, :416-422) stay the caller's: vg_triangulate and one multiplication.
+ * Refused with VG_ERR_BAD_ARG before anything is uploaded (vg_last_error says which; no output is touched, the handle stays usable):
+ * a wrong struct_size, F outside 2 .. VG_ALIGN_MAX_FRAMES, a NULL table, sample_off not ascending or an empty interval, a key list
+ * that does not ascend or leaves [0, F), n_key of 1 or above F, a non-finite input.  An interval longer than vg_imu_preintegrate's
+ * practice is integrated like there.  What is not computed for a window's status is returned as zeros. */
+enum { VG_ALIGN_OK = 0, VG_ALIGN_FAILED_LINEAR = 1, VG_ALIGN_FAILED_REFINE = 2, VG_ALIGN_NUMERIC = 3 };
+#define VG_ALIGN_MAX_FRAMES 32
+
+typedef struct {                 /* one window = one all_image_frame map */
+    size_t struct_size;          /* sizeof(vg_align_in) */
+    int n_frames;                /* F, 2 .. VG_ALIGN_MAX_FRAMES: ImageFrame entries in stamp order */
+    const double* R;             /* [F][9] row-major, ImageFrame::R (body rotation in the SfM frame c0) */
+    const double* T;             /* [F][3] ImageFrame::T (camera position in c0, unscaled) */
+    const int* sample_off;       /* [F] interval k (frame k -> k + 1) integrates rows [sample_off[k], sample_off[k + 1]) */
+    const double* samples;       /* rows dt acc gyr, as vg_imu_preintegrate */
+    const double* first;         /* [F - 1][6] acc_0 gyr_0 of every interval */
+    double ba0[3], bg0[3];       /* biases the records are FIRST integrated with (Bas / Bgs during initialisation) */
+    double noise[4];             /* ACC_N GYR_N ACC_W GYR_W */
+    double tic[3];               /* TIC[0] */
+    double g_norm;               /* G.norm() */
+    int n_key;                   /* K, 0 or 2 .. F: frames of the window (Headers[0 .. frame_count]) */
+    const int* key;              /* [K] ascending indices into the F frames */
+} vg_align_in;
+
+typedef struct {
+    size_t struct_size;          /* sizeof(vg_align_out), set by the caller */
+    int status;                  /* VG_ALIGN_* */
+    double delta_bg[3], bg[3];   /* solveGyroscopeBias; bg = bg0 + delta_bg */
+    double g_lin[3], s_lin;      /* LinearAlignment before RefineGravity (s already / 100) */
+    double g_c0[3], s;           /* after RefineGravity (the status is OK or FAILED_REFINE) */
+    double* v_body;              /* [F][3] x.segment<3>(3 i) after RefineGravity, or NULL */
+    vg_imu_preint* records;      /* [F - 1] the records re-propagated with (0, bg), or NULL */
+    double *Ps, *Rs, *Vs;        /* [K][3] [K][9] [K][3] the window after estimator.cpp:376-435, or NULL when n_key == 0 */
+    double g_w[3], R0[9];        /* g = R0 g, rot_diff */
+} vg_align_out;
+
+int vg_init_align(vg_handle* h, int n_windows, const vg_align_in* in, vg_align_out* out);
 
 /* block kinds of the marginalization prior (MarginalizationInfo::keep_block_*) */
 enum { VG_BLK_POSE = 0, VG_BLK_SPEEDBIAS = 1, VG_BLK_EXPOSE = 2, VG_BLK_TD = 3 };
@@ -881,9 +944,10 @@ int vg_fe_tracks_set(vg_handle* h, int cam, const vg_fe_tracks_state* state);
  * vg_vio_begin       needs, else VG_ERR_BAD_ARG with a vg_last_error text: resident lists begun (vg_fe_tracks_begin); a running sequence
  *                    in IMU mode (vg_ba_seq_begin + vg_ba_seq_imu_begin) on the same handle; n_cams == nwin; max_points <=
  *                    vg_ba_seq_config::max_new_obs; flags of VG_VIO_*.  The lists may hold tracks and the windows a seeded state -- the
- *                    normal case: initialisation stays on the host, the caller runs the first K-1 frames through vg_fe_tracks_step,
- *                    seeds the sequence from the collected messages and switches to vg_vio_step_async (the ids stay consistent
- *                    because the list is resident).
+ *                    normal case: the caller runs the first K-1 frames through vg_fe_tracks_step, initialises from the collected
+ *                    messages (SfM and the extrinsic-rotation calibration on the host, the visual-inertial alignment of all
+ *                    windows in one vg_init_align call), seeds the sequence from the result and switches to vg_vio_step_async
+ *                    (the ids stay consistent because the list is resident).
  * vg_vio_step_async  one frame for every stream.  The frame of vg_fe_tracks_step (same kernels, same host finish of RANSAC and
  *                    detection); fe.publish must be uniform over the streams of one call.  On a frame that publishes, one kernel
  *                    (ba_seq_bridge_kernel) moves every stream's message from the commit kernel's output into the staging

@@ -91,6 +91,22 @@ class ReloResult(C.Structure):        # vg_ba_relo_result
                 ("drift_correct_r", C.c_double * 9), ("drift_correct_t", C.c_double * 3)]
 
 
+VG_ALIGN_OK, VG_ALIGN_FAILED_LINEAR, VG_ALIGN_FAILED_REFINE, VG_ALIGN_NUMERIC = 0, 1, 2, 3
+VG_ALIGN_MAX_FRAMES = 32
+
+
+class AlignIn(C.Structure):           # vg_align_in
+    _fields_ = [("struct_size", C.c_size_t), ("n_frames", C.c_int), ("R", _pd), ("T", _pd), ("sample_off", _pi), ("samples", _pd),
+                ("first", _pd), ("ba0", C.c_double * 3), ("bg0", C.c_double * 3), ("noise", C.c_double * 4), ("tic", C.c_double * 3),
+                ("g_norm", C.c_double), ("n_key", C.c_int), ("key", _pi)]
+
+
+class AlignOut(C.Structure):          # vg_align_out
+    _fields_ = [("struct_size", C.c_size_t), ("status", C.c_int), ("delta_bg", C.c_double * 3), ("bg", C.c_double * 3),
+                ("g_lin", C.c_double * 3), ("s_lin", C.c_double), ("g_c0", C.c_double * 3), ("s", C.c_double), ("v_body", _pd),
+                ("records", C.POINTER(ImuPreint)), ("Ps", _pd), ("Rs", _pd), ("Vs", _pd), ("g_w", C.c_double * 3), ("R0", C.c_double * 9)]
+
+
 SEQ_INFO = ("flag", "n_features", "n_tracked", "n_parallax", "n_landmarks", "n_factors", "status", "n_after")
 
 
@@ -304,6 +320,8 @@ class Handle:
             L.vg_ba_seq_relo_reserve.argtypes = [C.c_void_p, C.c_int]
             L.vg_ba_seq_set_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloFrame)]
             L.vg_ba_seq_get_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloResult)]
+        if hasattr(L, "vg_init_align"):                   # (added within ABI 12)
+            L.vg_init_align.argtypes = [C.c_void_p, C.c_int, C.POINTER(AlignIn), C.POINTER(AlignOut)]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -793,6 +811,54 @@ class Handle:
             res.append(dict(sum_dt=q.sum_dt, delta_p=np.array(q.delta_p), delta_q=np.array(q.delta_q), delta_v=np.array(q.delta_v),
                             lin_ba=np.array(q.linearized_ba), lin_bg=np.array(q.linearized_bg),
                             jacobian=np.array(q.jacobian).reshape(15, 15), covariance=np.array(q.covariance).reshape(15, 15)))
+        return res
+
+    @staticmethod
+    def init_align_pack(windows):
+        """(vg_align_in array, vg_align_out array, the NumPy arrays both point into) for init_align's window dicts"""
+        n = len(windows)
+        ins, outs, keep = (AlignIn * n)(), (AlignOut * n)(), []
+        for w, (a, o) in zip(windows, zip(ins, outs)):
+            R = np.array(w['R'], np.float64).reshape(-1, 9)               # (copies: the call never aliases the caller's arrays)
+            F = len(R)
+            T = np.array(w['T'], np.float64).reshape(F, 3)
+            off, rows, first = np.zeros(F, np.int32), [], np.zeros((max(F - 1, 1), 6))
+            for k, iv in enumerate(w['intervals']):
+                first[k, :3], first[k, 3:] = iv[0][1], iv[0][2]
+                for dt, acc, gyr in iv[1:]:
+                    rows.append([dt, acc[0], acc[1], acc[2], gyr[0], gyr[1], gyr[2]])
+                off[k + 1] = len(rows)
+            smp = np.ascontiguousarray(rows if rows else np.zeros((1, 7)), dtype=np.float64)
+            key = np.ascontiguousarray(w['key'] if w.get('key') is not None else [], np.int32)
+            K = len(key)
+            bufs = dict(R=R, T=T, off=off, smp=smp, first=first, key=key, v_body=np.zeros((F, 3)), records=(ImuPreint * max(F - 1, 1))(),
+                        Ps=np.zeros((K, 3)), Rs=np.zeros((K, 3, 3)), Vs=np.zeros((K, 3)))
+            keep.append(bufs)
+            a.struct_size, a.n_frames, a.R, a.T, a.sample_off, a.samples, a.first = C.sizeof(AlignIn), F, _dp(R), _dp(T), _ip(off), _dp(smp), _dp(first)
+            a.ba0[:], a.bg0[:] = [float(x) for x in w['ba0']], [float(x) for x in w['bg0']]
+            a.noise[:], a.tic[:], a.g_norm = [float(x) for x in w['noise']], [float(x) for x in w['tic']], float(w['g_norm'])
+            a.n_key = K
+            if K:
+                a.key = _ip(key)
+                o.Ps, o.Rs, o.Vs = _dp(bufs['Ps']), _dp(bufs['Rs']), _dp(bufs['Vs'])
+            o.struct_size, o.v_body, o.records = C.sizeof(AlignOut), _dp(bufs['v_body']), bufs['records']
+        return ins, outs, keep
+
+    def init_align(self, windows):
+        """VisualIMUAlignment and the state change of visualInitialAlign for a batch of windows (vg_init_align).  A window is a dict:
+        R [F][3][3], T [F][3] (ImageFrame::R / T), intervals (F - 1 lists in the layout of imu_preintegrate), ba0, bg0, noise, tic,
+        g_norm, key (ascending frame indices of the window, or None).  Returns one dict per window."""
+        ins, outs, keep = self.init_align_pack(windows)
+        self._chk(self.lib.vg_init_align(self.h, len(windows), ins, outs), "vg_init_align")
+        res = []
+        for o, b in zip(outs, keep):
+            recs = [dict(sum_dt=q.sum_dt, delta_p=np.array(q.delta_p), delta_q=np.array(q.delta_q), delta_v=np.array(q.delta_v),
+                         lin_ba=np.array(q.linearized_ba), lin_bg=np.array(q.linearized_bg),
+                         jacobian=np.array(q.jacobian).reshape(15, 15), covariance=np.array(q.covariance).reshape(15, 15))
+                    for q in b['records'][:len(b['R']) - 1]]
+            res.append(dict(status=int(o.status), delta_bg=np.array(o.delta_bg), bg=np.array(o.bg), g_lin=np.array(o.g_lin), s_lin=float(o.s_lin),
+                            g_c0=np.array(o.g_c0), s=float(o.s), v_body=b['v_body'], records=recs, Ps=b['Ps'], Rs=b['Rs'], Vs=b['Vs'],
+                            g_w=np.array(o.g_w), R0=np.array(o.R0).reshape(3, 3)))
         return res
 
     def triangulate(self, Ps, Rs, tic, ric, start, nobs, obs_off, points, init_depth=5.0):

@@ -129,6 +129,71 @@ void Estimator::repropagate(IntegrationBase* p) {
     vg_pack::preint_from_abi(*p, out);
 }
 
+bool Estimator::visualInitialAlign() {                          // estimator.cpp:364-440
+    if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
+    const double noise[4] = {ACC_N, GYR_N, ACC_W, GYR_W};
+    const int F = (int)all_image_frame.size(), K = frame_count + 1;
+    vg_pack::AlignIn in;
+    vg_pack_align(all_image_frame, Headers, K, Bas[0], Bgs[0], noise, tic[0], G_NORM, in);
+    vg_pack::AlignOut o(F, K);
+    if (vg_init_align(vg_, 1, &in.in, &o.out) != VG_OK) throw std::runtime_error(std::string("vg_init_align: ") + vg_last_error(vg_));
+    align_status = o.out.status;
+    if (align_status == VG_ALIGN_NUMERIC) return false;
+    // solveGyroscopeBias has run whatever LinearAlignment said (initial_aligment.cpp:29-36): Bgs += delta_bg, the records of
+    // all_image_frame re-propagated with (0, Bgs[0])
+    const Vector3d dbg(o.out.delta_bg[0], o.out.delta_bg[1], o.out.delta_bg[2]);
+    for (int i = 0; i <= WINDOW_SIZE; i++) Bgs[i] = Bgs[i] + dbg;
+    int k = 0;
+    for (auto it = all_image_frame.begin(); it != all_image_frame.end(); ++it, ++k)
+        if (k > 0) vg_pack::preint_from_abi(*it->second.pre_integration, o.records[k - 1]);
+    if (align_status != VG_ALIGN_OK) return false;
+    // change state (:376-384, :400-415, :424-435)
+    for (int i = 0; i <= frame_count; i++) {
+        all_image_frame[Headers[i]].is_key_frame = true;
+        Ps[i] = Vector3d(o.Ps[3 * i], o.Ps[3 * i + 1], o.Ps[3 * i + 2]);
+        Vs[i] = Vector3d(o.Vs[3 * i], o.Vs[3 * i + 1], o.Vs[3 * i + 2]);
+        for (int e = 0; e < 9; ++e) Rs[i](e / 3, e % 3) = o.Rs[9 * i + e];
+    }
+    for (int i = 0; i <= WINDOW_SIZE; i++) {                     // pre_integrations[i]->repropagate(Vector3d::Zero(), Bgs[i]) (:400-403)
+        if (!pre_integrations[i]) continue;
+        pre_integrations[i]->linearized_ba = Vector3d();
+        pre_integrations[i]->linearized_bg = Bgs[i];
+        repropagate(pre_integrations[i]);
+    }
+    g = Vector3d(o.out.g_w[0], o.out.g_w[1], o.out.g_w[2]);
+    // clearDepth(-1); triangulate(Ps = the SfM camera positions, tic = 0, RIC) (:386-397); estimated_depth *= s (:416-422)
+    std::vector<double> cam_P, cam_R, points, depth;
+    std::vector<int> start, nobs, obs_off;
+    for (int i = 0; i <= frame_count; i++) {
+        const ImageFrame& fr = all_image_frame[Headers[i]];
+        for (int e = 0; e < 3; ++e) cam_P.push_back(fr.T(e));
+        for (int e = 0; e < 9; ++e) cam_R.push_back(fr.R(e / 3, e % 3));
+    }
+    for (auto& it : f_manager.feature) {
+        it.used_num = it.feature_per_frame.size();
+        if (!(it.used_num >= 2 && it.start_frame < WINDOW_SIZE - 2)) continue;
+        it.estimated_depth = -1;
+        start.push_back(it.start_frame); nobs.push_back((int)it.feature_per_frame.size()); obs_off.push_back((int)points.size() / 3);
+        for (auto& f : it.feature_per_frame)
+            for (int e = 0; e < 3; ++e) points.push_back(f.point(e));
+    }
+    const int L = (int)start.size();
+    if (L > 0) {
+        const double tic0[3] = {0, 0, 0};
+        double ric0[9];
+        for (int e = 0; e < 9; ++e) ric0[e] = ric[0](e / 3, e % 3);
+        depth.resize(L);
+        if (vg_triangulate(vg_, K, cam_P.data(), cam_R.data(), tic0, ric0, L, start.data(), nobs.data(), obs_off.data(), points.data(), INIT_DEPTH, depth.data()) != VG_OK)
+            throw std::runtime_error(std::string("vg_triangulate: ") + vg_last_error(vg_));
+        int l = 0;
+        for (auto& it : f_manager.feature) {
+            if (!(it.used_num >= 2 && it.start_frame < WINDOW_SIZE - 2)) continue;
+            it.estimated_depth = depth[l++] * o.out.s;
+        }
+    }
+    return true;
+}
+
 void Estimator::slideWindow() {
     // estimator.cpp:1005-1126 for frame_count == WINDOW_SIZE and solver_flag == NON_LINEAR; all_image_frame belongs to the
     // initialiser and is not mirrored here.  Ownership as in the reference: the IntegrationBase that ends up in slot

@@ -5,6 +5,7 @@
 // unchanged around this method in a real catkin build.
 #pragma once
 #include <list>
+#include <map>
 #include <string>
 #include <vector>
 #include "compat/eigen_compat.h"
@@ -67,6 +68,13 @@ struct MarginalizationInfo {       // the members MarginalizationFactor reads (m
     Eigen::VectorXd linearized_residuals;   // n
 };
 
+struct ImageFrame {                // initial/initial_alignment.h:14-28: what VisualIMUAlignment and visualInitialAlign read
+    Matrix3d R;                    // body rotation in the SfM frame c0
+    Vector3d T;                    // camera position in c0, unscaled
+    IntegrationBase* pre_integration = nullptr;      // the interval that ends at this frame (with its raw samples)
+    bool is_key_frame = false;
+};
+
 class Estimator {
   public:
     enum MarginalizationFlag { MARGIN_OLD = 0, MARGIN_SECOND_NEW = 1 };
@@ -79,6 +87,16 @@ class Estimator {
     void slideWindow();            // estimator.cpp:1005-1126 (state / pre-integration shift + slideWindowOld / slideWindowNew)
     // IntegrationBase::repropagate (integration_base.h:38-52) on the device: integrates p's raw samples with its linearized biases
     void repropagate(IntegrationBase* p);
+    // estimator.cpp:364-440 on the device: VisualIMUAlignment and the state change in one vg_init_align call over all_image_frame,
+    // then triangulate with a zero tic (vg_triangulate) and the depth scaling.  Reads Headers[0 .. frame_count], Bas[0], Bgs[0],
+    // tic[0] / ric[0] (the caller's copies of TIC[0] / RIC[0]), G_NORM and the noise densities; on success writes Ps / Rs / Vs
+    // [0 .. frame_count], Bgs, g, the records of all_image_frame and of pre_integrations, the landmarks' estimated_depth.
+    bool visualInitialAlign();
+    map<double, ImageFrame> all_image_frame;         // estimator.h:101
+    double Headers[(WINDOW_SIZE + 1)];               // Headers[i].stamp.toSec()
+    int frame_count = 0;
+    Vector3d g;
+    int align_status = 0;                            // VG_ALIGN_* of the last visualInitialAlign()
 
     MarginalizationFlag marginalization_flag = MARGIN_OLD;
     Vector3d Ps[(WINDOW_SIZE + 1)], Vs[(WINDOW_SIZE + 1)], Bas[(WINDOW_SIZE + 1)], Bgs[(WINDOW_SIZE + 1)];

@@ -28,6 +28,10 @@
 //     map of processImage): `seq` for one estimator whose tracks are NOT in the file (window.bin holds states and IMU samples only,
 //     L = 0 and n = 0) but come from FeatureTracker::readImage over frames.bin -- the first WINDOW_SIZE frames fill the window that
 //     is handed over, every further frame is one processImage + solve.  tests/e2e_vio.py renders the frames.
+//
+//   vins_replay align <in.bin> <out.txt>
+//     Estimator::visualInitialAlign() (vg_init_align, vg_triangulate with a zero tic, the depth scaling) over one all_image_frame map
+//     from a file; writes the status, Bgs[0], g, the window's Ps / Rs / Vs and the landmarks' depths (replay_align below).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -252,6 +256,88 @@ static int replay_ba(const char* in, const char* out) {
     fclose(o);
     fclose(rd.f);
     vg_destroy(h);
+    return 0;
+}
+
+// vins_replay align <in.bin> <out.txt>: Estimator::visualInitialAlign() over one all_image_frame map from a file
+// (tests/init_align_ref.write_replay): int32 'VAL1', F, K, L; doubles ba0 3, bg0 3, noise 4, tic 3, ric 9, g_norm, init_depth; per
+// frame stamp, R 9 (row-major), T 3; per interval int32 n, then acc_0 gyr_0 and n rows dt acc gyr; K int32 frame indices of the
+// window; per landmark int32 start_frame, n_obs and n_obs points x y z.  Writes the return value and the VG_ALIGN_* status, Bgs[0], g,
+// per window frame P, R, V, and every landmark's estimated_depth, all with 17 digits.
+static int replay_align(const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("align file"); return 2; }
+    int hdr[4];
+    rd.i(hdr, 4);
+    if (hdr[0] != 0x314C4156) { fprintf(stderr, "not a VAL1 file\n"); return 2; }
+    const int F = hdr[1], K = hdr[2], L = hdr[3];
+    if (K < 2 || K > WINDOW_SIZE + 1 || F < K) { fprintf(stderr, "K = %d, F = %d: the Estimator holds 2 .. %d window frames\n", K, F, WINDOW_SIZE + 1); return 2; }
+    double b[6], noise[4], ex[12], par[2];
+    rd.d(b, 6); rd.d(noise, 4); rd.d(ex, 12); rd.d(par, 2);
+    ACC_N = noise[0]; GYR_N = noise[1]; ACC_W = noise[2]; GYR_W = noise[3]; G_NORM = par[0]; INIT_DEPTH = par[1];
+    Estimator est;
+    est.tic[0] = Vector3d(ex[0], ex[1], ex[2]);
+    for (int e = 0; e < 9; ++e) est.ric[0](e / 3, e % 3) = ex[3 + e];
+    for (int i = 0; i <= WINDOW_SIZE; ++i) { est.Bas[i] = Vector3d(b[0], b[1], b[2]); est.Bgs[i] = Vector3d(b[3], b[4], b[5]); }
+    std::vector<double> stamp(F);
+    std::vector<std::unique_ptr<IntegrationBase>> owned;
+    for (int k = 0; k < F; ++k) {
+        double fr[13];
+        rd.d(fr, 13);
+        stamp[k] = fr[0];
+        ImageFrame& f = est.all_image_frame[fr[0]];
+        for (int e = 0; e < 9; ++e) f.R(e / 3, e % 3) = fr[1 + e];
+        f.T = Vector3d(fr[10], fr[11], fr[12]);
+    }
+    for (int k = 1; k < F; ++k) {
+        int n;
+        double first[6];
+        rd.i(&n, 1); rd.d(first, 6);
+        std::vector<double> smp((size_t)n * 7);
+        rd.d(smp.data(), n * 7);
+        owned.emplace_back(new IntegrationBase());
+        IntegrationBase* p = owned.back().get();
+        p->linearized_acc = Vector3d(first[0], first[1], first[2]);
+        p->linearized_gyr = Vector3d(first[3], first[4], first[5]);
+        for (int i = 0; i < n; ++i) {
+            p->dt_buf.push_back(smp[7 * i]);
+            p->acc_buf.push_back(Vector3d(smp[7 * i + 1], smp[7 * i + 2], smp[7 * i + 3]));
+            p->gyr_buf.push_back(Vector3d(smp[7 * i + 4], smp[7 * i + 5], smp[7 * i + 6]));
+        }
+        est.all_image_frame[stamp[k]].pre_integration = p;
+    }
+    std::vector<int> key(K);
+    rd.i(key.data(), K);
+    est.frame_count = K - 1;
+    for (int i = 0; i < K; ++i) est.Headers[i] = stamp[key[i]];
+    for (int l = 0; l < L; ++l) {
+        int meta[2];
+        rd.i(meta, 2);
+        FeaturePerId f;
+        f.feature_id = l; f.start_frame = meta[0];
+        for (int k = 0; k < meta[1]; ++k) {
+            double r[3];
+            rd.d(r, 3);
+            FeaturePerFrame fr;
+            fr.point = Vector3d(r[0], r[1], r[2]);
+            f.feature_per_frame.push_back(fr);
+        }
+        est.f_manager.feature.push_back(f);
+    }
+    fclose(rd.f);
+    const bool ok = est.visualInitialAlign();
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    fprintf(o, "result %d %d\n", ok ? 1 : 0, est.align_status);
+    fprintf(o, "bg %.17g %.17g %.17g\n", est.Bgs[0].x(), est.Bgs[0].y(), est.Bgs[0].z());
+    fprintf(o, "g %.17g %.17g %.17g\n", est.g.x(), est.g.y(), est.g.z());
+    for (int i = 0; ok && i < K; ++i) {
+        fprintf(o, "frame %.17g %.17g %.17g", est.Ps[i].x(), est.Ps[i].y(), est.Ps[i].z());
+        for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", est.Rs[i](e / 3, e % 3));
+        fprintf(o, " %.17g %.17g %.17g\n", est.Vs[i].x(), est.Vs[i].y(), est.Vs[i].z());
+    }
+    for (auto& f : est.f_manager.feature) fprintf(o, "depth %.17g\n", f.estimated_depth);
+    fclose(o);
     return 0;
 }
 
@@ -536,6 +622,10 @@ int main(int argc, char** argv) {
         try { return replay_seq(argv[2], argv[4], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay vio: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv>\n");
+    if (argc >= 4 && !strcmp(argv[1], "align")) {
+        try { return replay_align(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay align: %s\n", e.what()); return 1; }
+    }
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt>\n");
     return 2;
 }

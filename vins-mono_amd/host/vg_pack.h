@@ -179,6 +179,69 @@ template <class E> void install_prior(E& e, const vg_ba_prior& pr, int m) {
     e.last_marginalization_parameter_blocks = blocks;
 }
 
+// ---- initialisation: VisualIMUAlignment + the state change of visualInitialAlign (vg_init_align)
+// all_image_frame -> vg_align_in.  Map: std::map<double, ImageFrame> of either set of types (second.R / second.T / second.pre_integration
+// with dt_buf / acc_buf / gyr_buf / linearized_acc / linearized_gyr); interval k is the pre_integration of frame k + 1.  stamps: the
+// n_stamps key frames of the window (Headers[0 .. frame_count].stamp.toSec()), 0 for none; each must be a key of the map.  `p` owns
+// what p.in points to.
+struct AlignIn {
+    std::vector<double> R, T, samples, first;
+    std::vector<int> off, key;
+    vg_align_in in;
+};
+template <class Map, class V3>
+void pack_align(const Map& frames, const double* stamps, int n_stamps, const V3& ba0, const V3& bg0, const double* noise, const V3& tic, double g_norm, AlignIn& p) {
+    const int F = (int)frames.size();
+    p.R.clear(); p.T.clear(); p.samples.clear(); p.first.clear(); p.off.assign(1, 0); p.key.clear();
+    int k = 0;
+    for (auto it = frames.begin(); it != frames.end(); ++it, ++k) {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) p.R.push_back(it->second.R(r, c));
+        for (int r = 0; r < 3; ++r) p.T.push_back(it->second.T(r));
+        if (k == 0) continue;
+        const auto* pre = it->second.pre_integration;
+        if (!pre) throw std::runtime_error("pack_align: an ImageFrame behind the first has no pre_integration");
+        for (int r = 0; r < 3; ++r) p.first.push_back(pre->linearized_acc(r));
+        for (int r = 0; r < 3; ++r) p.first.push_back(pre->linearized_gyr(r));
+        for (size_t i = 0; i < pre->dt_buf.size(); ++i) {
+            p.samples.push_back(pre->dt_buf[i]);
+            for (int r = 0; r < 3; ++r) p.samples.push_back(pre->acc_buf[i](r));
+            for (int r = 0; r < 3; ++r) p.samples.push_back(pre->gyr_buf[i](r));
+        }
+        p.off.push_back((int)(p.samples.size() / 7));              // F entries: sample_off[k + 1] ends interval k
+    }
+    for (int i = 0; i < n_stamps; ++i) {
+        const auto it = frames.find(stamps[i]);
+        if (it == frames.end()) throw std::runtime_error("pack_align: a window stamp is not in all_image_frame");
+        int pos = 0;
+        for (auto jt = frames.begin(); jt != it; ++jt) ++pos;
+        p.key.push_back(pos);
+    }
+    if (p.samples.empty()) p.samples.assign(7, 0.0);
+    std::memset(&p.in, 0, sizeof(p.in));
+    p.in.struct_size = sizeof(p.in);
+    p.in.n_frames = F;
+    p.in.R = p.R.data(); p.in.T = p.T.data(); p.in.sample_off = p.off.data(); p.in.samples = p.samples.data(); p.in.first = p.first.data();
+    for (int r = 0; r < 3; ++r) { p.in.ba0[r] = ba0(r); p.in.bg0[r] = bg0(r); p.in.tic[r] = tic(r); }
+    for (int r = 0; r < 4; ++r) p.in.noise[r] = noise[r];
+    p.in.g_norm = g_norm;
+    p.in.n_key = n_stamps; p.in.key = p.key.data();
+}
+// the download buffers of one window with F frames, K of them in the window; `out` is the view
+struct AlignOut {
+    std::vector<double> v_body, Ps, Rs, Vs;
+    std::vector<vg_imu_preint> records;
+    vg_align_out out;
+    AlignOut(int F, int K) : v_body(3 * (size_t)F), Ps(3 * (size_t)K), Rs(9 * (size_t)K), Vs(3 * (size_t)K), records(F > 1 ? F - 1 : 1) {
+        std::memset(&out, 0, sizeof(out));
+        out.struct_size = sizeof(out);
+        out.v_body = v_body.data(); out.records = records.data();
+        if (K > 0) { out.Ps = Ps.data(); out.Rs = Rs.data(); out.Vs = Vs.data(); }
+    }
+    AlignOut(const AlignOut&) = delete;
+    AlignOut& operator=(const AlignOut&) = delete;
+};
+
 // ================================================================================================================== front end
 
 // reduceVector (feature_tracker.cpp:13-29) for any element type
@@ -336,3 +399,9 @@ template <class T> void take_setmask_result(T& t, const typename OrderCtx<T>::So
 }
 
 }  // namespace vg_pack
+
+// (the packer of vg_init_align under the name the integration guide uses)
+template <class Map, class V3>
+void vg_pack_align(const Map& frames, const double* stamps, int n_stamps, const V3& ba0, const V3& bg0, const double* noise, const V3& tic, double g_norm, vg_pack::AlignIn& p) {
+    vg_pack::pack_align(frames, stamps, n_stamps, ba0, bg0, noise, tic, g_norm, p);
+}
