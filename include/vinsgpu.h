@@ -31,7 +31,7 @@ extern "C" {
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
-                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align) */
+                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -181,6 +181,113 @@ typedef struct {
 } vg_align_out;
 
 int vg_init_align(vg_handle* h, int n_windows, const vg_align_in* in, vg_align_out* out);
+
+/* ---- Initialisation: global SfM and the per-frame PnP, batched (added within ABI 12, nothing existing changed) -------------------------
+ * The part of Estimator::initialStructure between relativePose() and visualInitialAlign() (estimator.cpp:250-353, initial/initial_sfm.cpp,
+ * ReprojectionError3D of initial/initial_sfm.h:25-54) for n_windows independent windows in one synchronous call: one upload, two launches
+ * (one workgroup per window: GlobalSFM::construct with its full BA; then one workgroup per non-key frame: its PnP), one download, FP64.
+ * R_all / T_all are ImageFrame::R / T, the inputs of vg_align_in::R / T.  relativePose / solveRelativeRT, InitialEXRotation and the
+ * IMU-excitation check of :222-248 (which has no effect in the reference) are NOT part of it: l, relative_R, relative_T are inputs.
+ *
+ * construct, statement by statement:
+ *   - q[l] = identity, T[l] = 0, q[F-1] = q[l] * Quaterniond(relative_R) (Eigen's matrix-to-quaternion conversion), T[F-1] = relative_T;
+ *     c_Quat = q.inverse() (conjugate over squared norm), c_Rotation = toRotationMatrix, c_Translation = -(c_Rotation T);
+ *   - stages 1 to 5 in the reference's order (:158-217): for i = l .. F-2: (i > l: PnP of i from the pose of i-1) then
+ *     triangulateTwoFrames(i, F-1); for i = l+1 .. F-2: triangulateTwoFrames(l, i); for i = l-1 .. 0: PnP of i from i+1, then
+ *     triangulateTwoFrames(i, l); last, every feature still without a position and with two observations or more from its first and its
+ *     LAST observation.  triangulateTwoFrames touches only features whose state is false and makes no depth or cheirality test.  A feature
+ *     with one observation is never triangulated: it stays out of the BA and out of sfm_tracked_points (state 0);
+ *   - triangulatePoint: the right singular vector of the 4x4 design matrix for the smallest singular value (one-sided Jacobi SVD, as
+ *     vg_triangulate), divided by its last component;
+ *   - solveFrameByPnP: the points are the features with state 1 seen in the frame, in feature order; fewer than 10 give
+ *     VG_SFM_FAILED_PNP (:45-50).  The 2-D and 3-D inputs are ROUNDED TO FLOAT32 (cv::Point2f / Point3f) and then used in double.
+ * cv::solvePnP(..., useExtrinsicGuess = 1, SOLVEPNP_ITERATIVE) is third-party and unpinned; this is its definition here (OpenCV 3.3.1's
+ * guess branch of cvFindExtrinsicCameraParams2, restated): CvLevMarq over (rvec, t), at most 20 iterations; lambda = 10^k, k starting
+ * at -3; normal equations JtJ, JtErr over all points with the diagonal of JtJ multiplied by 1 + lambda; param = prevParam - solution; when
+ * the error norm grew: k + 1 and, while k <= 16, a re-solve from the same JtJ (counted in pnp_up); else, and past the cap, the step is
+ * kept and k - 1 (floor -16); stop when |param - prevParam| / (|prevParam| + DBL_EPSILON) < FLT_EPSILON; the residual is projected minus
+ * observed with K = I and no distortion, the Jacobian the exact derivative through Rodrigues; the result is always "success".
+ * The full BA is Ceres' TrustRegionMinimizer with the LEVENBERG_MARQUARDT strategy at the defaults the reference leaves in place: at most
+ * 50 iterations (accepted, rejected and invalid ones counted); gradient tolerance 1e-10 on the max-norm of the unscaled gradient in the
+ * tangent space, checked at the start and after every accepted step; parameter tolerance |dx| <= 1e-8 (|x| + 1e-8) and function tolerance
+ * |cost - candidate| <= 1e-6 cost, checked in this order BEFORE the step is judged (the point stays where it was, as in the dogleg
+ * restatement of vg_ba_optimize); radius 1e4 at first, at most 1e16, below 1e-32 after a rejected step ends with CONVERGENCE; a step is
+ * accepted when (cost - candidate) / model change > 1e-3 (monotonic); LM diagonal D = sqrt(clamp(diag(JtJ), 1e-6, 1e32) / radius) of the
+ * Jacobi-scaled Jacobian (scale 1 / (1 + column norm) from the FIRST Jacobian), D * D added to the diagonal; radius / max(1/3, 1 - (2 rho -
+ * 1)^3) on success; / decrease_factor (2 at first and after every success, doubling) on a rejected or invalid step; 5 invalid steps in a
+ * row (a point block or the reduced system not positive definite, a model change that is not positive) end with FAILURE.  Blocks: a
+ * 4-parameter quaternion (w x y z) with QuaternionParameterization (Plus = [cos|d|, sin|d| / |d| d] * q), a translation per frame, 3 per
+ * triangulated feature; constant: the rotation of l, the translations of l and F-1 (x and |x| leave them out).  One ReprojectionError3D
+ * per observation of every triangulated feature; QuaternionRotatePoint normalises the quaternion inside the cost, the Jacobian is what
+ * auto-diff gives times the 4x3 plus-Jacobian.  The points are eliminated first (DENSE_SCHUR), the reduced camera system (6 F - 9) by
+ * Cholesky.  VG_SFM_FAILED_BA: not CONVERGENCE and final_cost >= 5e-3 (:281-289).  Afterwards q[i] = inverse(), T[i] = -(q[i] * c_t).
+ * Frames: a key entry gets R = Q[i] ric^T, T = T[i]; a non-key entry starts from Q[g]^-1, -R T[g] (g = all_guess), takes the ids of its
+ * map found among the features with state 1, in the map's order (fewer than 6: VG_SFM_FAILED_FRAME, :333), and gets R = R_pnp^T ric^T,
+ * T = -R_pnp^T t.
+ * Deviations:
+ *   - max_solver_time_in_seconds = 0.2 is NOT enforced (as SOLVER_TIME for vg_ba_optimize: a wall-clock cap is not reproducible);
+ *   - a triangulated coordinate that is not finite (division by w = 0) gives VG_SFM_NUMERIC where the reference goes on with it;
+ *   - Rodrigues in both directions is the regular branch (theta < DBL_EPSILON included), without OpenCV's SVD re-orthogonalisation of the
+ *     matrix; the near-pi branch (sin part below 1e-5 with a trace part that is not positive) gives VG_SFM_NUMERIC;
+ *   - the 6x6 solve of a PnP step is an unpivoted LDL^T where OpenCV takes an SVD solve: a pivot that is not positive and finite, or an
+ *     error norm that is not finite, gives VG_SFM_NUMERIC;
+ *   - every non-key entry is solved on its own: an entry behind a failed one is still returned; the status is that of the FIRST failed
+ *     entry in stamp order (the reference returns at it).
+ * What a status leaves uncomputed comes back as zeros: FAILED_PNP / NUMERIC inside construct return pnp_iters / pnp_up of the frames done
+ * and nothing else; FAILED_BA returns the taps, state[] and the BA trace; FAILED_FRAME / NUMERIC of a frame return everything but that
+ * entry's R_all / T_all.  A window's status never touches its neighbours; a batch equals the single calls bit for bit.
+ * Refused with VG_ERR_BAD_ARG before anything is uploaded (vg_last_error names the cause; no output is touched, the handle stays usable): a
+ * wrong struct_size, F outside 3 .. VG_SFM_MAX_FRAMES, l outside [0, F-2], n_feat outside 1 .. VG_SFM_MAX_FEATURES, a NULL table, start +
+ * nobs > F or nobs < 1, obs_off not ascending (rows that overlap), duplicate feature_id, all_key not ascending over its non-negative
+ * entries or not covering 0 .. F-1 exactly once when n_all > 0, all_guess outside [0, F), all_off not ascending, a non-finite input. */
+enum { VG_SFM_OK = 0, VG_SFM_FAILED_PNP = 1, VG_SFM_FAILED_BA = 2, VG_SFM_FAILED_FRAME = 3, VG_SFM_NUMERIC = 4 };
+#define VG_SFM_MAX_FRAMES 16     /* the reduced camera system of 6 F - 9 unknowns sits in LDS beside the per-feature blocks */
+#define VG_SFM_MAX_FEATURES 1024 /* 15 doubles of LDS per feature: csrc/init_sfm_carve.h */
+#define VG_SFM_MAX_ITERS 50      /* Ceres' max_num_iterations default */
+
+typedef struct {                 /* one window: f_manager.feature and all_image_frame at the time of initialStructure() */
+    size_t struct_size;          /* sizeof(vg_sfm_in) */
+    int n_frames;                /* F = frame_count + 1, 3 .. VG_SFM_MAX_FRAMES (the reference runs 11) */
+    int l;                       /* the reference frame relativePose() chose, 0 .. F-2 */
+    double relative_R[9];        /* row-major */
+    double relative_T[3];
+    double ric[9];               /* RIC[0], row-major */
+    int n_feat;                  /* 1 .. VG_SFM_MAX_FEATURES */
+    const int* feature_id;       /* [n_feat] distinct */
+    const int* start;            /* [n_feat] the layout of vg_triangulate: feature j is seen in frames start[j] .. start[j] + nobs[j] - 1 */
+    const int* nobs;
+    const int* obs_off;          /* [n_feat] ascending: the feature's first row of points */
+    const double* points;        /* x y z rows (feature_per_frame.point; x and y are used) */
+    int n_all;                   /* entries of all_image_frame in stamp order; 0: construct only */
+    const int* all_key;          /* [n_all] the index i of the key frame (Headers[i]) this entry IS, or -1 */
+    const int* all_guess;        /* [n_all] for a non-key entry: the i whose pose is its guess (the walk of estimator.cpp:290-306) */
+    const int* all_off;          /* [n_all + 1] a non-key entry's map is rows all_off[a] .. all_off[a + 1] - 1 of all_id / all_xy */
+    const int* all_id;           /* feature ids, ascending inside an entry (the order of the frame's points map) */
+    const double* all_xy;        /* x y of camera 0 */
+} vg_sfm_in;
+
+typedef struct {                 /* every pointer may be NULL */
+    size_t struct_size;          /* sizeof(vg_sfm_out), set by the caller */
+    int status;                  /* VG_SFM_* */
+    double* q;                   /* [F][4] (w x y z) Q after construct */
+    double* T;                   /* [F][3] */
+    int* state;                  /* [n_feat] sfm_f[j].state: the set bits are sfm_tracked_points */
+    double* position;            /* [n_feat][3] sfm_f[j].position after the BA (zeros where state is 0) */
+    double* R_all;               /* [n_all][9] ImageFrame::R */
+    double* T_all;               /* [n_all][3] ImageFrame::T */
+    int* is_key;                 /* [n_all] ImageFrame::is_key_frame */
+    /* taps for the tests */
+    double *q0, *T0;             /* [F][4] [F][3] c_Quat, c_Translation right before the full BA */
+    double* position0;           /* [n_feat][3] the triangulated positions right before the full BA */
+    int *pnp_iters, *pnp_up;     /* [F] iterations, and lambda increases, of each chain PnP (0 for l and F-1) */
+    int ba_iters, ba_termination;/* VG_TERM_* */
+    double final_cost;
+    double it_cost[VG_SFM_MAX_ITERS], it_cost_cand[VG_SFM_MAX_ITERS], it_model[VG_SFM_MAX_ITERS], it_radius[VG_SFM_MAX_ITERS];
+    int it_flags[VG_SFM_MAX_ITERS];      /* the trace of vg_ba_summary: bit0 valid, bit1 accepted */
+    double* device_ms;           /* read on out[0] only: [2] device time of the two launches from events, or NULL (no events) */
+} vg_sfm_out;
+
+int vg_init_sfm(vg_handle* h, int n_windows, const vg_sfm_in* in, vg_sfm_out* out);
 
 /* block kinds of the marginalization prior (MarginalizationInfo::keep_block_*) */
 enum { VG_BLK_POSE = 0, VG_BLK_SPEEDBIAS = 1, VG_BLK_EXPOSE = 2, VG_BLK_TD = 3 };

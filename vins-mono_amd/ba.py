@@ -107,6 +107,23 @@ class AlignOut(C.Structure):          # vg_align_out
                 ("records", C.POINTER(ImuPreint)), ("Ps", _pd), ("Rs", _pd), ("Vs", _pd), ("g_w", C.c_double * 3), ("R0", C.c_double * 9)]
 
 
+SFM_MAX_ITERS = 50                   # VG_SFM_MAX_ITERS
+
+
+class SfmIn(C.Structure):             # vg_sfm_in
+    _fields_ = [("struct_size", C.c_size_t), ("n_frames", C.c_int), ("l", C.c_int), ("relative_R", C.c_double * 9), ("relative_T", C.c_double * 3),
+                ("ric", C.c_double * 9), ("n_feat", C.c_int), ("feature_id", _pi), ("start", _pi), ("nobs", _pi), ("obs_off", _pi), ("points", _pd),
+                ("n_all", C.c_int), ("all_key", _pi), ("all_guess", _pi), ("all_off", _pi), ("all_id", _pi), ("all_xy", _pd)]
+
+
+class SfmOut(C.Structure):            # vg_sfm_out
+    _fields_ = [("struct_size", C.c_size_t), ("status", C.c_int), ("q", _pd), ("T", _pd), ("state", _pi), ("position", _pd), ("R_all", _pd),
+                ("T_all", _pd), ("is_key", _pi), ("q0", _pd), ("T0", _pd), ("position0", _pd), ("pnp_iters", _pi), ("pnp_up", _pi),
+                ("ba_iters", C.c_int), ("ba_termination", C.c_int), ("final_cost", C.c_double), ("it_cost", C.c_double * SFM_MAX_ITERS),
+                ("it_cost_cand", C.c_double * SFM_MAX_ITERS), ("it_model", C.c_double * SFM_MAX_ITERS), ("it_radius", C.c_double * SFM_MAX_ITERS),
+                ("it_flags", C.c_int * SFM_MAX_ITERS), ("device_ms", _pd)]
+
+
 SEQ_INFO = ("flag", "n_features", "n_tracked", "n_parallax", "n_landmarks", "n_factors", "status", "n_after")
 
 
@@ -322,6 +339,8 @@ class Handle:
             L.vg_ba_seq_get_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloResult)]
         if hasattr(L, "vg_init_align"):                   # (added within ABI 12)
             L.vg_init_align.argtypes = [C.c_void_p, C.c_int, C.POINTER(AlignIn), C.POINTER(AlignOut)]
+        if hasattr(L, "vg_init_sfm"):                     # (added within ABI 12)
+            L.vg_init_sfm.argtypes = [C.c_void_p, C.c_int, C.POINTER(SfmIn), C.POINTER(SfmOut)]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -859,6 +878,70 @@ class Handle:
             res.append(dict(status=int(o.status), delta_bg=np.array(o.delta_bg), bg=np.array(o.bg), g_lin=np.array(o.g_lin), s_lin=float(o.s_lin),
                             g_c0=np.array(o.g_c0), s=float(o.s), v_body=b['v_body'], records=recs, Ps=b['Ps'], Rs=b['Rs'], Vs=b['Vs'],
                             g_w=np.array(o.g_w), R0=np.array(o.R0).reshape(3, 3)))
+        return res
+
+    @staticmethod
+    def init_sfm_pack(windows, timed=False):
+        """(vg_sfm_in array, vg_sfm_out array, the NumPy arrays both point into) for init_sfm's window dicts"""
+        n = len(windows)
+        ins, outs, keep = (SfmIn * n)(), (SfmOut * n)(), []
+        i32 = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
+        for w, (a, o) in zip(windows, zip(ins, outs)):
+            F = int(w['n_frames'])
+            start, nobs, fid = i32(w['start']), i32(w['nobs']), i32(w['feature_id'])
+            nf = len(start)
+            off = i32(w['obs_off']) if w.get('obs_off') is not None else i32(np.concatenate([[0], np.cumsum(nobs)[:-1]]))
+            points = np.array(w['points'], np.float64).reshape(-1, 3)           # (copies: the call never aliases the caller's arrays)
+            all_key, all_guess = i32(w.get('all_key', [])), i32(w.get('all_guess', []))
+            na = len(all_key)
+            all_off, ids, xy = np.zeros(na + 1, np.int32), [], []
+            for e in range(na):
+                pts = w['all_pts'][e]
+                if all_key[e] < 0 and pts is not None:
+                    ids.extend(int(x) for x in pts[0])
+                    xy.extend(np.asarray(pts[1], np.float64).reshape(-1, 2).tolist())
+                all_off[e + 1] = len(ids)
+            ids, xy = i32(ids if ids else [0]), np.ascontiguousarray(xy if xy else np.zeros((1, 2)), np.float64)
+            bufs = dict(start=start, nobs=nobs, fid=fid, off=off, points=points, all_key=all_key, all_guess=all_guess, all_off=all_off, ids=ids, xy=xy,
+                        q=np.zeros((F, 4)), T=np.zeros((F, 3)), state=np.zeros(nf, np.int32), position=np.zeros((nf, 3)), R_all=np.zeros((na, 3, 3)),
+                        T_all=np.zeros((na, 3)), is_key=np.zeros(max(na, 1), np.int32), q0=np.zeros((F, 4)), T0=np.zeros((F, 3)), position0=np.zeros((nf, 3)),
+                        pnp_iters=np.zeros(F, np.int32), pnp_up=np.zeros(F, np.int32), device_ms=np.zeros(2))
+            keep.append(bufs)
+            a.struct_size, a.n_frames, a.l, a.n_feat, a.n_all = C.sizeof(SfmIn), F, int(w['l']), nf, na
+            a.relative_R[:] = [float(x) for x in np.asarray(w['relative_R']).reshape(-1)]
+            a.relative_T[:] = [float(x) for x in w['relative_T']]
+            a.ric[:] = [float(x) for x in np.asarray(w['ric']).reshape(-1)]
+            a.feature_id, a.start, a.nobs, a.obs_off, a.points = _ip(fid), _ip(start), _ip(nobs), _ip(off), _dp(points)
+            if na:
+                a.all_key, a.all_guess, a.all_off, a.all_id, a.all_xy = _ip(all_key), _ip(all_guess), _ip(all_off), _ip(ids), _dp(xy)
+            o.struct_size = C.sizeof(SfmOut)
+            o.q, o.T, o.state, o.position, o.q0, o.T0, o.position0 = (_dp(bufs['q']), _dp(bufs['T']), _ip(bufs['state']), _dp(bufs['position']),
+                                                                       _dp(bufs['q0']), _dp(bufs['T0']), _dp(bufs['position0']))
+            o.pnp_iters, o.pnp_up = _ip(bufs['pnp_iters']), _ip(bufs['pnp_up'])
+            if na:                                              # (n_all = 0: construct only, every all_* table and output stays NULL)
+                o.R_all, o.T_all, o.is_key = _dp(bufs['R_all']), _dp(bufs['T_all']), _ip(bufs['is_key'])
+            if timed:
+                o.device_ms = _dp(bufs['device_ms'])
+        return ins, outs, keep
+
+    def init_sfm(self, windows, timed=False):
+        """GlobalSFM::construct and the per-frame PnP of Estimator::initialStructure for a batch of windows (vg_init_sfm).  A window is a
+        dict: n_frames, l, relative_R [3][3], relative_T, ric [3][3], feature_id, start, nobs, points (x y z rows, feature after feature;
+        obs_off optional), all_key, all_guess, all_pts (per entry None or (ids ascending, xy)).  Returns one dict per window; with
+        timed, the first carries device_ms: the device time of the two launches."""
+        ins, outs, keep = self.init_sfm_pack(windows, timed)
+        self._chk(self.lib.vg_init_sfm(self.h, len(windows), ins, outs), "vg_init_sfm")
+        res = []
+        for o, b in zip(outs, keep):
+            it = int(o.ba_iters)
+            d = dict(status=int(o.status), ba_iters=it, ba_termination=int(o.ba_termination), final_cost=float(o.final_cost),
+                     it_cost=np.array(o.it_cost)[:it], it_cost_cand=np.array(o.it_cost_cand)[:it], it_model=np.array(o.it_model)[:it],
+                     it_radius=np.array(o.it_radius)[:it], it_flags=np.array(o.it_flags)[:it])
+            d.update({k: b[k] for k in ('q', 'T', 'state', 'position', 'R_all', 'T_all', 'q0', 'T0', 'position0', 'pnp_iters', 'pnp_up')})
+            d['is_key'] = b['is_key'][:len(b['all_key'])]
+            if timed:
+                d['device_ms'] = b['device_ms']
+            res.append(d)
         return res
 
     def triangulate(self, Ps, Rs, tic, ric, start, nobs, obs_off, points, init_depth=5.0):

@@ -129,6 +129,30 @@ void Estimator::repropagate(IntegrationBase* p) {
     vg_pack::preint_from_abi(*p, out);
 }
 
+bool Estimator::initialStructure(int l, const Matrix3d& relative_R, const Vector3d& relative_T) {      // estimator.cpp:250-362
+    if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
+    vg_pack::SfmIn in;
+    vg_pack_sfm(f_manager.feature, all_image_frame, Headers, frame_count + 1, l, relative_R, relative_T, ric[0], in);
+    vg_pack::SfmOut o(frame_count + 1, in.in.n_feat, in.in.n_all);
+    if (vg_init_sfm(vg_, 1, &in.in, &o.out) != VG_OK) throw std::runtime_error(std::string("vg_init_sfm: ") + vg_last_error(vg_));
+    sfm_status = o.out.status;
+    // is_key is written only once construct has succeeded: FAILED_PNP, FAILED_BA and a NUMERIC inside construct leave it zero
+    bool constructed = false;
+    for (int a = 0; a < in.in.n_all; ++a) constructed = constructed || o.is_key[a] != 0;
+    if (!constructed) {                                         // "global SFM failed!" (:277-284)
+        marginalization_flag = MARGIN_OLD;
+        return false;
+    }
+    int a = 0;
+    for (auto it = all_image_frame.begin(); it != all_image_frame.end(); ++it, ++a) {      // :290-352
+        it->second.is_key_frame = o.is_key[a] != 0;
+        for (int e = 0; e < 9; ++e) it->second.R(e / 3, e % 3) = o.R_all[9 * a + e];
+        it->second.T = Vector3d(o.T_all[3 * a], o.T_all[3 * a + 1], o.T_all[3 * a + 2]);
+    }
+    if (sfm_status != VG_SFM_OK) return false;                  // a non-key frame with fewer than 6 points, or whose PnP failed (:333-343)
+    return visualInitialAlign();
+}
+
 bool Estimator::visualInitialAlign() {                          // estimator.cpp:364-440
     if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
     const double noise[4] = {ACC_N, GYR_N, ACC_W, GYR_W};

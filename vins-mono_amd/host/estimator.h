@@ -73,6 +73,9 @@ struct ImageFrame {                // initial/initial_alignment.h:14-28: what Vi
     Vector3d T;                    // camera position in c0, unscaled
     IntegrationBase* pre_integration = nullptr;      // the interval that ends at this frame (with its raw samples)
     bool is_key_frame = false;
+    // feature id -> (camera id, x y z u v vx vy): the frame's observations (initial_alignment.h:20); initialStructure reads x y of
+    // camera 0 for the PnP of a non-key frame
+    map<int, vector<pair<int, Eigen::Matrix<double, 7, 1>>>> points;
 };
 
 class Estimator {
@@ -92,6 +95,11 @@ class Estimator {
     // tic[0] / ric[0] (the caller's copies of TIC[0] / RIC[0]), G_NORM and the noise densities; on success writes Ps / Rs / Vs
     // [0 .. frame_count], Bgs, g, the records of all_image_frame and of pre_integrations, the landmarks' estimated_depth.
     bool visualInitialAlign();
+    // estimator.cpp:250-362 behind relativePose(), on the device: GlobalSFM::construct and the PnP of every non-key frame in one
+    // vg_init_sfm call over f_manager.feature and all_image_frame (l, relative_R, relative_T: what relativePose() returned), then
+    // ImageFrame::R / T / is_key_frame, then visualInitialAlign().  A construct failure sets marginalization_flag = MARGIN_OLD (:282).
+    bool initialStructure(int l, const Matrix3d& relative_R, const Vector3d& relative_T);
+    int sfm_status = 0;                              // VG_SFM_* of the last initialStructure()
     map<double, ImageFrame> all_image_frame;         // estimator.h:101
     double Headers[(WINDOW_SIZE + 1)];               // Headers[i].stamp.toSec()
     int frame_count = 0;

@@ -32,6 +32,10 @@
 //   vins_replay align <in.bin> <out.txt>
 //     Estimator::visualInitialAlign() (vg_init_align, vg_triangulate with a zero tic, the depth scaling) over one all_image_frame map
 //     from a file; writes the status, Bgs[0], g, the window's Ps / Rs / Vs and the landmarks' depths (replay_align below).
+//
+//   vins_replay sfm <in.bin> <out.txt>
+//     Estimator::initialStructure(l, relative_R, relative_T) (vg_init_sfm, then visualInitialAlign) over f_manager.feature and one
+//     all_image_frame map from a file; writes the statuses, every entry's is_key_frame / R / T and what `align` writes (replay_sfm below).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -341,6 +345,102 @@ static int replay_align(const char* in, const char* out) {
     return 0;
 }
 
+// vins_replay sfm <in.bin> <out.txt>: Estimator::initialStructure(l, relative_R, relative_T) over f_manager.feature and one
+// all_image_frame map from a file (tests/init_sfm_ref.write_replay): int32 'VSR1', A (entries of all_image_frame), K (window frames), L
+// (features), l; doubles ba0 3, bg0 3, noise 4, tic 3, ric 9, g_norm, init_depth, relative_R 9, relative_T 3; per entry its stamp, int32
+// n and n times (int32 id, double x y): its points map; per interval int32 n, then acc_0 gyr_0 and n rows dt acc gyr; K int32 entry
+// indices of the window; per feature int32 id, start_frame, n_obs and n_obs points x y z.  Writes the return value, the VG_SFM_* and
+// VG_ALIGN_* statuses and marginalization_flag, per entry is_key_frame, R, T, then what `align` writes, all with 17 digits.
+static int replay_sfm(const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("sfm file"); return 2; }
+    int hdr[5];
+    rd.i(hdr, 5);
+    if (hdr[0] != 0x31525356) { fprintf(stderr, "not a VSR1 file\n"); return 2; }
+    const int A = hdr[1], K = hdr[2], L = hdr[3], l = hdr[4];
+    if (K < 3 || K > WINDOW_SIZE + 1 || A < K) { fprintf(stderr, "K = %d, A = %d: the Estimator holds 3 .. %d window frames\n", K, A, WINDOW_SIZE + 1); return 2; }
+    double b[6], noise[4], ex[12], par[2], rel[12];
+    rd.d(b, 6); rd.d(noise, 4); rd.d(ex, 12); rd.d(par, 2); rd.d(rel, 12);
+    ACC_N = noise[0]; GYR_N = noise[1]; ACC_W = noise[2]; GYR_W = noise[3]; G_NORM = par[0]; INIT_DEPTH = par[1];
+    Estimator est;
+    est.tic[0] = Vector3d(ex[0], ex[1], ex[2]);
+    Matrix3d relative_R;
+    for (int e = 0; e < 9; ++e) { est.ric[0](e / 3, e % 3) = ex[3 + e]; relative_R(e / 3, e % 3) = rel[e]; }
+    const Vector3d relative_T(rel[9], rel[10], rel[11]);
+    for (int i = 0; i <= WINDOW_SIZE; ++i) { est.Bas[i] = Vector3d(b[0], b[1], b[2]); est.Bgs[i] = Vector3d(b[3], b[4], b[5]); }
+    std::vector<double> stamp(A);
+    std::vector<std::unique_ptr<IntegrationBase>> owned;
+    for (int k = 0; k < A; ++k) {
+        int n;
+        rd.d(&stamp[k], 1); rd.i(&n, 1);
+        ImageFrame& f = est.all_image_frame[stamp[k]];
+        for (int i = 0; i < n; ++i) {
+            int id;
+            double xy[2];
+            rd.i(&id, 1); rd.d(xy, 2);
+            Eigen::Matrix<double, 7, 1> m;
+            m(0, 0) = xy[0]; m(1, 0) = xy[1]; m(2, 0) = 1.0;
+            f.points[id].emplace_back(0, m);
+        }
+    }
+    for (int k = 1; k < A; ++k) {
+        int n;
+        double first[6];
+        rd.i(&n, 1); rd.d(first, 6);
+        std::vector<double> smp((size_t)n * 7);
+        rd.d(smp.data(), n * 7);
+        owned.emplace_back(new IntegrationBase());
+        IntegrationBase* p = owned.back().get();
+        p->linearized_acc = Vector3d(first[0], first[1], first[2]);
+        p->linearized_gyr = Vector3d(first[3], first[4], first[5]);
+        for (int i = 0; i < n; ++i) {
+            p->dt_buf.push_back(smp[7 * i]);
+            p->acc_buf.push_back(Vector3d(smp[7 * i + 1], smp[7 * i + 2], smp[7 * i + 3]));
+            p->gyr_buf.push_back(Vector3d(smp[7 * i + 4], smp[7 * i + 5], smp[7 * i + 6]));
+        }
+        est.all_image_frame[stamp[k]].pre_integration = p;
+    }
+    std::vector<int> key(K);
+    rd.i(key.data(), K);
+    est.frame_count = K - 1;
+    for (int i = 0; i < K; ++i) est.Headers[i] = stamp[key[i]];
+    for (int j = 0; j < L; ++j) {
+        int meta[3];
+        rd.i(meta, 3);
+        FeaturePerId f;
+        f.feature_id = meta[0]; f.start_frame = meta[1];
+        for (int k = 0; k < meta[2]; ++k) {
+            double r[3];
+            rd.d(r, 3);
+            FeaturePerFrame fr;
+            fr.point = Vector3d(r[0], r[1], r[2]);
+            f.feature_per_frame.push_back(fr);
+        }
+        est.f_manager.feature.push_back(f);
+    }
+    fclose(rd.f);
+    est.marginalization_flag = Estimator::MARGIN_SECOND_NEW;    // (so that the MARGIN_OLD of a construct failure shows)
+    const bool ok = est.initialStructure(l, relative_R, relative_T);
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    fprintf(o, "result %d %d %d %d\n", ok ? 1 : 0, est.sfm_status, est.align_status, (int)est.marginalization_flag);
+    for (auto& kv : est.all_image_frame) {
+        fprintf(o, "entry %d", kv.second.is_key_frame ? 1 : 0);
+        for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", kv.second.R(e / 3, e % 3));
+        fprintf(o, " %.17g %.17g %.17g\n", kv.second.T.x(), kv.second.T.y(), kv.second.T.z());
+    }
+    fprintf(o, "bg %.17g %.17g %.17g\n", est.Bgs[0].x(), est.Bgs[0].y(), est.Bgs[0].z());
+    fprintf(o, "g %.17g %.17g %.17g\n", est.g.x(), est.g.y(), est.g.z());
+    for (int i = 0; ok && i < K; ++i) {
+        fprintf(o, "frame %.17g %.17g %.17g", est.Ps[i].x(), est.Ps[i].y(), est.Ps[i].z());
+        for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", est.Rs[i](e / 3, e % 3));
+        fprintf(o, " %.17g %.17g %.17g\n", est.Vs[i].x(), est.Vs[i].y(), est.Vs[i].z());
+    }
+    for (auto& f : est.f_manager.feature) fprintf(o, "depth %.17g\n", f.estimated_depth);
+    fclose(o);
+    return 0;
+}
+
 namespace {
 // the front end of `vio`: one frame through readImage + updateID, returned as the `image` map (features seen at least twice)
 struct FrontEnd {
@@ -626,6 +726,10 @@ int main(int argc, char** argv) {
         try { return replay_align(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay align: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt>\n");
+    if (argc >= 4 && !strcmp(argv[1], "sfm")) {
+        try { return replay_sfm(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
+    }
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt>\n");
     return 2;
 }

@@ -242,6 +242,74 @@ struct AlignOut {
     AlignOut& operator=(const AlignOut&) = delete;
 };
 
+// ---- initialisation: GlobalSFM::construct + the per-frame PnP of initialStructure (vg_init_sfm)
+// f_manager.feature and all_image_frame -> vg_sfm_in.  Features: a list of FeaturePerId (feature_id, start_frame, feature_per_frame with
+// .point); Map: std::map<double, ImageFrame> whose entries carry `points` (id -> vector of (camera, x y z u v vx vy)); stamps: the
+// n_stamps key frames Headers[0 .. frame_count].stamp.toSec().  all_key / all_guess come from the walk of estimator.cpp:290-306: a
+// counter i over the stamps; an entry whose stamp equals stamps[i] IS key frame i (i moves on); any other entry moves i on once when
+// its stamp is past stamps[i], and takes the pose of i as its guess.  `p` owns what p.in points to.
+struct SfmIn {
+    std::vector<int> id, start, nobs, off, all_key, all_guess, all_off, all_id;
+    std::vector<double> points, all_xy;
+    vg_sfm_in in;
+};
+template <class Features, class Map, class M3, class V3>
+void pack_sfm(const Features& features, const Map& frames, const double* stamps, int n_stamps, int l, const M3& relative_R, const V3& relative_T,
+              const M3& ric, SfmIn& p) {
+    p.id.clear(); p.start.clear(); p.nobs.clear(); p.off.clear(); p.points.clear();
+    p.all_key.clear(); p.all_guess.clear(); p.all_off.assign(1, 0); p.all_id.clear(); p.all_xy.clear();
+    for (const auto& f : features) {
+        p.id.push_back(f.feature_id); p.start.push_back(f.start_frame); p.nobs.push_back((int)f.feature_per_frame.size());
+        p.off.push_back((int)(p.points.size() / 3));
+        for (const auto& o : f.feature_per_frame)
+            for (int r = 0; r < 3; ++r) p.points.push_back(o.point(r));
+    }
+    int i = 0;
+    for (auto it = frames.begin(); it != frames.end(); ++it) {
+        if (i < n_stamps && it->first == stamps[i]) {
+            p.all_key.push_back(i); p.all_guess.push_back(i);
+            ++i;
+        } else {
+            if (i < n_stamps && it->first > stamps[i]) ++i;
+            if (i >= n_stamps) throw std::runtime_error("pack_sfm: a frame of all_image_frame lies behind the last window stamp");
+            p.all_key.push_back(-1); p.all_guess.push_back(i);
+            for (const auto& id_pts : it->second.points) {                     // (a std::map: ascending ids)
+                if (id_pts.second.empty()) continue;
+                p.all_id.push_back(id_pts.first);
+                p.all_xy.push_back(id_pts.second[0].second(0, 0)); p.all_xy.push_back(id_pts.second[0].second(1, 0));
+            }
+        }
+        p.all_off.push_back((int)p.all_id.size());
+    }
+    if (p.all_id.empty()) { p.all_id.assign(1, 0); p.all_xy.assign(2, 0.0); }
+    std::memset(&p.in, 0, sizeof(p.in));
+    p.in.struct_size = sizeof(p.in);
+    p.in.n_frames = n_stamps; p.in.l = l;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) { p.in.relative_R[3 * r + c] = relative_R(r, c); p.in.ric[3 * r + c] = ric(r, c); }
+        p.in.relative_T[r] = relative_T(r);
+    }
+    p.in.n_feat = (int)p.id.size();
+    p.in.feature_id = p.id.data(); p.in.start = p.start.data(); p.in.nobs = p.nobs.data(); p.in.obs_off = p.off.data(); p.in.points = p.points.data();
+    p.in.n_all = (int)p.all_key.size();
+    p.in.all_key = p.all_key.data(); p.in.all_guess = p.all_guess.data(); p.in.all_off = p.all_off.data(); p.in.all_id = p.all_id.data();
+    p.in.all_xy = p.all_xy.data();
+}
+// the download buffers of one window with F key frames, n features and A entries of all_image_frame; `out` is the view
+struct SfmOut {
+    std::vector<double> q, T, position, R_all, T_all;
+    std::vector<int> state, is_key;
+    vg_sfm_out out;
+    SfmOut(int F, int n, int A) : q(4 * (size_t)F), T(3 * (size_t)F), position(3 * (size_t)n), R_all(9 * (size_t)A + 1), T_all(3 * (size_t)A + 1), state(n), is_key(A + 1) {
+        std::memset(&out, 0, sizeof(out));
+        out.struct_size = sizeof(out);
+        out.q = q.data(); out.T = T.data(); out.position = position.data(); out.state = state.data();
+        out.R_all = R_all.data(); out.T_all = T_all.data(); out.is_key = is_key.data();
+    }
+    SfmOut(const SfmOut&) = delete;
+    SfmOut& operator=(const SfmOut&) = delete;
+};
+
 // ================================================================================================================== front end
 
 // reduceVector (feature_tracker.cpp:13-29) for any element type
@@ -400,6 +468,12 @@ template <class T> void take_setmask_result(T& t, const typename OrderCtx<T>::So
 
 }  // namespace vg_pack
 
+// (the packer of vg_init_sfm under the name the integration guide uses)
+template <class Features, class Map, class M3, class V3>
+void vg_pack_sfm(const Features& features, const Map& frames, const double* stamps, int n_stamps, int l, const M3& relative_R, const V3& relative_T,
+                 const M3& ric, vg_pack::SfmIn& p) {
+    vg_pack::pack_sfm(features, frames, stamps, n_stamps, l, relative_R, relative_T, ric, p);
+}
 // (the packer of vg_init_align under the name the integration guide uses)
 template <class Map, class V3>
 void vg_pack_align(const Map& frames, const double* stamps, int n_stamps, const V3& ba0, const V3& bg0, const double* noise, const V3& tic, double g_norm, vg_pack::AlignIn& p) {
