@@ -31,7 +31,7 @@ extern "C" {
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
-                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm) */
+                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -186,8 +186,9 @@ int vg_init_align(vg_handle* h, int n_windows, const vg_align_in* in, vg_align_o
  * The part of Estimator::initialStructure between relativePose() and visualInitialAlign() (estimator.cpp:250-353, initial/initial_sfm.cpp,
  * ReprojectionError3D of initial/initial_sfm.h:25-54) for n_windows independent windows in one synchronous call: one upload, two launches
  * (one workgroup per window: GlobalSFM::construct with its full BA; then one workgroup per non-key frame: its PnP), one download, FP64.
- * R_all / T_all are ImageFrame::R / T, the inputs of vg_align_in::R / T.  relativePose / solveRelativeRT, InitialEXRotation and the
- * IMU-excitation check of :222-248 (which has no effect in the reference) are NOT part of it: l, relative_R, relative_T are inputs.
+ * R_all / T_all are ImageFrame::R / T, the inputs of vg_align_in::R / T.  l, relative_R, relative_T are inputs: relativePose / solveRelativeRT
+ * is vg_init_relpose (below), whose outputs they are.  InitialEXRotation and the IMU-excitation check of :222-248 (which has no effect in the
+ * reference) are NOT part of either call.
  *
  * construct, statement by statement:
  *   - q[l] = identity, T[l] = 0, q[F-1] = q[l] * Quaterniond(relative_R) (Eigen's matrix-to-quaternion conversion), T[F-1] = relative_T;
@@ -288,6 +289,110 @@ typedef struct {                 /* every pointer may be NULL */
 } vg_sfm_out;
 
 int vg_init_sfm(vg_handle* h, int n_windows, const vg_sfm_in* in, vg_sfm_out* out);
+
+/* ---- Initialisation: relativePose (RANSAC + recoverPose), batched (added within ABI 12, nothing existing changed) ----------------------
+ * Estimator::relativePose (estimator.cpp:442-471) for n_windows independent windows in one synchronous call: FeatureManager::
+ * getCorresponding (feature_manager.cpp:120), the parallax gate, MotionEstimator::solveRelativeRT (initial/solve_5pts.cpp:193-227) with the
+ * file's own recoverPose / decomposeEssentialMat (:4-190), over the candidate frames i = 0 .. F-2 against frame F-1.  The outputs l,
+ * relative_R, relative_T are the inputs of vg_sfm_in under the same names and layout, and the feature tables are those of vg_sfm_in: one
+ * packing serves both calls.  One upload, nine launches, one download on the ordinary path (a second small submission when a candidate
+ * needs the exact sample schedule, see 4).
+ *
+ * Statement by statement, quirks kept:
+ *   1. Correspondences.  Candidate i gets the features with start <= i and start + nobs - 1 >= F-1, in feature order, as pairs (point at
+ *      i, point at F-1); x and y of the rows are used.
+ *   2. Gate.  It passes when n_corres > min_corres (20) and average_parallax * focal (460) > parallax_gate (30), both strict.  The
+ *      parallax of a pair is sqrt(dx dx + dy dy) on the DOUBLE x, y; average_parallax = sum / n_corres.  The sum runs in ONE FIXED ORDER,
+ *      which is not the reference's left-to-right one: with d[k] the parallax of pair k, s[t] = d[t] + d[t + 256] + d[t + 512] + ...
+ *      (ascending, t = 0 .. 255, missing terms are +0), then seven halving steps s[t] += s[t + h], h = 128, 64, .. 1; the sum is s[0].
+ *      Any order of these positive terms lies within n_corres 2^-53 relative of any other.
+ *   3. Rounding.  ll, rr are the pairs rounded to float32 (cv::Point2f); everything after the gate uses them, widened to double.
+ *   4. RANSAC.  cv::findFundamentalMat(ll, rr, FM_RANSAC, ransac_threshold (0.3 / 460), 0.99, mask) is this library's deterministic
+ *      RANSAC of vg_fe_reject_with_f (oracle/ASSUMPTIONS.md F9) at this threshold: the sample schedule of cv::RNG((uint64)-1), run7Point
+ *      on the raw points, the models of a sample ranked best first, the float error against threshold^2, a model replacing the best one
+ *      when it has more inliers than max(best, 6), the bound RANSACUpdateNumIters(0.99, ...) after every improvement.  The model goes out
+ *      unchanged (OpenCV 3.3's registrator does not refit) and is used as E: the points are normalised.  The device runs the schedule as
+ *      far as it depends on n alone; a candidate in whose schedule a sample would have been REDRAWN by OpenCV (its last point collinear
+ *      with two earlier ones) is repeated with the exact schedule, made on the host, through the same kernels; its results are those of
+ *      the exact schedule and used_fallback is 1.  min_corres >= 14, so a gated candidate always has the 15 points of the RANSAC branch.
+ *   5. decomposeEssentialMat.  The SVD of the 3x3 matrix here is a one-sided Jacobi on its columns (pairs (0,1), (0,2), (1,2) in turn,
+ *      a pair is rotated while |a.b| > 1e-15 |a||b|; at most 40 sweeps; only rotations between two columns above 1e-13 of the Frobenius
+ *      norm keep the sweeps going).  Singular values: the column norms, descending (stable).  Vt: the accumulated rotations in that
+ *      order, negated when its determinant is negative.  U: u0, u1 the first two columns over their norms, u2 = u0 x u1 (so det U = +1;
+ *      the third column of a matrix of rank 2 is rounding noise and is not used).  R1 = U W Vt, R2 = U Wt Vt, t = u2.  The set
+ *      {R1, R2} x {t, -t} does not depend on this convention; the ORDER does, and with it the >= tie-break of :152-181 -- a LAPACK SVD
+ *      may name R1 what is R2 here.
+ *   6. Four triangulations, (R1, t), (R2, t), (R1, -t), (R2, -t) against P0 = [I|0].  cv::triangulatePoints is third-party and unpinned.
+ *      RECALLED for OpenCV 3.3.1, NOT PINNED: per point a 6x4 design matrix, three rows per view (x P[2] - P[0], y P[2] - P[1],
+ *      x P[1] - y P[0]), and the right singular vector of the smallest singular value -- here by the one-sided Jacobi of vg_triangulate
+ *      (threshold 1e-16, at most 40 sweeps) on the four columns.  (Later OpenCV releases build a 4x4 matrix from two rows per view; the
+ *      null vector of exact data is the same, of noisy data it is not.)  Masks in exactly the order of :80-88: Q.z Q.w > 0; Q divided by
+ *      Q.w; z < dist (50); z' = (P Q).z summed left to right; z' > 0; z' < dist.  ANDed with the RANSAC mask.  The winner by the chain
+ *      good1 >= the others, else good2 >= the others, else good3, else the fourth.  relative_R = R^T, relative_T = -(R^T t) of the
+ *      winner; success is inlier_cnt > min_inliers (12).
+ *   7. Pick.  l is the first i in ascending order whose gate passes and whose solveRelativeRT succeeds.
+ * Deviations:
+ *   - the candidates are evaluated in parallel; every gated one is computed whatever an earlier one returned, so the taps are the same
+ *     from run to run and do not depend on l;
+ *   - a triangulated value that is not finite (Q.w = 0) fails every comparison it enters, as cv::compare has it: the point counts for no
+ *     candidate;
+ *   - a RANSAC that finds no model (no sample with more than 6 inliers) makes the candidate fail with zero taps, where the reference
+ *     hands an empty matrix to recoverPose and aborts;
+ *   - a 3x3 SVD that does not converge inside the sweep cap makes the candidate numeric; when the walk of 7 meets such a candidate before
+ *     a success the window ends with VG_RELPOSE_NUMERIC (l = -1).  That window only: its neighbours are untouched.
+ * Taps of a candidate that is not gated are zero.  ransac_iter is the iteration the bookkeeping ended on, the last one its loop looked at (the larger of the
+ * winning iteration and bound - 1; -1: the schedule was empty), ransac_bound the bound it ended with, ransac_best the iteration whose model
+ * won (-1: none).  A batch equals the single calls bit for bit.
+ * Refused with VG_ERR_BAD_ARG before anything is uploaded (vg_last_error names the cause; no output is touched, the handle stays usable): a
+ * wrong struct_size, F outside 3 .. VG_SFM_MAX_FRAMES, n_feat outside 1 .. VG_SFM_MAX_FEATURES, a NULL table, start + nobs > F or nobs <
+ * 1, obs_off not ascending, a non-finite input, a threshold, gate, focal or distance that is not positive, min_corres < 14 or min_inliers <
+ * 0, a confidence other than 0.99 (the bound table is built for it), more than VG_RELPOSE_MAX_STREAMS candidates in one call.
+ * NOT part of it: InitialEXRotation::CalibrationExRotation (it keeps state across frames and uses another findFundamentalMat mode),
+ * re-initialisation inside vg_vio_*, a drop-in against the reference's headers. */
+enum { VG_RELPOSE_OK = 0, VG_RELPOSE_NONE = 1, VG_RELPOSE_NUMERIC = 2 };
+#define VG_RELPOSE_LAUNCHES 9         /* gather | RANSAC part 1: samples, counts, bookkeeping | part 2: the same | pose | pick */
+#define VG_RELPOSE_MAX_STREAMS 4096   /* (window, candidate) pairs of one call: each holds the models of 1000 iterations on the device */
+
+typedef struct {
+    size_t struct_size;          /* sizeof(vg_relpose_in) */
+    int n_frames;                /* F = frame_count + 1, 3 .. VG_SFM_MAX_FRAMES */
+    int n_feat;                  /* 1 .. VG_SFM_MAX_FEATURES */
+    const int* start;            /* [n_feat] the tables of vg_sfm_in */
+    const int* nobs;
+    const int* obs_off;
+    const double* points;        /* x y z rows; x and y are used */
+    /* what the reference hard-codes; its values are the defaults a caller should set */
+    double ransac_threshold;     /* 0.3 / 460 */
+    double confidence;           /* 0.99 (nothing else is accepted) */
+    int min_corres;              /* 20 */
+    int min_inliers;             /* 12 */
+    double parallax_gate;        /* 30 */
+    double focal;                /* 460 */
+    double cheirality_dist;      /* 50 */
+} vg_relpose_in;
+
+typedef struct {                 /* every pointer may be NULL */
+    size_t struct_size;          /* sizeof(vg_relpose_out), set by the caller */
+    int status;                  /* VG_RELPOSE_* */
+    int l;                       /* -1 when none */
+    double relative_R[9];        /* row-major; zeros when none */
+    double relative_T[3];
+    int n_mask;                  /* n_corres of l */
+    unsigned char* mask;         /* [n_feat] the first n_mask: the final mask (RANSAC and cheirality) over the correspondences of l */
+    unsigned char* ransac_mask;  /* [n_feat] the first n_mask: the mask findFundamentalMat returned for l (a tap) */
+    /* taps per candidate, [F-1] each */
+    int* n_corres;
+    double* avg_parallax;
+    int* gate;
+    int *ransac_iter, *ransac_bound, *ransac_inliers, *ransac_best;
+    double* F;                   /* [F-1][9] */
+    int* good;                   /* [F-1][4] */
+    int *winner, *inlier_cnt, *used_fallback;
+    double* device_ms;           /* read on out[0] only: [VG_RELPOSE_LAUNCHES] device time per launch from events, or NULL.  The second
+                                  * submission of the candidates that need the exact schedule (used_fallback) is NOT in these figures */
+} vg_relpose_out;
+
+int vg_init_relpose(vg_handle* h, int n_windows, const vg_relpose_in* in, vg_relpose_out* out);
 
 /* block kinds of the marginalization prior (MarginalizationInfo::keep_block_*) */
 enum { VG_BLK_POSE = 0, VG_BLK_SPEEDBIAS = 1, VG_BLK_EXPOSE = 2, VG_BLK_TD = 3 };

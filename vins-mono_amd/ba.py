@@ -124,6 +124,27 @@ class SfmOut(C.Structure):            # vg_sfm_out
                 ("it_flags", C.c_int * SFM_MAX_ITERS), ("device_ms", _pd)]
 
 
+RELPOSE_LAUNCHES = 9                 # VG_RELPOSE_LAUNCHES
+RELPOSE_OK, RELPOSE_NONE, RELPOSE_NUMERIC = 0, 1, 2
+# what the reference hard-codes (estimator.cpp:442-471, solve_5pts.cpp:193-227): the defaults of Handle.init_relpose
+RELPOSE_DEFAULTS = dict(ransac_threshold=0.3 / 460, confidence=0.99, min_corres=20, min_inliers=12, parallax_gate=30.0, focal=460.0,
+                        cheirality_dist=50.0)
+_pu8 = C.POINTER(C.c_uint8)
+
+
+class RelposeIn(C.Structure):         # vg_relpose_in
+    _fields_ = [("struct_size", C.c_size_t), ("n_frames", C.c_int), ("n_feat", C.c_int), ("start", _pi), ("nobs", _pi), ("obs_off", _pi),
+                ("points", _pd), ("ransac_threshold", C.c_double), ("confidence", C.c_double), ("min_corres", C.c_int), ("min_inliers", C.c_int),
+                ("parallax_gate", C.c_double), ("focal", C.c_double), ("cheirality_dist", C.c_double)]
+
+
+class RelposeOut(C.Structure):        # vg_relpose_out
+    _fields_ = [("struct_size", C.c_size_t), ("status", C.c_int), ("l", C.c_int), ("relative_R", C.c_double * 9), ("relative_T", C.c_double * 3),
+                ("n_mask", C.c_int), ("mask", _pu8), ("ransac_mask", _pu8), ("n_corres", _pi), ("avg_parallax", _pd), ("gate", _pi),
+                ("ransac_iter", _pi), ("ransac_bound", _pi), ("ransac_inliers", _pi), ("ransac_best", _pi), ("F", _pd), ("good", _pi), ("winner", _pi),
+                ("inlier_cnt", _pi), ("used_fallback", _pi), ("device_ms", _pd)]
+
+
 SEQ_INFO = ("flag", "n_features", "n_tracked", "n_parallax", "n_landmarks", "n_factors", "status", "n_after")
 
 
@@ -341,6 +362,8 @@ class Handle:
             L.vg_init_align.argtypes = [C.c_void_p, C.c_int, C.POINTER(AlignIn), C.POINTER(AlignOut)]
         if hasattr(L, "vg_init_sfm"):                     # (added within ABI 12)
             L.vg_init_sfm.argtypes = [C.c_void_p, C.c_int, C.POINTER(SfmIn), C.POINTER(SfmOut)]
+        if hasattr(L, "vg_init_relpose"):                 # (added within ABI 12)
+            L.vg_init_relpose.argtypes = [C.c_void_p, C.c_int, C.POINTER(RelposeIn), C.POINTER(RelposeOut)]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -939,6 +962,58 @@ class Handle:
                      it_radius=np.array(o.it_radius)[:it], it_flags=np.array(o.it_flags)[:it])
             d.update({k: b[k] for k in ('q', 'T', 'state', 'position', 'R_all', 'T_all', 'q0', 'T0', 'position0', 'pnp_iters', 'pnp_up')})
             d['is_key'] = b['is_key'][:len(b['all_key'])]
+            if timed:
+                d['device_ms'] = b['device_ms']
+            res.append(d)
+        return res
+
+    RELPOSE_TAPS = ('n_corres', 'avg_parallax', 'gate', 'ransac_iter', 'ransac_bound', 'ransac_inliers', 'ransac_best', 'F', 'good', 'winner', 'inlier_cnt',
+                    'used_fallback')
+
+    @staticmethod
+    def init_relpose_pack(windows, timed=False):
+        """(vg_relpose_in array, vg_relpose_out array, the NumPy arrays both point into) for init_relpose's window dicts"""
+        n = len(windows)
+        ins, outs, keep = (RelposeIn * n)(), (RelposeOut * n)(), []
+        i32 = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
+        for w, (a, o) in zip(windows, zip(ins, outs)):
+            F = int(w['n_frames'])
+            start, nobs = i32(w['start']), i32(w['nobs'])
+            nf, nc = len(start), max(F - 1, 1)
+            off = i32(w['obs_off']) if w.get('obs_off') is not None else i32(np.concatenate([[0], np.cumsum(nobs)[:-1]]))
+            points = np.array(w['points'], np.float64).reshape(-1, 3)           # (copies: the call never aliases the caller's arrays)
+            bufs = dict(start=start, nobs=nobs, off=off, points=points, mask=np.zeros(max(nf, 1), np.uint8), ransac_mask=np.zeros(max(nf, 1), np.uint8),
+                        n_corres=np.zeros(nc, np.int32), avg_parallax=np.zeros(nc), gate=np.zeros(nc, np.int32), ransac_iter=np.zeros(nc, np.int32),
+                        ransac_bound=np.zeros(nc, np.int32), ransac_inliers=np.zeros(nc, np.int32), ransac_best=np.zeros(nc, np.int32), F=np.zeros((nc, 3, 3)),
+                        good=np.zeros((nc, 4), np.int32), winner=np.zeros(nc, np.int32), inlier_cnt=np.zeros(nc, np.int32),
+                        used_fallback=np.zeros(nc, np.int32), device_ms=np.zeros(RELPOSE_LAUNCHES))
+            keep.append(bufs)
+            a.struct_size, a.n_frames, a.n_feat = C.sizeof(RelposeIn), F, nf
+            a.start, a.nobs, a.obs_off, a.points = _ip(start), _ip(nobs), _ip(off), _dp(points)
+            for k, v in RELPOSE_DEFAULTS.items():
+                setattr(a, k, type(v)(w.get(k, v)))
+            o.struct_size = C.sizeof(RelposeOut)
+            o.mask, o.ransac_mask = bufs['mask'].ctypes.data_as(_pu8), bufs['ransac_mask'].ctypes.data_as(_pu8)
+            for k in Handle.RELPOSE_TAPS:
+                setattr(o, k, _dp(bufs[k]) if bufs[k].dtype == np.float64 else _ip(bufs[k]))
+            if timed:
+                o.device_ms = _dp(bufs['device_ms'])
+        return ins, outs, keep
+
+    def init_relpose(self, windows, timed=False):
+        """Estimator::relativePose for a batch of windows (vg_init_relpose): the candidate frames 0 .. F-2 against F-1, the first one that
+        passes the parallax gate and whose solveRelativeRT succeeds is l.  A window is a dict with the feature tables of init_sfm
+        (n_frames, start, nobs, points as x y z rows, obs_off optional) and, optionally, the constants of RELPOSE_DEFAULTS.  Returns one
+        dict per window: status (RELPOSE_*), l (-1: none), relative_R [3][3], relative_T, mask / ransac_mask over the correspondences
+        of l, and the per-candidate taps of RELPOSE_TAPS; with timed, the first carries device_ms, one figure per launch."""
+        ins, outs, keep = self.init_relpose_pack(windows, timed)
+        self._chk(self.lib.vg_init_relpose(self.h, len(windows), ins, outs), "vg_init_relpose")
+        res = []
+        for w, o, b in zip(windows, outs, keep):
+            nc = int(w['n_frames']) - 1
+            d = dict(status=int(o.status), l=int(o.l), relative_R=np.array(o.relative_R).reshape(3, 3), relative_T=np.array(o.relative_T),
+                     mask=b['mask'][:int(o.n_mask)], ransac_mask=b['ransac_mask'][:int(o.n_mask)])
+            d.update({k: b[k][:nc] for k in self.RELPOSE_TAPS})
             if timed:
                 d['device_ms'] = b['device_ms']
             res.append(d)

@@ -403,3 +403,6 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
     if (n_inliers) *n_inliers = n_in;
     return VG_OK;
 }
+
+// ---- vg_init_relpose: the two kernel bodies above with a (window, candidate) pair as the stream, the pose stage and the host entry
+#include "init_relpose.h"

@@ -157,4 +157,8 @@ struct vg_handle {
     void* imu_buf = nullptr;                      // device scratch of vg_imu_preintegrate (grown on demand)
     size_t imu_cap = 0;
     void* ransac_buf = nullptr;                   // device scratch of vg_fe_reject_with_f (fixed size, allocated on first use)
+    void* relpose_buf = nullptr;                  // device scratch of vg_init_relpose (grown on demand)
+    size_t relpose_cap = 0;
+    void* relpose_tab = nullptr;                  // its resident RANSAC tables: the n-only schedules and the bounds for n = 15 .. relpose_nmax
+    int relpose_nmax = 0;
 };

@@ -129,6 +129,28 @@ void Estimator::repropagate(IntegrationBase* p) {
     vg_pack::preint_from_abi(*p, out);
 }
 
+bool Estimator::relativePose(Matrix3d& relative_R, Vector3d& relative_T, int& l) {                      // estimator.cpp:442-471
+    if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
+    vg_pack::RelposeIn in;
+    vg_pack_relpose(f_manager.feature, frame_count + 1, in);
+    vg_pack::RelposeOut o;
+    if (vg_init_relpose(vg_, 1, &in.in, &o.out) != VG_OK) throw std::runtime_error(std::string("vg_init_relpose: ") + vg_last_error(vg_));
+    relpose_status = o.out.status;
+    l = o.out.l;
+    if (o.out.status != VG_RELPOSE_OK) return false;
+    for (int e = 0; e < 9; ++e) relative_R(e / 3, e % 3) = o.out.relative_R[e];
+    relative_T = Vector3d(o.out.relative_T[0], o.out.relative_T[1], o.out.relative_T[2]);
+    return true;
+}
+
+bool Estimator::initialStructure() {                            // estimator.cpp:250-257, then the rest
+    Matrix3d relative_R;
+    Vector3d relative_T;
+    int l;
+    if (!relativePose(relative_R, relative_T, l)) return false;
+    return initialStructure(l, relative_R, relative_T);
+}
+
 bool Estimator::initialStructure(int l, const Matrix3d& relative_R, const Vector3d& relative_T) {      // estimator.cpp:250-362
     if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
     vg_pack::SfmIn in;

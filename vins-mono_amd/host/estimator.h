@@ -99,6 +99,13 @@ class Estimator {
     // vg_init_sfm call over f_manager.feature and all_image_frame (l, relative_R, relative_T: what relativePose() returned), then
     // ImageFrame::R / T / is_key_frame, then visualInitialAlign().  A construct failure sets marginalization_flag = MARGIN_OLD (:282).
     bool initialStructure(int l, const Matrix3d& relative_R, const Vector3d& relative_T);
+    // estimator.cpp:442-471 on the device: every candidate frame 0 .. frame_count - 1 against frame_count in one vg_init_relpose call
+    // over f_manager.feature; false (l = -1) when no frame passes the parallax gate and solveRelativeRT
+    bool relativePose(Matrix3d& relative_R, Vector3d& relative_T, int& l);
+    // relativePose() chained into initialStructure(l, relative_R, relative_T); when no frame passes: false, marginalization_flag untouched
+    // (the reference's "Not enough features or parallax; Move device around", :252-257)
+    bool initialStructure();
+    int relpose_status = 0;                          // VG_RELPOSE_* of the last relativePose()
     int sfm_status = 0;                              // VG_SFM_* of the last initialStructure()
     map<double, ImageFrame> all_image_frame;         // estimator.h:101
     double Headers[(WINDOW_SIZE + 1)];               // Headers[i].stamp.toSec()

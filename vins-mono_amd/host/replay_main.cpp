@@ -36,6 +36,11 @@
 //   vins_replay sfm <in.bin> <out.txt>
 //     Estimator::initialStructure(l, relative_R, relative_T) (vg_init_sfm, then visualInitialAlign) over f_manager.feature and one
 //     all_image_frame map from a file; writes the statuses, every entry's is_key_frame / R / T and what `align` writes (replay_sfm below).
+//
+//   vins_replay relpose <in.bin> <out.txt>
+//     Estimator::relativePose(relative_R, relative_T, l) (vg_init_relpose) over f_manager.feature from a file; writes the return value,
+//     the VG_RELPOSE_* status, l, relative_R and relative_T and, when no frame passes, what the zero-argument initialStructure() returns
+//     and leaves in marginalization_flag (replay_relpose below).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -441,6 +446,55 @@ static int replay_sfm(const char* in, const char* out) {
     return 0;
 }
 
+// vins_replay relpose <in.bin> <out.txt>: Estimator::relativePose over f_manager.feature from a file (tests/init_relpose_ref.write_file):
+// int32 'VRP1', F (window frames), L (features), rows; L int32 start_frame, L int32 n_obs, L int32 first row; rows x y z.  Writes
+// "result <return value> <VG_RELPOSE_*> <l>", "R" with nine numbers, "T" with three (17 digits) and, when relativePose returned false,
+// "structure <return value of initialStructure()> <marginalization_flag>".
+static int replay_relpose(const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("relpose file"); return 2; }
+    int hdr[4];
+    rd.i(hdr, 4);
+    if (hdr[0] != 0x31505256) { fprintf(stderr, "not a VRP1 file\n"); return 2; }
+    const int K = hdr[1], L = hdr[2], rows = hdr[3];
+    if (K < 3 || K > WINDOW_SIZE + 1) { fprintf(stderr, "K = %d: the Estimator holds 3 .. %d window frames\n", K, WINDOW_SIZE + 1); return 2; }
+    std::vector<int> start(L), nobs(L), off(L);
+    std::vector<double> pts((size_t)rows * 3);
+    rd.i(start.data(), L); rd.i(nobs.data(), L); rd.i(off.data(), L); rd.d(pts.data(), rows * 3);
+    fclose(rd.f);
+    Estimator est;
+    est.frame_count = K - 1;
+    for (int j = 0; j < L; ++j) {
+        FeaturePerId f;
+        f.feature_id = j; f.start_frame = start[j];
+        for (int k = 0; k < nobs[j]; ++k) {
+            FeaturePerFrame fr;
+            const double* r = &pts[3 * ((size_t)off[j] + k)];
+            fr.point = Vector3d(r[0], r[1], r[2]);
+            f.feature_per_frame.push_back(fr);
+        }
+        est.f_manager.feature.push_back(f);
+    }
+    Matrix3d relative_R;
+    for (int e = 0; e < 9; ++e) relative_R(e / 3, e % 3) = 0.0;
+    Vector3d relative_T(0.0, 0.0, 0.0);
+    int l = -2;
+    const bool ok = est.relativePose(relative_R, relative_T, l);
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    fprintf(o, "result %d %d %d\n", ok ? 1 : 0, est.relpose_status, l);
+    fprintf(o, "R");
+    for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", relative_R(e / 3, e % 3));
+    fprintf(o, "\nT %.17g %.17g %.17g\n", relative_T.x(), relative_T.y(), relative_T.z());
+    if (!ok) {
+        est.marginalization_flag = Estimator::MARGIN_SECOND_NEW;    // (initialStructure() must leave it alone when no frame passes)
+        const bool st = est.initialStructure();
+        fprintf(o, "structure %d %d\n", st ? 1 : 0, (int)est.marginalization_flag);
+    }
+    fclose(o);
+    return 0;
+}
+
 namespace {
 // the front end of `vio`: one frame through readImage + updateID, returned as the `image` map (features seen at least twice)
 struct FrontEnd {
@@ -726,10 +780,14 @@ int main(int argc, char** argv) {
         try { return replay_align(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay align: %s\n", e.what()); return 1; }
     }
+    if (argc >= 4 && !strcmp(argv[1], "relpose")) {
+        try { return replay_relpose(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay relpose: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "sfm")) {
         try { return replay_sfm(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt>\n");
     return 2;
 }

@@ -242,6 +242,18 @@ struct AlignOut {
     AlignOut& operator=(const AlignOut&) = delete;
 };
 
+// the walk over f_manager.feature that vg_sfm_in and vg_relpose_in share: one row of (id, start, nobs, obs_off) per feature, its points behind
+template <class Features>
+void pack_feature_tables(const Features& features, std::vector<int>& id, std::vector<int>& start, std::vector<int>& nobs, std::vector<int>& off,
+                         std::vector<double>& points) {
+    for (const auto& f : features) {
+        id.push_back(f.feature_id); start.push_back(f.start_frame); nobs.push_back((int)f.feature_per_frame.size());
+        off.push_back((int)(points.size() / 3));
+        for (const auto& o : f.feature_per_frame)
+            for (int r = 0; r < 3; ++r) points.push_back(o.point(r));
+    }
+}
+
 // ---- initialisation: GlobalSFM::construct + the per-frame PnP of initialStructure (vg_init_sfm)
 // f_manager.feature and all_image_frame -> vg_sfm_in.  Features: a list of FeaturePerId (feature_id, start_frame, feature_per_frame with
 // .point); Map: std::map<double, ImageFrame> whose entries carry `points` (id -> vector of (camera, x y z u v vx vy)); stamps: the
@@ -258,12 +270,7 @@ void pack_sfm(const Features& features, const Map& frames, const double* stamps,
               const M3& ric, SfmIn& p) {
     p.id.clear(); p.start.clear(); p.nobs.clear(); p.off.clear(); p.points.clear();
     p.all_key.clear(); p.all_guess.clear(); p.all_off.assign(1, 0); p.all_id.clear(); p.all_xy.clear();
-    for (const auto& f : features) {
-        p.id.push_back(f.feature_id); p.start.push_back(f.start_frame); p.nobs.push_back((int)f.feature_per_frame.size());
-        p.off.push_back((int)(p.points.size() / 3));
-        for (const auto& o : f.feature_per_frame)
-            for (int r = 0; r < 3; ++r) p.points.push_back(o.point(r));
-    }
+    pack_feature_tables(features, p.id, p.start, p.nobs, p.off, p.points);
     int i = 0;
     for (auto it = frames.begin(); it != frames.end(); ++it) {
         if (i < n_stamps && it->first == stamps[i]) {
@@ -308,6 +315,31 @@ struct SfmOut {
     }
     SfmOut(const SfmOut&) = delete;
     SfmOut& operator=(const SfmOut&) = delete;
+};
+
+// ---- initialisation: Estimator::relativePose (vg_init_relpose) over the same feature tables; the constants are the reference's
+struct RelposeIn {
+    std::vector<int> id, start, nobs, off;
+    std::vector<double> points;
+    vg_relpose_in in;
+};
+template <class Features>
+void pack_relpose(const Features& features, int n_frames, RelposeIn& p) {
+    p.id.clear(); p.start.clear(); p.nobs.clear(); p.off.clear(); p.points.clear();
+    pack_feature_tables(features, p.id, p.start, p.nobs, p.off, p.points);
+    std::memset(&p.in, 0, sizeof(p.in));
+    p.in.struct_size = sizeof(p.in);
+    p.in.n_frames = n_frames; p.in.n_feat = (int)p.id.size();
+    p.in.start = p.start.data(); p.in.nobs = p.nobs.data(); p.in.obs_off = p.off.data(); p.in.points = p.points.data();
+    p.in.ransac_threshold = 0.3 / 460; p.in.confidence = 0.99; p.in.min_corres = 20; p.in.min_inliers = 12;      // solve_5pts.cpp:204, :221, estimator.cpp:449
+    p.in.parallax_gate = 30; p.in.focal = 460; p.in.cheirality_dist = 50;                                        // estimator.cpp:460, solve_5pts.cpp:77
+}
+struct RelposeOut {
+    vg_relpose_out out;
+    RelposeOut() {
+        std::memset(&out, 0, sizeof(out));
+        out.struct_size = sizeof(out);
+    }
 };
 
 // ================================================================================================================== front end
@@ -473,6 +505,11 @@ template <class Features, class Map, class M3, class V3>
 void vg_pack_sfm(const Features& features, const Map& frames, const double* stamps, int n_stamps, int l, const M3& relative_R, const V3& relative_T,
                  const M3& ric, vg_pack::SfmIn& p) {
     vg_pack::pack_sfm(features, frames, stamps, n_stamps, l, relative_R, relative_T, ric, p);
+}
+// (the packer of vg_init_relpose under the name the integration guide uses)
+template <class Features>
+void vg_pack_relpose(const Features& features, int n_frames, vg_pack::RelposeIn& p) {
+    vg_pack::pack_relpose(features, n_frames, p);
 }
 // (the packer of vg_init_align under the name the integration guide uses)
 template <class Map, class V3>
