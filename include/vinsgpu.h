@@ -31,7 +31,7 @@ extern "C" {
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
-                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose) */
+                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -187,8 +187,8 @@ int vg_init_align(vg_handle* h, int n_windows, const vg_align_in* in, vg_align_o
  * ReprojectionError3D of initial/initial_sfm.h:25-54) for n_windows independent windows in one synchronous call: one upload, two launches
  * (one workgroup per window: GlobalSFM::construct with its full BA; then one workgroup per non-key frame: its PnP), one download, FP64.
  * R_all / T_all are ImageFrame::R / T, the inputs of vg_align_in::R / T.  l, relative_R, relative_T are inputs: relativePose / solveRelativeRT
- * is vg_init_relpose (below), whose outputs they are.  InitialEXRotation and the IMU-excitation check of :222-248 (which has no effect in the
- * reference) are NOT part of either call.
+ * is vg_init_relpose (below), whose outputs they are; ric may be what vg_init_exrot (below) calibrated.  The IMU-excitation check of
+ * :222-248 (which has no effect in the reference) is NOT part of either call.
  *
  * construct, statement by statement:
  *   - q[l] = identity, T[l] = 0, q[F-1] = q[l] * Quaterniond(relative_R) (Eigen's matrix-to-quaternion conversion), T[F-1] = relative_T;
@@ -347,8 +347,8 @@ int vg_init_sfm(vg_handle* h, int n_windows, const vg_sfm_in* in, vg_sfm_out* ou
  * wrong struct_size, F outside 3 .. VG_SFM_MAX_FRAMES, n_feat outside 1 .. VG_SFM_MAX_FEATURES, a NULL table, start + nobs > F or nobs <
  * 1, obs_off not ascending, a non-finite input, a threshold, gate, focal or distance that is not positive, min_corres < 14 or min_inliers <
  * 0, a confidence other than 0.99 (the bound table is built for it), more than VG_RELPOSE_MAX_STREAMS candidates in one call.
- * NOT part of it: InitialEXRotation::CalibrationExRotation (it keeps state across frames and uses another findFundamentalMat mode),
- * re-initialisation inside vg_vio_*, a drop-in against the reference's headers. */
+ * NOT part of it: re-initialisation inside vg_vio_*, a drop-in against the reference's headers.  (InitialEXRotation::
+ * CalibrationExRotation, which keeps state across frames and uses another findFundamentalMat mode, is vg_init_exrot below.) */
 enum { VG_RELPOSE_OK = 0, VG_RELPOSE_NONE = 1, VG_RELPOSE_NUMERIC = 2 };
 #define VG_RELPOSE_LAUNCHES 9         /* gather | RANSAC part 1: samples, counts, bookkeeping | part 2: the same | pose | pick */
 #define VG_RELPOSE_MAX_STREAMS 4096   /* (window, candidate) pairs of one call: each holds the models of 1000 iterations on the device */
@@ -393,6 +393,113 @@ typedef struct {                 /* every pointer may be NULL */
 } vg_relpose_out;
 
 int vg_init_relpose(vg_handle* h, int n_windows, const vg_relpose_in* in, vg_relpose_out* out);
+
+/* ---- Initialisation: extrinsic-rotation calibration, batched (added within ABI 12, nothing existing changed) ---------------------------
+ * InitialEXRotation::CalibrationExRotation (initial/initial_ex_rotation.cpp, the whole file) for n_windows independent windows in one
+ * synchronous call; every window gets a run of S = n_steps consecutive calls of the reference's member.  Step k (k = 1 .. S) is the call
+ * with frame_count = n_prev + k.  One upload, nine launches, one download on the ordinary path; a step in the LMedS range costs one small
+ * estimate of its own before the upload, a step that needs the exact sample schedule a second small submission (see 3, 4).  With it every
+ * stage of vins_estimator/src/initial/ has its call: a caller with estimate_extrinsic: 2 feeds calib_ric to vg_sfm_in::ric / vg_align_in.
+ *
+ * Statement by statement, quirks kept:
+ *   1. solveRelativeR, small inputs.  Fewer than min_points (9) correspondences give Rc = identity (branch 0); F and the other taps are 0.
+ *   2. Rounding.  ll, rr are the pairs rounded to float32 (cv::Point2f); everything after uses them, widened to double.
+ *   3. Fundamental matrix, 15 points or more (branch 2): cv::findFundamentalMat(ll, rr) is FM_RANSAC at threshold 3.0, confidence 0.99 --
+ *      this library's deterministic RANSAC exactly as in vg_init_relpose item 4: the cv::RNG((uint64)-1) schedule, run7Point on the raw
+ *      points, the float error against threshold squared, no refit, and the second submission with the exact schedule (used_fallback)
+ *      for a step whose n-only schedule holds a redrawn sample.  CONSEQUENCE, kept: the points are normalised coordinates, so at 3.0
+ *      almost every point is an inlier of almost any model; the bookkeeping usually ends at iteration 0 with bound 0 and the matrix is
+ *      that of the FIRST sample, and where that sample's cubic has several real roots every root's model takes all points and the tie
+ *      may go to a spurious one, whose Rc is degrees off (about every second step of a rendered window).  That is the reference's
+ *      behaviour.  ransac_threshold is a field: in the units of the points (solveRelativeRT passes 0.3 / 460) the RANSAC separates them.
+ *   4. Fundamental matrix, 9 to 14 points (branch 1): OpenCV switches to LMedS.  It is the front end's LMedS (vg_fe_reject_with_f, csrc/
+ *      fe_ransac.hip, oracle/ASSUMPTIONS.md F9) run on the step's float32 points at this threshold, through that call's kernels, before the
+ *      upload, as the front end's fall-back streams run; ransac_* are 0 for it.  These estimates are NOT batched: one synchronous round trip
+ *      per such step, 0.2 ms each on an MI355X (profiles/init_exrot.json), outside device_ms.
+ *   5. decomposeE.  The SVD is vg_init_relpose item 5 (rp_decompose): R1 = U W Vt, R2 = U Wt Vt, t1 = u2, t2 = -u2.  det U = det Vt = +1
+ *      by construction, so det R1 = +1 and the E = -E branch of :83-87 is never taken; the set {R1, R2} x {t, -t} does not depend on
+ *      this.  The ORDER does depend on the convention, and with it the strict ratio1 > ratio2 of :90.
+ *   6. testTriangulation, in the order (R1,t1) (R1,t2) (R2,t1) (R2,t2) (front[4]).  P1 is a Matx34f: R and t are rounded to float32 and
+ *      widened.  cv::triangulatePoints is the 6x4 form of vg_init_relpose item 6 with the same Jacobi, in double, on the widened P1 and
+ *      points (RECALLED, NOT PINNED).  Its result is stored as float32: q = float32(Q).  RECALLED for OpenCV 3.3.1, NOT PINNED, and exactly
+ *      what the kernel does: col / normal_factor is a float32 scaling, inv = float32(1.0 / double(q.w)), a = q * inv in float32 (four
+ *      products); each of the two products P a is one row, z = float32(P[2][0] a.x + P[2][1] a.y + P[2][2] a.z + P[2][3] a.w) summed
+ *      left to right in double over the widened float32 operands (the products are exact) and rounded once.  front counts the points
+ *      with z_l > 0 and z_r > 0; a comparison with a non-finite value is false.  ratio = front / n in double.  The result is R1 when
+ *      max(ratio(R1,t1), ratio(R1,t2)) > max(ratio(R2,t1), ratio(R2,t2)), else R2 (picked 1 or 2; the double R, not its float32
+ *      rounding), and it goes out TRANSPOSED (:93-95): that is Rc of the step.
+ *   7. CalibrationExRotation.  Rimu = delta_q.toRotationMatrix() (not normalised, as Eigen).  Rc_g = (ric^-1 Rimu) ric, products left to
+ *      right, ric^-1 Eigen's 3x3 cofactor inverse (cofactors times 1 / det, det = (c00 m00 + c10 m10) + c20 m20), not a transpose.
+ *      Quaterniond(Matrix3d) is the conversion restated for vg_init_sfm.  angularDistance in Eigen 3.3's form, 2 atan2(|vec(d)|, |w(d)|)
+ *      with d = r1 * conj(r2) (UNPINNED: Eigen 3.2 takes 2 acos); in degrees by (180 / M_PI) *.  The Huber weight is huber_deg / angle
+ *      above huber_deg (5) degrees, else 1.  L and R exactly as :32-47, the vector part first and w last; the block of record i is
+ *      huber (L - R) entry by entry, and A is 4 (n_prev + k) x 4.  A record's block depends on the record alone.
+ *      JacobiSVD is third-party; here it is a one-sided Jacobi on the four columns of A itself, not on A^T A: the pairs (0,1) (0,2) (0,3)
+ *      (1,2) (1,3) (2,3) in turn; al = |a_p|^2, be = |a_q|^2, ga = a_p . a_q, each the sum over a record's four rows in ascending order
+ *      from 0, then over the 64 record slots (absent ones are 0) by six butterfly steps s += s[slot ^ h], h = 32 .. 1; the pair is rotated
+ *      when |ga| > 1e-16 sqrt(al be) and ga != 0, with zeta = (be - al) / (2 ga), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), c = 1 /
+ *      sqrt(1 + t^2), s = c t; the sweeps go on while a sweep met a pair with |ga| > 1e-13 sqrt(al be) between two columns above 1e-26 of
+ *      the squared Frobenius norm; at most 40 sweeps.  Singular values: the column norms, sorted descending (sigma); x is the column of V
+ *      of the smallest.  Quaterniond(x) reads x as (x y z w); ric = toRotationMatrix(x)^-1, the cofactor inverse again, no normalisation.
+ *      ok = (n_prev + k >= min_frames (10)) && sigma[2] > cov_threshold (0.25), strict: the test is on the THIRD singular value, the
+ *      result is the vector of the FOURTH.
+ * Deviations:
+ *   - every step is computed even after a success, where the reference's caller stops calling: first_ok = n_prev + k of the first step
+ *     with ok (-1: none) tells where it stopped, calib_ric is ric of that step (zeros when none);
+ *   - a 3x3 or 4N x 4 Jacobi that does not end inside its cap, or a RANSAC / LMedS that finds no model (the reference aborts inside
+ *     OpenCV on the empty matrix; here the step's Rc is the identity), gives VG_EXROT_NUMERIC for that window only, with first_ok -1;
+ *   - a batch equals the single calls bit for bit; a run split at any step and resumed with prev = the earlier records (carried and
+ *     returned, in order) and ric_prev = ric of the last step equals the unsplit run bit for bit.
+ * Refused with VG_ERR_BAD_ARG before anything is uploaded (vg_last_error names the cause; no output is touched, the handle stays usable): a
+ * wrong struct_size, n_steps < 1, n_prev < 0, n_prev + n_steps above VG_EXROT_MAX_STEPS, a NULL table, corr_off not ascending, a step over
+ * VG_SFM_MAX_FEATURES pairs, a non-finite input, a delta_q of zero norm, a threshold, huber_deg or cov_threshold that is not positive, a
+ * confidence other than 0.99, min_points < 9, more than VG_RELPOSE_MAX_STREAMS (window, step) pairs in one call (they use its scratch).
+ * NOT part of it: a drop-in against the reference's headers. */
+enum { VG_EXROT_OK = 0, VG_EXROT_NUMERIC = 1 };
+#define VG_EXROT_LAUNCHES 9           /* gather | RANSAC part 1: samples, counts, bookkeeping | part 2: the same | rotation | calibration */
+#define VG_EXROT_MAX_STEPS 64         /* n_prev + n_steps: one record per lane of the calibration stage's wavefront */
+
+typedef struct {
+    size_t struct_size;          /* sizeof(vg_exrot_in) */
+    int n_steps;                 /* S >= 1 */
+    const int* corr_off;         /* [S + 1] ascending: step k's correspondences are rows corr_off[k-1] .. corr_off[k] - 1 of corr */
+    const double* corr;          /* x0 y0 x1 y1 rows: corres[i].first(0,1) / .second(0,1) of getCorresponding(frame_count - 1, frame_count) */
+    const double* delta_q;       /* [S][4] (w x y z) pre_integrations[frame_count]->delta_q */
+    /* the carried state: a caller who feeds one frame at a time gets what one long call gives */
+    int n_prev;                  /* records before this call (0: the reference's constructor) */
+    const double* prev;          /* [n_prev][27] the records Rc | Rimu | Rc_g, row-major, in order */
+    const double* ric_prev;      /* [9] ric after the last earlier step; the identity when n_prev = 0, as the constructor sets it */
+    /* what the reference hard-codes; its values are the defaults a caller should set */
+    double ransac_threshold;     /* 3.0, cv::findFundamentalMat's default */
+    double confidence;           /* 0.99 (nothing else is accepted) */
+    int min_points;              /* 9 */
+    double huber_deg;            /* 5.0 */
+    int min_frames;              /* 10 (WINDOW_SIZE) */
+    double cov_threshold;        /* 0.25 */
+} vg_exrot_in;
+
+typedef struct {                 /* every pointer may be NULL */
+    size_t struct_size;          /* sizeof(vg_exrot_out), set by the caller */
+    int status;                  /* VG_EXROT_* */
+    int first_ok;                /* n_prev + k of the first step the reference would have returned true at, or -1 */
+    double calib_ric[9];         /* ric of that step, row-major; zeros when none */
+    /* per step, [S] each */
+    double* records;             /* [S][27] Rc | Rimu | Rc_g: append to prev to resume */
+    double* ric;                 /* [S][9] */
+    double* sigma;               /* [S][4] descending */
+    int* ok;
+    double* huber;               /* the weight of the step's OWN record */
+    /* taps per step */
+    int* branch;                 /* 0 identity, 1 LMedS, 2 RANSAC */
+    int *ransac_iter, *ransac_bound, *ransac_inliers, *ransac_best;     /* as vg_relpose_out; 0 outside branch 2 */
+    double* F;                   /* [S][9] */
+    int* front;                  /* [S][4] (R1,t1) (R1,t2) (R2,t1) (R2,t2) */
+    int *picked, *used_fallback; /* 1 or 2 (0: identity) */
+    double* device_ms;           /* read on out[0] only: [VG_EXROT_LAUNCHES] device time per launch from events, or NULL.  The LMedS
+                                  * estimates and the second submission (used_fallback) are NOT in these figures */
+} vg_exrot_out;
+
+int vg_init_exrot(vg_handle* h, int n_windows, const vg_exrot_in* in, vg_exrot_out* out);
 
 /* block kinds of the marginalization prior (MarginalizationInfo::keep_block_*) */
 enum { VG_BLK_POSE = 0, VG_BLK_SPEEDBIAS = 1, VG_BLK_EXPOSE = 2, VG_BLK_TD = 3 };
@@ -1157,8 +1264,8 @@ int vg_fe_tracks_set(vg_handle* h, int cam, const vg_fe_tracks_state* state);
  *                    in IMU mode (vg_ba_seq_begin + vg_ba_seq_imu_begin) on the same handle; n_cams == nwin; max_points <=
  *                    vg_ba_seq_config::max_new_obs; flags of VG_VIO_*.  The lists may hold tracks and the windows a seeded state -- the
  *                    normal case: the caller runs the first K-1 frames through vg_fe_tracks_step, initialises from the collected
- *                    messages (SfM and the extrinsic-rotation calibration on the host, the visual-inertial alignment of all
- *                    windows in one vg_init_align call), seeds the sequence from the result and switches to vg_vio_step_async
+ *                    messages (vg_init_exrot while estimate_extrinsic is 2, then vg_init_relpose, vg_init_sfm and vg_init_align, each
+ *                    one call for all windows), seeds the sequence from the result and switches to vg_vio_step_async
  *                    (the ids stay consistent because the list is resident).
  * vg_vio_step_async  one frame for every stream.  The frame of vg_fe_tracks_step (same kernels, same host finish of RANSAC and
  *                    detection); fe.publish must be uniform over the streams of one call.  On a frame that publishes, one kernel

@@ -145,6 +145,26 @@ class RelposeOut(C.Structure):        # vg_relpose_out
                 ("inlier_cnt", _pi), ("used_fallback", _pi), ("device_ms", _pd)]
 
 
+EXROT_LAUNCHES = 9                   # VG_EXROT_LAUNCHES
+EXROT_MAX_STEPS = 64                 # VG_EXROT_MAX_STEPS
+EXROT_OK, EXROT_NUMERIC = 0, 1
+# what the reference hard-codes (initial_ex_rotation.cpp; cv::findFundamentalMat's defaults): the defaults of Handle.init_exrot
+EXROT_DEFAULTS = dict(ransac_threshold=3.0, confidence=0.99, min_points=9, huber_deg=5.0, min_frames=10, cov_threshold=0.25)
+
+
+class ExrotIn(C.Structure):           # vg_exrot_in
+    _fields_ = [("struct_size", C.c_size_t), ("n_steps", C.c_int), ("corr_off", _pi), ("corr", _pd), ("delta_q", _pd), ("n_prev", C.c_int),
+                ("prev", _pd), ("ric_prev", _pd), ("ransac_threshold", C.c_double), ("confidence", C.c_double), ("min_points", C.c_int),
+                ("huber_deg", C.c_double), ("min_frames", C.c_int), ("cov_threshold", C.c_double)]
+
+
+class ExrotOut(C.Structure):          # vg_exrot_out
+    _fields_ = [("struct_size", C.c_size_t), ("status", C.c_int), ("first_ok", C.c_int), ("calib_ric", C.c_double * 9), ("records", _pd),
+                ("ric", _pd), ("sigma", _pd), ("ok", _pi), ("huber", _pd), ("branch", _pi), ("ransac_iter", _pi), ("ransac_bound", _pi),
+                ("ransac_inliers", _pi), ("ransac_best", _pi), ("F", _pd), ("front", _pi), ("picked", _pi), ("used_fallback", _pi),
+                ("device_ms", _pd)]
+
+
 SEQ_INFO = ("flag", "n_features", "n_tracked", "n_parallax", "n_landmarks", "n_factors", "status", "n_after")
 
 
@@ -364,6 +384,8 @@ class Handle:
             L.vg_init_sfm.argtypes = [C.c_void_p, C.c_int, C.POINTER(SfmIn), C.POINTER(SfmOut)]
         if hasattr(L, "vg_init_relpose"):                 # (added within ABI 12)
             L.vg_init_relpose.argtypes = [C.c_void_p, C.c_int, C.POINTER(RelposeIn), C.POINTER(RelposeOut)]
+        if hasattr(L, "vg_init_exrot"):                   # (added within ABI 12)
+            L.vg_init_exrot.argtypes = [C.c_void_p, C.c_int, C.POINTER(ExrotIn), C.POINTER(ExrotOut)]
         if L.vg_abi_version() != VG_ABI_VERSION:
             raise RuntimeError(f"libvinsgpu.so reports ABI version {L.vg_abi_version()}, this binding was written for {VG_ABI_VERSION}")
         self.h = C.c_void_p()
@@ -1014,6 +1036,58 @@ class Handle:
             d = dict(status=int(o.status), l=int(o.l), relative_R=np.array(o.relative_R).reshape(3, 3), relative_T=np.array(o.relative_T),
                      mask=b['mask'][:int(o.n_mask)], ransac_mask=b['ransac_mask'][:int(o.n_mask)])
             d.update({k: b[k][:nc] for k in self.RELPOSE_TAPS})
+            if timed:
+                d['device_ms'] = b['device_ms']
+            res.append(d)
+        return res
+
+    EXROT_TAPS = ('records', 'ric', 'sigma', 'ok', 'huber', 'branch', 'ransac_iter', 'ransac_bound', 'ransac_inliers', 'ransac_best', 'F', 'front', 'picked',
+                  'used_fallback')
+
+    @staticmethod
+    def init_exrot_pack(windows, timed=False):
+        """(vg_exrot_in array, vg_exrot_out array, the NumPy arrays both point into) for init_exrot's window dicts"""
+        n = len(windows)
+        ins, outs, keep = (ExrotIn * n)(), (ExrotOut * n)(), []
+        for w, (a, o) in zip(windows, zip(ins, outs)):
+            steps = [np.asarray(c, np.float64).reshape(-1, 4) for c in w['corr']]
+            S, ns = len(steps), max(len(steps), 1)
+            corr_off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(c) for c in steps])]), np.int32)
+            corr = np.ascontiguousarray(np.concatenate(steps + [np.zeros((1, 4))]))     # (never empty: the pointer is not NULL)
+            dq = np.array(w['delta_q'], np.float64).reshape(-1, 4)
+            prev = np.array(w.get('prev', np.zeros((0, 27))), np.float64).reshape(-1, 27)
+            n_prev = len(prev)
+            prev = np.ascontiguousarray(np.concatenate([prev, np.zeros((1, 27))]))
+            ric_prev = np.array(w.get('ric_prev', np.eye(3)), np.float64).reshape(9)
+            bufs = dict(corr_off=corr_off, corr=corr, delta_q=dq, prev=prev, ric_prev=ric_prev, records=np.zeros((ns, 27)), ric=np.zeros((ns, 3, 3)),
+                        sigma=np.zeros((ns, 4)), ok=np.zeros(ns, np.int32), huber=np.zeros(ns), branch=np.zeros(ns, np.int32),
+                        ransac_iter=np.zeros(ns, np.int32), ransac_bound=np.zeros(ns, np.int32), ransac_inliers=np.zeros(ns, np.int32),
+                        ransac_best=np.zeros(ns, np.int32), F=np.zeros((ns, 3, 3)), front=np.zeros((ns, 4), np.int32), picked=np.zeros(ns, np.int32),
+                        used_fallback=np.zeros(ns, np.int32), device_ms=np.zeros(EXROT_LAUNCHES))
+            keep.append(bufs)
+            a.struct_size, a.n_steps, a.n_prev = C.sizeof(ExrotIn), S, n_prev
+            a.corr_off, a.corr, a.delta_q, a.prev, a.ric_prev = _ip(corr_off), _dp(corr), _dp(dq), _dp(prev), _dp(ric_prev)
+            for k, v in EXROT_DEFAULTS.items():
+                setattr(a, k, type(v)(w.get(k, v)))
+            o.struct_size = C.sizeof(ExrotOut)
+            for k in Handle.EXROT_TAPS:
+                setattr(o, k, _dp(bufs[k]) if bufs[k].dtype == np.float64 else _ip(bufs[k]))
+            if timed:
+                o.device_ms = _dp(bufs['device_ms'])
+        return ins, outs, keep
+
+    def init_exrot(self, windows, timed=False):
+        """InitialEXRotation::CalibrationExRotation for a batch of windows (vg_init_exrot), a run of consecutive calls per window.  A window
+        is a dict with corr (one [n, 4] array x0 y0 x1 y1 per step), delta_q ([S][4], w x y z) and, to resume a run, prev ([n_prev][27]
+        records) and ric_prev; optionally the constants of EXROT_DEFAULTS.  Returns one dict per window: status (EXROT_*), first_ok (-1:
+        none), calib_ric [3][3] and the per-step arrays of EXROT_TAPS; with timed, the first carries device_ms, one figure per launch."""
+        ins, outs, keep = self.init_exrot_pack(windows, timed)
+        self._chk(self.lib.vg_init_exrot(self.h, len(windows), ins, outs), "vg_init_exrot")
+        res = []
+        for w, o, b in zip(windows, outs, keep):
+            S = len(w['corr'])
+            d = dict(status=int(o.status), first_ok=int(o.first_ok), calib_ric=np.array(o.calib_ric).reshape(3, 3))
+            d.update({k: b[k][:S] for k in self.EXROT_TAPS})
             if timed:
                 d['device_ms'] = b['device_ms']
             res.append(d)

@@ -406,3 +406,6 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
 
 // ---- vg_init_relpose: the two kernel bodies above with a (window, candidate) pair as the stream, the pose stage and the host entry
 #include "init_relpose.h"
+
+// ---- vg_init_exrot: the same RANSAC kernels with a (window, step) pair as the stream, the rotation and calibration stages, the host entry
+#include "init_exrot.h"

@@ -444,6 +444,77 @@ bool rp_finite(const double* p, size_t n) {
         if (!std::isfinite(p[i])) return false;
     return true;
 }
+// ---- what vg_init_relpose and vg_init_exrot (init_exrot.h) share on the host: one text for the tables, the scratch, the six RANSAC
+// launches and the exact schedules, so that the two entries cannot drift apart
+// the resident tables: built once per handle up to the largest point count seen, rebuilt larger when a call exceeds it
+hipError_t rp_resident_tables(vg_handle* h, int nmax) {
+    if (nmax <= h->relpose_nmax) return hipSuccess;
+    hipError_t e;
+    std::vector<int> sched, tab;
+    const int stride = nmax + 1;
+    fe_ransac_tables(nmax, sched, tab, stride);
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return e;
+    (void)hipFree(h->relpose_tab);
+    h->relpose_tab = nullptr; h->relpose_nmax = 0;
+    if ((e = hipMalloc(&h->relpose_tab, sizeof(int) * (sched.size() + tab.size()))) != hipSuccess) return e;
+    if ((e = hipMemcpy(h->relpose_tab, sched.data(), sizeof(int) * sched.size(), hipMemcpyHostToDevice)) != hipSuccess) return e;
+    if ((e = hipMemcpy((int*)h->relpose_tab + sched.size(), tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice)) != hipSuccess) return e;
+    h->relpose_nmax = nmax;
+    return hipSuccess;
+}
+// the scratch block, grown on demand
+hipError_t rp_scratch(vg_handle* h, size_t need) {
+    if (need <= h->relpose_cap) return hipSuccess;
+    hipError_t e;
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return e;
+    (void)hipFree(h->relpose_buf);
+    h->relpose_buf = nullptr; h->relpose_cap = 0;
+    if ((e = hipMalloc(&h->relpose_buf, need)) != hipSuccess) return e;
+    h->relpose_cap = need;
+    return hipSuccess;
+}
+// the schedule and bound pointers of a control block from the resident tables
+void rp_table_pointers(const vg_handle* h, RpDev& b) {
+    const int tmax = h->relpose_nmax;
+    b.tab_stride = tmax + 1;
+    b.sched = (const int*)h->relpose_tab; b.niters_tab = b.sched + (size_t)(tmax - 14) * FE_RANSAC_MAXIT * 7;
+}
+// the RANSAC stage of the streams whose RP_RUN is set: the chunked two-part scheme, six launches; stamp() after each
+template <class Stamp>
+hipError_t rp_ransac_launches(vg_handle* h, const RpDev& b, size_t NS, Stamp&& stamp) {
+    hipError_t r;
+    hipLaunchKernelGGL(rp_ransac7_kernel, dim3(RP_CHUNK0 / FR_PER_WAVE, (unsigned)NS), dim3(64), 0, h->stream, b, 0, RP_CHUNK0);
+    if ((r = stamp()) != hipSuccess) return r;
+    hipLaunchKernelGGL(rp_count_kernel, dim3(RP_CHUNK0, (unsigned)NS), dim3(64), 0, h->stream, b, 0, RP_CHUNK0);
+    if ((r = stamp()) != hipSuccess) return r;
+    hipLaunchKernelGGL(rp_pick_kernel, dim3((unsigned)NS), dim3(64), 0, h->stream, b, 0, RP_CHUNK0, 0);
+    if ((r = stamp()) != hipSuccess) return r;
+    hipLaunchKernelGGL(rp_ransac7_kernel, dim3(RP_P2_WAVES, (unsigned)NS), dim3(64), 0, h->stream, b, RP_CHUNK0, FE_RANSAC_MAXIT);
+    if ((r = stamp()) != hipSuccess) return r;
+    hipLaunchKernelGGL(rp_count_kernel, dim3(RP_P2_COUNT, (unsigned)NS), dim3(64), 0, h->stream, b, RP_CHUNK0, FE_RANSAC_MAXIT);
+    if ((r = stamp()) != hipSuccess) return r;
+    hipLaunchKernelGGL(rp_pick_kernel, dim3((unsigned)NS), dim3(64), 0, h->stream, b, RP_CHUNK0, FE_RANSAC_MAXIT, 1);
+    return stamp();
+}
+// The second submission's control blocks and exact schedules: only the streams of `again` run; points(s, pts) fills the stream's float32
+// point sets (the two sets 2 * cap apart) and returns their count.  xs gets one schedule per stream of `again`.
+template <class Points>
+void rp_exact_schedules(const std::vector<int>& again, int* ctl, size_t NS, int cap, std::vector<int>& xs, Points&& points) {
+    xs.assign(again.size() * FE_RANSAC_MAXIT * 7, 0);
+    std::vector<float> pts((size_t)cap * 4);
+    for (size_t s = 0; s < NS; ++s) ctl[s * RP_CTL_INTS + RP_RUN] = 0;
+    for (size_t k = 0; k < again.size(); ++k) {
+        const size_t s = again[k];
+        int* c = ctl + s * RP_CTL_INTS;
+        const int n = points(s, pts.data());
+        CvRng rng((unsigned long long)-1);
+        int nsched = 0;
+        for (; nsched < FE_RANSAC_MAXIT; ++nsched)
+            if (!get_subset(rng, pts.data(), pts.data() + 2 * cap, n, xs.data() + (k * FE_RANSAC_MAXIT + nsched) * 7, 10000)) break;
+        c[RP_RUN] = 1; c[RP_XS] = (int)k; c[RP_MAXIT] = nsched; c[RP_BEST] = -1; c[RP_NITERS] = 0; c[RP_MAXGOOD] = 0;
+    }
+}
+#define RP_XS_CAP 64                // exact schedules the scratch block has room for; more: a block of their own
 }  // namespace
 
 extern "C" int vg_init_relpose(vg_handle* h, int n_windows, const vg_relpose_in* in, vg_relpose_out* out) {
@@ -520,45 +591,26 @@ extern "C" int vg_init_relpose(vg_handle* h, int n_windows, const vg_relpose_in*
     auto fail = [&](hipError_t err) { h->err = std::string("vg_init_relpose: ") + hipGetErrorString(err); return VG_ERR_HIP; };
     if (e != hipSuccess) return fail(e);
     // ---- the resident tables: built once per handle up to the largest n_feat seen, rebuilt larger when a call exceeds it
-    if (nmax > h->relpose_nmax) {
-        std::vector<int> sched, tab;
-        const int stride = nmax + 1;
-        fe_ransac_tables(nmax, sched, tab, stride);
-        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail(e);
-        (void)hipFree(h->relpose_tab);
-        h->relpose_tab = nullptr; h->relpose_nmax = 0;
-        if ((e = hipMalloc(&h->relpose_tab, sizeof(int) * (sched.size() + tab.size()))) != hipSuccess) return fail(e);
-        if ((e = hipMemcpy(h->relpose_tab, sched.data(), sizeof(int) * sched.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
-        if ((e = hipMemcpy((int*)h->relpose_tab + sched.size(), tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
-        h->relpose_nmax = nmax;
-    }
-    const int tmax = h->relpose_nmax;
+    if ((e = rp_resident_tables(h, nmax)) != hipSuccess) return fail(e);
     // ---- device block: [out | in doubles | ints | scratch]
     const size_t b_out = 0, b_in = b_out + n_out * 8, b_int = b_in + n_in * 8, b_p1 = rp_up(b_int + n_int * 4, 256), b_p2 = b_p1 + NS * cap * 2 * sizeof(float);
     const size_t b_md = rp_up(b_p2 + NS * cap * 2 * sizeof(float), 256), b_F = b_md + NS * FE_RANSAC_MAXIT * 27 * 8, b_me = b_F + NS * FE_RANSAC_MAXIT * 9 * 8;
     const size_t b_wd = b_me + NS * FE_RANSAC_MAXIT * 8, b_m4 = b_wd + NS * FE_RANSAC_MAXIT * (size_t)words_n * 8, b_ct = b_m4 + NS * 4 * (size_t)words_n * 8;
     const size_t b_xs = rp_up(b_ct + NS * FE_RANSAC_MAXIT * 4, 256);
-    const size_t xs_cap = 64;                                       // exact schedules the block has room for at first; more: a block of their own
-    const size_t need = b_xs + xs_cap * FE_RANSAC_MAXIT * 7 * 4;
-    if (need > h->relpose_cap) {
-        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail(e);
-        (void)hipFree(h->relpose_buf);
-        h->relpose_buf = nullptr; h->relpose_cap = 0;
-        if ((e = hipMalloc(&h->relpose_buf, need)) != hipSuccess) return fail(e);
-        h->relpose_cap = need;
-    }
+    const size_t xs_cap = RP_XS_CAP;
+    if ((e = rp_scratch(h, b_xs + xs_cap * FE_RANSAC_MAXIT * 7 * 4)) != hipSuccess) return fail(e);
     char* base = (char*)h->relpose_buf;
     double* d_out = (double*)(base + b_out);
     double* d_in = (double*)(base + b_in);
     int* d_int = (int*)(base + b_int);
     RpDev b;
-    b.NS = (int)NS; b.W = W; b.cap = cap; b.words_n = words_n; b.tab_stride = tmax + 1;
+    b.NS = (int)NS; b.W = W; b.cap = cap; b.words_n = words_n;
+    rp_table_pointers(h, b);
     b.wi = d_int + i_wi; b.swin = d_int + i_sw; b.start = d_int + i_st; b.nobs = d_int + i_nb; b.off = d_int + i_of;
     b.par = d_in + o_par; b.obs = d_in + o_obs;
     b.ctl = (int*)(d_out + d_ctl); b.wout = (int*)(d_out + d_wo); b.avg = d_out + d_avg; b.res = d_out + d_res;
     b.rmask = (unsigned long long*)(d_out + d_rm); b.mask = (unsigned long long*)(d_out + d_mask);
     b.p1 = (float*)(base + b_p1); b.p2 = (float*)(base + b_p2);
-    b.sched = (const int*)h->relpose_tab; b.niters_tab = b.sched + (size_t)(tmax - 14) * FE_RANSAC_MAXIT * 7;
     b.xsched = (const int*)(base + b_xs);
     b.models = (double*)(base + b_md); b.Fit = (double*)(base + b_F); b.med = (double*)(base + b_me);
     b.words = (unsigned long long*)(base + b_wd); b.mask4 = (unsigned long long*)(base + b_m4); b.count = (int*)(base + b_ct);
@@ -578,18 +630,7 @@ extern "C" int vg_init_relpose(vg_handle* h, int n_windows, const vg_relpose_in*
     // the RANSAC and pose stages of the streams whose RP_RUN is set, then the pick over every window
     auto stages = [&](bool on) -> hipError_t {
         hipError_t r;
-        hipLaunchKernelGGL(rp_ransac7_kernel, dim3(RP_CHUNK0 / FR_PER_WAVE, (unsigned)NS), dim3(64), 0, h->stream, b, 0, RP_CHUNK0);
-        if ((r = stamp(on)) != hipSuccess) return r;
-        hipLaunchKernelGGL(rp_count_kernel, dim3(RP_CHUNK0, (unsigned)NS), dim3(64), 0, h->stream, b, 0, RP_CHUNK0);
-        if ((r = stamp(on)) != hipSuccess) return r;
-        hipLaunchKernelGGL(rp_pick_kernel, dim3((unsigned)NS), dim3(64), 0, h->stream, b, 0, RP_CHUNK0, 0);
-        if ((r = stamp(on)) != hipSuccess) return r;
-        hipLaunchKernelGGL(rp_ransac7_kernel, dim3(RP_P2_WAVES, (unsigned)NS), dim3(64), 0, h->stream, b, RP_CHUNK0, FE_RANSAC_MAXIT);
-        if ((r = stamp(on)) != hipSuccess) return r;
-        hipLaunchKernelGGL(rp_count_kernel, dim3(RP_P2_COUNT, (unsigned)NS), dim3(64), 0, h->stream, b, RP_CHUNK0, FE_RANSAC_MAXIT);
-        if ((r = stamp(on)) != hipSuccess) return r;
-        hipLaunchKernelGGL(rp_pick_kernel, dim3((unsigned)NS), dim3(64), 0, h->stream, b, RP_CHUNK0, FE_RANSAC_MAXIT, 1);
-        if ((r = stamp(on)) != hipSuccess) return r;
+        if ((r = rp_ransac_launches(h, b, NS, [&] { return stamp(on); })) != hipSuccess) return r;
         hipLaunchKernelGGL(rp_pose_kernel, dim3((unsigned)NS), dim3(64), 0, h->stream, b);
         if ((r = stamp(on)) != hipSuccess) return r;
         hipLaunchKernelGGL(rp_window_kernel, dim3((unsigned)(W + 63) / 64), dim3(64), 0, h->stream, b);
@@ -610,36 +651,25 @@ extern "C" int vg_init_relpose(vg_handle* h, int n_windows, const vg_relpose_in*
     void* xs_own = nullptr;
     struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } xs_free{xs_own};
     if (!again.empty()) {
-        std::vector<int> xs(again.size() * FE_RANSAC_MAXIT * 7, 0);
-        std::vector<float> pts((size_t)cap * 4);
+        // the stream's float32 point sets, gathered here from the caller's tables as rp_gather_kernel gathers them (no copy back)
+        std::vector<int> xs;
+        rp_exact_schedules(again, ctl, NS, cap, xs, [&](size_t s, float* pts) {
+            const int w = hint[i_sw + 2 * s], i = hint[i_sw + 2 * s + 1], n = ctl[s * RP_CTL_INTS + RP_N];
+            const vg_relpose_in& a = in[w];
+            int k = 0;
+            for (int j = 0; j < a.n_feat && k < n; ++j) {
+                const int s0 = a.start[j];
+                if (!(s0 <= i && s0 + a.nobs[j] - 1 >= a.n_frames - 1)) continue;
+                const double* r = a.points + 3 * (size_t)a.obs_off[j];
+                pts[2 * k] = (float)r[3 * (i - s0)]; pts[2 * k + 1] = (float)r[3 * (i - s0) + 1];
+                pts[2 * cap + 2 * k] = (float)r[3 * (a.n_frames - 1 - s0)]; pts[2 * cap + 2 * k + 1] = (float)r[3 * (a.n_frames - 1 - s0) + 1];
+                ++k;
+            }
+            return n;
+        });
         if (again.size() > xs_cap) {
             if ((e = hipMalloc(&xs_own, xs.size() * 4)) != hipSuccess) return fail(e);
             b.xsched = (const int*)xs_own;
-        }
-        for (size_t s = 0; s < NS; ++s) ctl[s * RP_CTL_INTS + RP_RUN] = 0;
-        for (size_t k = 0; k < again.size(); ++k) {
-            const size_t s = again[k];
-            int* c = ctl + s * RP_CTL_INTS;
-            const int n = c[RP_N];
-            // the stream's float32 point sets, gathered here from the caller's tables as rp_gather_kernel gathers them (no copy back)
-            {
-                const int w = hint[i_sw + 2 * s], i = hint[i_sw + 2 * s + 1];
-                const vg_relpose_in& a = in[w];
-                int k = 0;
-                for (int j = 0; j < a.n_feat && k < n; ++j) {
-                    const int s0 = a.start[j];
-                    if (!(s0 <= i && s0 + a.nobs[j] - 1 >= a.n_frames - 1)) continue;
-                    const double* r = a.points + 3 * (size_t)a.obs_off[j];
-                    pts[2 * k] = (float)r[3 * (i - s0)]; pts[2 * k + 1] = (float)r[3 * (i - s0) + 1];
-                    pts[2 * cap + 2 * k] = (float)r[3 * (a.n_frames - 1 - s0)]; pts[2 * cap + 2 * k + 1] = (float)r[3 * (a.n_frames - 1 - s0) + 1];
-                    ++k;
-                }
-            }
-            CvRng rng((unsigned long long)-1);
-            int nsched = 0;
-            for (; nsched < FE_RANSAC_MAXIT; ++nsched)
-                if (!get_subset(rng, pts.data(), pts.data() + 2 * cap, n, xs.data() + (k * FE_RANSAC_MAXIT + nsched) * 7, 10000)) break;
-            c[RP_RUN] = 1; c[RP_XS] = (int)k; c[RP_MAXIT] = nsched; c[RP_BEST] = -1; c[RP_NITERS] = 0; c[RP_MAXGOOD] = 0;
         }
         if ((e = hipMemcpyAsync((void*)b.xsched, xs.data(), xs.size() * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail(e);
         if ((e = hipMemcpyAsync(b.ctl, ctl, NS * RP_CTL_INTS * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail(e);

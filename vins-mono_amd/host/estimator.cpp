@@ -129,6 +129,61 @@ void Estimator::repropagate(IntegrationBase* p) {
     vg_pack::preint_from_abi(*p, out);
 }
 
+vector<pair<Vector3d, Vector3d>> FeatureManager::getCorresponding(int frame_count_l, int frame_count_r) {    // feature_manager.cpp:120-140
+    vector<pair<Vector3d, Vector3d>> corres;
+    for (auto& it : feature) {
+        const int end = it.start_frame + (int)it.feature_per_frame.size() - 1;
+        if (it.start_frame <= frame_count_l && end >= frame_count_r) {
+            const int idx_l = frame_count_l - it.start_frame, idx_r = frame_count_r - it.start_frame;
+            corres.push_back(make_pair(it.feature_per_frame[idx_l].point, it.feature_per_frame[idx_r].point));
+        }
+    }
+    return corres;
+}
+
+InitialEXRotation::InitialEXRotation() : frame_count(0) {}       // (ric is the identity; the reference's identity record 0 is never read)
+InitialEXRotation::~InitialEXRotation() { if (own_ && vg_) vg_destroy(vg_); }
+
+bool InitialEXRotation::CalibrationExRotation(vector<pair<Vector3d, Vector3d>> corres, Quaterniond delta_q_imu, Matrix3d& calib_ric_result) {
+    if (!vg_) {
+        if (vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
+        own_ = true;
+    }
+    // the call holds VG_EXROT_MAX_STEPS records, this one included: at the cap the OLDEST is dropped (the reference keeps every record;
+    // a rig that has not turned about two axes in 63 frames goes on with its newest 63)
+    if (records.size() / 27 >= (size_t)VG_EXROT_MAX_STEPS) records.erase(records.begin(), records.begin() + 27);
+    vg_pack::ExrotIn in;
+    vg_pack_exrot(corres, delta_q_imu, records, ric, in);
+    vg_pack::ExrotOut o;
+    if (vg_init_exrot(vg_, 1, &in.in, &o.out) != VG_OK) throw std::runtime_error(std::string("vg_init_exrot: ") + vg_last_error(vg_));
+    status = o.out.status;
+    // a NUMERIC step (no model, a Jacobi past its cap: the reference aborts there) is NOT recorded: the frame is skipped, records and ric
+    // stay as they were, status says so; a later invocation is not built on its identity record
+    if (o.out.status != VG_EXROT_OK) return false;
+    frame_count++;
+    records.insert(records.end(), o.records, o.records + 27);
+    for (int e = 0; e < 9; ++e) ric(e / 3, e % 3) = o.ric[e];
+    for (int e = 0; e < 4; ++e) sigma[e] = o.sigma[e];
+    if (o.out.first_ok < 0) return false;
+    calib_ric_result = ric;
+    return true;
+}
+
+bool Estimator::calibrateExtrinsicRotation() {                  // estimator.cpp:140-156
+    if (ESTIMATE_EXTRINSIC != 2 || frame_count == 0) return false;
+    if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
+    initial_ex_rotation.attach(vg_);
+    vector<pair<Vector3d, Vector3d>> corres = f_manager.getCorresponding(frame_count - 1, frame_count);
+    Matrix3d calib_ric;
+    const bool ok = initial_ex_rotation.CalibrationExRotation(corres, pre_integrations[frame_count]->delta_q, calib_ric);
+    exrot_status = initial_ex_rotation.status;
+    if (!ok) return false;
+    ric[0] = calib_ric;
+    RIC[0] = calib_ric;
+    ESTIMATE_EXTRINSIC = 1;
+    return true;
+}
+
 bool Estimator::relativePose(Matrix3d& relative_R, Vector3d& relative_T, int& l) {                      // estimator.cpp:442-471
     if (!vg_ && vg_create(&vg_) != VG_OK) throw std::runtime_error("vg_create failed: no MI355X / libvinsgpu (no CPU fallback)");
     vg_pack::RelposeIn in;

@@ -44,6 +44,8 @@ struct FeatureManager {
     void removeBackShiftDepth(Matrix3d marg_R, Vector3d marg_P, Matrix3d new_R, Vector3d new_P);
     void removeBack();
     void removeFront(int frame_count);
+    // feature_manager.cpp:120-140: the features seen in both frames, as (point in frame_count_l, point in frame_count_r)
+    vector<pair<Vector3d, Vector3d>> getCorresponding(int frame_count_l, int frame_count_r);
 };
 
 struct IntegrationBase {           // the members IMUFactor reads (factor/integration_base.h:188-208), same types
@@ -78,6 +80,28 @@ struct ImageFrame {                // initial/initial_alignment.h:14-28: what Vi
     map<int, vector<pair<int, Eigen::Matrix<double, 7, 1>>>> points;
 };
 
+// initial/initial_ex_rotation.h: the reference's constructor and CalibrationExRotation signature; every invocation is ONE one-step
+// vg_init_exrot call that carries the records and ric of the invocations before it (what Rc / Rimu / Rc_g / ric are in the reference).
+// Two cases the reference does not have: the call holds VG_EXROT_MAX_STEPS records, so from the 64th invocation on the oldest record is
+// dropped before the call (frame_count goes on counting); a step that comes back VG_EXROT_NUMERIC is not recorded -- the invocation
+// returns false with status set, records / ric / sigma unchanged, and the next frame goes on from the state before it
+class InitialEXRotation {
+  public:
+    InitialEXRotation();
+    ~InitialEXRotation();
+    bool CalibrationExRotation(vector<pair<Vector3d, Vector3d>> corres, Quaterniond delta_q_imu, Matrix3d& calib_ric_result);
+    void attach(vg_handle* h) { if (!own_) vg_ = h; }      // run on the caller's handle instead of one of its own
+    int status = 0;                                  // VG_EXROT_* of the last invocation
+    double sigma[4] = {0, 0, 0, 0};                  // its singular values
+    int frame_count;
+    vector<double> records;                          // Rc | Rimu | Rc_g, 27 doubles per invocation
+    Matrix3d ric;
+
+  private:
+    vg_handle* vg_ = nullptr;
+    bool own_ = false;
+};
+
 class Estimator {
   public:
     enum MarginalizationFlag { MARGIN_OLD = 0, MARGIN_SECOND_NEW = 1 };
@@ -105,6 +129,12 @@ class Estimator {
     // relativePose() chained into initialStructure(l, relative_R, relative_T); when no frame passes: false, marginalization_flag untouched
     // (the reference's "Not enough features or parallax; Move device around", :252-257)
     bool initialStructure();
+    // the ESTIMATE_EXTRINSIC == 2 block of processImage (estimator.cpp:140-156): getCorresponding(frame_count - 1, frame_count) and
+    // pre_integrations[frame_count]->delta_q through initial_ex_rotation; on success ric[0] = RIC[0] = the result and ESTIMATE_EXTRINSIC
+    // = 1.  Returns whether the calibration succeeded in THIS call (false also when the block does not apply).
+    bool calibrateExtrinsicRotation();
+    InitialEXRotation initial_ex_rotation;           // estimator.h:97
+    int exrot_status = 0;                            // VG_EXROT_* of the last calibrateExtrinsicRotation()
     int relpose_status = 0;                          // VG_RELPOSE_* of the last relativePose()
     int sfm_status = 0;                              // VG_SFM_* of the last initialStructure()
     map<double, ImageFrame> all_image_frame;         // estimator.h:101

@@ -37,6 +37,8 @@
 //     Estimator::initialStructure(l, relative_R, relative_T) (vg_init_sfm, then visualInitialAlign) over f_manager.feature and one
 //     all_image_frame map from a file; writes the statuses, every entry's is_key_frame / R / T and what `align` writes (replay_sfm below).
 //
+//   vins_replay exrot <in.bin> <out.txt>
+//     the extrinsic-rotation calibration of processImage, one vg_init_exrot call per frame (replay_exrot below).
 //   vins_replay relpose <in.bin> <out.txt>
 //     Estimator::relativePose(relative_R, relative_T, l) (vg_init_relpose) over f_manager.feature from a file; writes the return value,
 //     the VG_RELPOSE_* status, l, relative_R and relative_T and, when no frame passes, what the zero-argument initialStructure() returns
@@ -495,6 +497,61 @@ static int replay_relpose(const char* in, const char* out) {
     return 0;
 }
 
+// vins_replay exrot <in.bin> <out.txt>: the ESTIMATE_EXTRINSIC == 2 block of processImage (Estimator::calibrateExtrinsicRotation, class
+// InitialEXRotation, vg_pack_exrot) fed ONE FRAME AT A TIME from a file (tests/init_exrot_ref.write_file): int32 'VEX1', S (steps), rows;
+// S + 1 int32 first rows; rows x0 y0 x1 y1; S rows w x y z.  Per step it writes "step <k> <return value> <VG_EXROT_*> <ESTIMATE_EXTRINSIC
+// after>", "ric" with nine numbers and "sigma" with four (17 digits); after a success the block no longer applies, as in the reference, and
+// the remaining steps are written as "skipped <k>"; "calib" is ric[0] at the end.
+static int replay_exrot(const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("exrot file"); return 2; }
+    int hdr[3];
+    rd.i(hdr, 3);
+    if (hdr[0] != 0x31584556) { fprintf(stderr, "not a VEX1 file\n"); return 2; }
+    const int S = hdr[1], rows = hdr[2];
+    if (S < 1 || rows < 0) { fprintf(stderr, "S = %d, rows = %d\n", S, rows); return 2; }
+    std::vector<int> off(S + 1);
+    std::vector<double> corr((size_t)rows * 4 + 4), dq((size_t)S * 4);
+    rd.i(off.data(), S + 1); rd.d(corr.data(), rows * 4); rd.d(dq.data(), S * 4);
+    fclose(rd.f);
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    Estimator est;
+    ESTIMATE_EXTRINSIC = 2;                                     // as readEstimatorParameters leaves the globals for estimate_extrinsic: 2
+    RIC.assign(1, Matrix3d());
+    TIC.assign(1, Vector3d());
+    IntegrationBase ib;
+    for (int k = 0; k < S; ++k) {
+        if (ESTIMATE_EXTRINSIC != 2) { fprintf(o, "skipped %d\n", k); continue; }
+        // the two newest frames of a window: every correspondence is a feature seen in both
+        est.frame_count = 1;
+        est.f_manager.feature.clear();
+        for (int j = off[k]; j < off[k + 1]; ++j) {
+            FeaturePerId f;
+            f.feature_id = j; f.start_frame = 0;
+            FeaturePerFrame a, b;
+            a.point = Vector3d(corr[4 * (size_t)j], corr[4 * (size_t)j + 1], 1.0);
+            b.point = Vector3d(corr[4 * (size_t)j + 2], corr[4 * (size_t)j + 3], 1.0);
+            f.feature_per_frame.push_back(a); f.feature_per_frame.push_back(b);
+            est.f_manager.feature.push_back(f);
+        }
+        ib.delta_q = Quaterniond(dq[4 * (size_t)k], dq[4 * (size_t)k + 1], dq[4 * (size_t)k + 2], dq[4 * (size_t)k + 3]);
+        est.pre_integrations[1] = &ib;
+        const bool ok = est.calibrateExtrinsicRotation();
+        est.pre_integrations[1] = nullptr;
+        fprintf(o, "step %d %d %d %d\nric", k, ok ? 1 : 0, est.exrot_status, ESTIMATE_EXTRINSIC);
+        for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", est.initial_ex_rotation.ric(e / 3, e % 3));
+        fprintf(o, "\nsigma");
+        for (int e = 0; e < 4; ++e) fprintf(o, " %.17g", est.initial_ex_rotation.sigma[e]);
+        fprintf(o, "\n");
+    }
+    fprintf(o, "calib");
+    for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", est.ric[0](e / 3, e % 3));
+    fprintf(o, "\n");
+    fclose(o);
+    return 0;
+}
+
 namespace {
 // the front end of `vio`: one frame through readImage + updateID, returned as the `image` map (features seen at least twice)
 struct FrontEnd {
@@ -780,6 +837,10 @@ int main(int argc, char** argv) {
         try { return replay_align(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay align: %s\n", e.what()); return 1; }
     }
+    if (argc >= 4 && !strcmp(argv[1], "exrot")) {
+        try { return replay_exrot(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay exrot: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "relpose")) {
         try { return replay_relpose(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay relpose: %s\n", e.what()); return 1; }
@@ -788,6 +849,6 @@ int main(int argc, char** argv) {
         try { return replay_sfm(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt>\n");
     return 2;
 }

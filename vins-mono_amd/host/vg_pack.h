@@ -342,6 +342,46 @@ struct RelposeOut {
     }
 };
 
+// ---- initialisation: InitialEXRotation::CalibrationExRotation (vg_init_exrot), ONE step: the correspondences of (frame_count - 1,
+// frame_count), the interval's delta_q, and the state the earlier steps left (records of 27 doubles each, ric); the constants are the
+// reference's (initial_ex_rotation.cpp, cv::findFundamentalMat's defaults)
+struct ExrotIn {
+    int off[2];
+    std::vector<double> corr, prev;
+    double dq[4], ric[9];
+    vg_exrot_in in;
+};
+template <class Corres, class Q, class M3>
+void pack_exrot(const Corres& corres, const Q& delta_q, const std::vector<double>& records, const M3& ric, ExrotIn& p) {
+    p.corr.assign(4 * corres.size() + 4, 0.0);                 // (never empty: the pointer is not NULL)
+    for (size_t i = 0; i < corres.size(); ++i) {
+        p.corr[4 * i] = corres[i].first(0); p.corr[4 * i + 1] = corres[i].first(1);
+        p.corr[4 * i + 2] = corres[i].second(0); p.corr[4 * i + 3] = corres[i].second(1);
+    }
+    p.off[0] = 0; p.off[1] = (int)corres.size();
+    p.dq[0] = delta_q.w(); p.dq[1] = delta_q.x(); p.dq[2] = delta_q.y(); p.dq[3] = delta_q.z();
+    p.prev = records;
+    for (int e = 0; e < 9; ++e) p.ric[e] = ric(e / 3, e % 3);
+    std::memset(&p.in, 0, sizeof(p.in));
+    p.in.struct_size = sizeof(p.in);
+    p.in.n_steps = 1; p.in.corr_off = p.off; p.in.corr = p.corr.data(); p.in.delta_q = p.dq;
+    p.in.n_prev = (int)(records.size() / 27); p.in.prev = p.prev.empty() ? nullptr : p.prev.data(); p.in.ric_prev = p.ric;
+    p.in.ransac_threshold = 3.0; p.in.confidence = 0.99; p.in.min_points = 9;                   // initial_ex_rotation.cpp:71, :79
+    p.in.huber_deg = 5.0; p.in.min_frames = 10; p.in.cov_threshold = 0.25;                      // :30, :60
+}
+struct ExrotOut {
+    vg_exrot_out out;
+    double records[27], ric[9], sigma[4], huber = 0;
+    int ok = 0;
+    ExrotOut() {
+        std::memset(&out, 0, sizeof(out));
+        out.struct_size = sizeof(out);
+        out.records = records; out.ric = ric; out.sigma = sigma; out.huber = &huber; out.ok = &ok;
+    }
+    ExrotOut(const ExrotOut&) = delete;
+    ExrotOut& operator=(const ExrotOut&) = delete;
+};
+
 // ================================================================================================================== front end
 
 // reduceVector (feature_tracker.cpp:13-29) for any element type
@@ -510,6 +550,11 @@ void vg_pack_sfm(const Features& features, const Map& frames, const double* stam
 template <class Features>
 void vg_pack_relpose(const Features& features, int n_frames, vg_pack::RelposeIn& p) {
     vg_pack::pack_relpose(features, n_frames, p);
+}
+// (the packer of vg_init_exrot under the name the integration guide uses)
+template <class Corres, class Q, class M3>
+void vg_pack_exrot(const Corres& corres, const Q& delta_q, const std::vector<double>& records, const M3& ric, vg_pack::ExrotIn& p) {
+    vg_pack::pack_exrot(corres, delta_q, records, ric, p);
 }
 // (the packer of vg_init_align under the name the integration guide uses)
 template <class Map, class V3>
