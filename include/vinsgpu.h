@@ -31,7 +31,8 @@ extern "C" {
                              * 12: vg_config::device is 0 = current device / k + 1 = device k, vg_config::imu_info_mode, vg_ba_set_imu_info_mode
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
-                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot) */
+                             * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot;
+                             * vg_kf_configure / _add / _get / _set / _match) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -1304,6 +1305,109 @@ int vg_vio_begin(vg_handle* h, int flags);
 int vg_vio_step_async(vg_handle* h, int n, const vg_vio_in* in /* [n] */, vg_vio_out* out /* [n] */);
 int vg_vio_get_frame(vg_handle* h, int window, int cap, int* n_obs, int* feature_id, double* obs7);
 int vg_vio_end(vg_handle* h);
+
+/* ---- Loop closure: keyframe BRIEF descriptors and matching (added within ABI 12, nothing existing changed) ----------------------------
+ * The integer-exact, batchable part of the pose graph's KeyFrame (pose_graph/src/keyframe.cpp): computeWindowBRIEFPoint and
+ * computeBRIEFPoint with keypoints_norm (vg_kf_add), searchByBRIEFDes with the reduceVector step of findConnection:301-312
+ * (vg_kf_match).  NOT here: PnPRANSAC (cv::solvePnPRansac), the loop_info arithmetic behind it, DBoW2 loop detection, the 4-DoF
+ * pose-graph optimisation, thumbnails and debug images.  Independent of vg_fe_configure: the pose graph's image is not the front
+ * end's current frame.
+ *
+ * DVision::BRIEF is read from the reference as the definition.  cv::GaussianBlur and cv::FAST are RECALLED, NOT PINNED (no OpenCV to
+ * compare with; SURVEY.md Appendix B.6 and DESIGN.md section 4 list them).  Everything is integer or float32-exact:
+ *   blur    cv::GaussianBlur(img, im, Size(9, 9), 2, 2) on CV_8UC1, BORDER_REFLECT_101, as OpenCV's fixed-point separable path:
+ *           taps k = 7 17 32 46 52 46 32 17 7 (sum 256), out(x, y) = (sum_j k_j (sum_i k_i p(x + i - 4, y + j - 4)) + 32768) >> 16,
+ *           indices reflected without repeating the edge pixel (-1 -> 1, W -> W - 2)
+ *   FAST    cv::FAST(image, keypoints, 20, true) on the image that is NOT blurred.  Ring (dx, dy) clockwise from the top: (0,-3) (1,-3)
+ *           (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3); d_k = v - ring_k; A = max
+ *           over the 16 arcs of 9 contiguous ring pixels of min d_k, B the same for -d_k.  A pixel with 3 <= x < W - 3, 3 <= y < H - 3
+ *           is a corner iff max(A, B) > 20, its score max(A, B) - 1 (cornerScore<16> of a pixel that passed); every other pixel scores
+ *           0.  Kept iff the score is strictly greater than each of its 8 neighbours'.  Listed row-major (y, then x), pt = (float x,
+ *           float y), the score as the response.  The ORDER is part of the result: the match breaks ties by index.
+ *   BRIEF   DVision::BRIEF::compute (BRIEF.cpp:39-106) with the 256 tests of `pattern` on the blurred image: x1 = (int)(pt.x +
+ *           (float)pattern_x1[i]) (a float32 add, truncation toward zero: a coordinate in (-1, 0) is 0 and inside), likewise y1 x2 y2; bit
+ *           i = all four inside the image && im(y1, x1) < im(y2, x2).  A descriptor is 4 little-endian 64-bit words, bit i in word i / 64
+ *           at position i % 64.
+ *   lift    keypoints_norm = vg_fe_lift of the entry's camera on the keypoints.
+ *   match   searchInAera: for window descriptor w the smallest (Hamming distance, index) among the old record's descriptors with
+ *           distance < 128: best_dist, best_idx (128, -1: none); status = best_idx >= 0 && best_dist < 80; matched_2d_old(_norm) = the
+ *           old pt / norm at best_idx where status, else (0, 0).  The compacted lists are the status-1 entries in window order.
+ *
+ * vg_kf_configure  allocates n_slots resident keyframe records: max_keypoints x (descriptor, pt, norm, score), max_window_points x
+ *                  (descriptor, pt), the counts.  pattern: int16[4][256] = x1 y1 x2 y2.  Calling it again replaces everything.
+ *                  Refused: width or height < 7, max_keypoints outside 1 .. VG_KF_MAX_KEYPOINTS, max_window_points outside 1 ..
+ *                  VG_KF_MAX_WINDOW, n_slots < 1, pattern NULL or an offset outside +-127.
+ * vg_kf_add        n keyframes in one call: one upload (images, cameras, window points), seven launches over the batch, one download.
+ *                  A frame with more than max_keypoints corners keeps the first max_keypoints in row-major order, reports the true
+ *                  count in n_keypoints and status VG_KF_TRUNCATED (the reference has no cap).  The output arrays are optional
+ *                  (NULL: not copied); their capacities are max_keypoints / max_window_points.
+ * vg_kf_get / set  download a record / upload one whole (the KeyFrame constructor of loadPoseGraph).  vg_kf_get fills the counts and the
+ *                  arrays whose pointers are non-NULL; vg_kf_set takes every array of a non-zero count.
+ * vg_kf_match      n_pairs of (current slot, old slot), pairs may share slots: the current record's window descriptors against the old
+ *                  record's keypoint descriptors.  An old record without keypoints gives all-zero status.  One launch, one download.
+ * Refused with VG_ERR_BAD_ARG before anything is touched (vg_last_error says why): a handle without vg_kf_configure, a wrong struct_size,
+ * a slot out of range or (get, match) never filled, the same slot twice in one vg_kf_add, n_window or a count of vg_kf_set above its
+ * capacity, a NULL image, stride < width, a NULL table of a non-zero count, a camera vg_fe_set_camera would refuse. */
+#define VG_KF_MAX_KEYPOINTS 65535    /* the match key is (distance << 16) | index */
+#define VG_KF_MAX_WINDOW 1024
+#define VG_KF_OK 0
+#define VG_KF_TRUNCATED 1
+#define VG_KF_ADD_LAUNCHES 7         /* blur, FAST score, non-max masks, scan, scatter, lift, BRIEF */
+typedef struct vg_kf_in {
+    int struct_size;             /* sizeof(vg_kf_in) */
+    int slot;
+    const uint8_t* img;          /* height rows of width raw 8-bit pixels, `stride` bytes apart */
+    int stride;
+    int n_window;                /* point_2d_uv.size() */
+    const float* window_xy;      /* n_window x 2: point_2d_uv */
+    vg_fe_camera camera;         /* m_camera of keypoints_norm */
+} vg_kf_in;
+typedef struct vg_kf_out {
+    int struct_size;             /* sizeof(vg_kf_out) */
+    int n_keypoints;             /* corners cv::FAST lists: the TRUE count, the record keeps min(n_keypoints, max_keypoints) */
+    int status;                  /* VG_KF_OK / VG_KF_TRUNCATED */
+    int n_kept;
+    float* keypoints_xy;         /* [max_keypoints][2] or NULL */
+    uint8_t* scores;             /* [max_keypoints] */
+    float* norm_xy;              /* [max_keypoints][2] */
+    uint64_t* descriptors;       /* [max_keypoints][4] */
+    uint64_t* window_descriptors;/* [max_window_points][4] */
+    float* device_ms;            /* out[0] only: VG_KF_ADD_LAUNCHES event intervals of the batch, or NULL */
+} vg_kf_out;
+typedef struct vg_kf_record {
+    int struct_size;             /* sizeof(vg_kf_record) */
+    int n_keypoints, n_window;   /* what the record holds */
+    int n_true;                  /* corners before the cap (vg_kf_set: 0 means n_keypoints) */
+    float* keypoints_xy;
+    uint8_t* scores;
+    float* norm_xy;
+    uint64_t* descriptors;
+    float* window_xy;
+    uint64_t* window_descriptors;
+} vg_kf_record;
+typedef struct vg_kf_pair {
+    int struct_size;             /* sizeof(vg_kf_pair) */
+    int cur_slot, old_slot;
+} vg_kf_pair;
+typedef struct vg_kf_match_out {
+    int struct_size;             /* sizeof(vg_kf_match_out) */
+    int n_window;                /* window points of the current record */
+    int n_matched;               /* entries of the compacted lists; the caller compares it with MIN_LOOP_NUM */
+    int* best_idx;               /* [max_window_points] each, or NULL */
+    int* best_dist;
+    uint8_t* status;
+    float* matched_2d_old;       /* [..][2] */
+    float* matched_2d_old_norm;  /* [..][2] */
+    int* matched_index;          /* the surviving window indices, ascending: gathers matched_2d_cur, point_3d, point_id */
+    float* matched_old_xy;       /* [..][2] compacted */
+    float* matched_old_norm;     /* [..][2] compacted */
+    float* device_ms;            /* out[0] only: the launch's event interval, or NULL */
+} vg_kf_match_out;
+int vg_kf_configure(vg_handle* h, int width, int height, int max_keypoints, int max_window_points, int n_slots, const int16_t* pattern);
+int vg_kf_add(vg_handle* h, int n, const vg_kf_in* in /* [n] */, vg_kf_out* out /* [n] */);
+int vg_kf_get(vg_handle* h, int slot, vg_kf_record* rec);
+int vg_kf_set(vg_handle* h, int slot, const vg_kf_record* rec);
+int vg_kf_match(vg_handle* h, int n_pairs, const vg_kf_pair* in /* [n_pairs] */, vg_kf_match_out* out /* [n_pairs] */);
 
 #ifdef __cplusplus
 }

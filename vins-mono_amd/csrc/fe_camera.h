@@ -12,6 +12,7 @@
 // (-ffp-contract=off, or a target without fused multiply-add): a contracted a * b + c rounds once.
 #pragma once
 #include <math.h>
+#include <cmath>
 
 #if defined(__HIPCC__) || defined(VINS_SIMT)
 #define FE_CAM_FN __host__ __device__ __forceinline__
@@ -119,4 +120,20 @@ FE_CAM_FN void fe_cam_lift_xy(const FeCamera& c, float px, float py, float& ox, 
     fe_cam_lift(c, px, py, x, y, z);
     if (c.model != FE_CAM_PINHOLE) { ox = (float)(x / z); oy = (float)(y / z); }
     else { ox = (float)x; oy = (float)y; }
+}
+
+// a caller's vg_fe_camera (include/vinsgpu.h; a template so that this header needs no other) -> FeCamera, or the reason it is refused:
+// the rules of vg_fe_set_camera, vg_fe_lift and vg_kf_add
+template <typename VgCamera>
+inline const char* fe_camera_check(const VgCamera* in, FeCamera* out) {
+    if (in->struct_size != (int)sizeof(VgCamera)) return "struct_size is not sizeof(vg_fe_camera)";
+    if (in->model != FE_CAM_PINHOLE && in->model != FE_CAM_MEI && in->model != FE_CAM_KB) return "unknown camera model";
+    for (int i = 0; i < 8; ++i)
+        if (!std::isfinite(in->p[i])) return "a camera parameter is not finite";
+    if (in->model == FE_CAM_MEI && !std::isfinite(in->xi)) return "xi is not finite";
+    if (in->p[0] == 0.0 || in->p[1] == 0.0) return "a zero focal length (p[0] / p[1])";
+    out->model = in->model;
+    for (int i = 0; i < 8; ++i) out->p[i] = in->p[i];
+    out->xi = in->model == FE_CAM_MEI ? in->xi : 0.0;
+    return nullptr;
 }

@@ -576,20 +576,7 @@ static FeCamera fe_pinhole(const double* intr) {
 // the camera stream `c` lifts with: the one vg_fe_set_camera gave it, else the pinhole of the frame's intr
 static FeCamera fe_stream_camera(const FeState* s, int c, const double* intr) { return s->cam_set[c] ? s->cam[c] : fe_pinhole(intr); }
 
-// a caller's vg_fe_camera -> FeCamera, or the reason it is refused
-static const char* fe_camera_check(const vg_fe_camera* in, FeCamera* out) {
-    if (in->struct_size != (int)sizeof(vg_fe_camera)) return "struct_size is not sizeof(vg_fe_camera)";
-    if (in->model != VG_CAM_PINHOLE && in->model != VG_CAM_MEI && in->model != VG_CAM_KANNALA_BRANDT) return "unknown camera model";
-    for (int i = 0; i < 8; ++i)
-        if (!std::isfinite(in->p[i])) return "a camera parameter is not finite";
-    if (in->model == VG_CAM_MEI && !std::isfinite(in->xi)) return "xi is not finite";
-    if (in->p[0] == 0.0 || in->p[1] == 0.0) return "a zero focal length (p[0] / p[1])";
-    out->model = in->model == VG_CAM_MEI ? FE_CAM_MEI : in->model == VG_CAM_KANNALA_BRANDT ? FE_CAM_KB : FE_CAM_PINHOLE;
-    for (int i = 0; i < 8; ++i) out->p[i] = in->p[i];
-    out->xi = in->model == VG_CAM_MEI ? in->xi : 0.0;
-    return nullptr;
-}
-
+// (fe_camera_check, a caller's vg_fe_camera -> FeCamera or the reason it is refused: fe_camera.h, shared with vg_kf_add)
 extern "C" int vg_fe_set_camera(vg_handle* h, int cam, const vg_fe_camera* camera) {
     if (!h) return VG_ERR_BAD_ARG;
     if (!h->fe) { h->err = "vg_fe_set_camera: the handle has no front end (vg_fe_configure)"; return VG_ERR_BAD_ARG; }

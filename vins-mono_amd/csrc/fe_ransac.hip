@@ -409,3 +409,6 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
 
 // ---- vg_init_exrot: the same RANSAC kernels with a (window, step) pair as the stream, the rotation and calibration stages, the host entry
 #include "init_exrot.h"
+
+// ---- vg_kf_*: keyframe BRIEF descriptors and matching for the pose graph (blur, FAST, BRIEF, the lift, Hamming matching), the host entries
+#include "kf_brief.h"

@@ -11,6 +11,8 @@ extern "C" void ba_graph_release(vg_handle* h);
 extern "C" void ba_seq_release(vg_handle* h);
 // (weak: builds without csrc/vg_rccl.hip — the CPU emulation of tests/simt — have no communicator to release)
 extern "C" int vg_ba_rccl_finalize(vg_handle* h) __attribute__((weak));
+// (weak: a program linked without csrc/fe_ransac.hip has no keyframe records to release)
+extern "C" void kf_release(vg_handle* h) __attribute__((weak));
 
 extern "C" int vg_abi_version(void) { return VG_ABI_VERSION; }
 
@@ -78,6 +80,7 @@ extern "C" int vg_destroy(vg_handle* h) {
     h->ba.h_out.release(); h->ba.h_iout.release(); h->ba.h_mout.release(); h->ba.h_miout.release();
     (void)hipFree(P.mout); (void)hipFree(P.miout); (void)hipFree(P.mscr); (void)hipFree(P.rb1); (void)hipFree(P.rb2);
     if (h->fe) fe_state_destroy(h->fe);
+    if (kf_release) kf_release(h);
     (void)hipFree(h->ransac_buf);
     (void)hipFree(h->relpose_buf);
     (void)hipFree(h->relpose_tab);

@@ -161,4 +161,5 @@ struct vg_handle {
     size_t relpose_cap = 0;
     void* relpose_tab = nullptr;                  // its resident RANSAC tables: the n-only schedules and the bounds for n = 15 .. relpose_nmax
     int relpose_nmax = 0;
+    void* kf = nullptr;                           // KfState of vg_kf_configure (csrc/kf_brief.h): the resident keyframe records
 };

@@ -568,3 +568,172 @@ class FrontEnd:
         out = np.zeros((self.H, self.W), np.float32)
         self.hd._chk(self.lib.vg_fe_get_eig(self.h, cam, out.ctypes.data_as(_f4)), "vg_fe_get_eig")
         return out
+
+
+# ---- loop closure: keyframe BRIEF descriptors and matching (vg_kf_*) -------------------------------------------------------------------
+_u64 = C.POINTER(C.c_uint64)
+KF_OK, KF_TRUNCATED = 0, 1
+KF_ADD_LAUNCHES = 7
+KF_KERNELS = ("blur", "fast_score", "nonmax_masks", "scan", "scatter", "lift", "brief")
+
+
+class KfIn(C.Structure):
+    """vg_kf_in (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("slot", C.c_int), ("img", _u8), ("stride", C.c_int), ("n_window", C.c_int), ("window_xy", _f4),
+                ("camera", Camera)]
+
+
+class KfOut(C.Structure):
+    """vg_kf_out (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("n_keypoints", C.c_int), ("status", C.c_int), ("n_kept", C.c_int), ("keypoints_xy", _f4),
+                ("scores", _u8), ("norm_xy", _f4), ("descriptors", _u64), ("window_descriptors", _u64), ("device_ms", _f4)]
+
+
+class KfRecord(C.Structure):
+    """vg_kf_record (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("n_keypoints", C.c_int), ("n_window", C.c_int), ("n_true", C.c_int), ("keypoints_xy", _f4),
+                ("scores", _u8), ("norm_xy", _f4), ("descriptors", _u64), ("window_xy", _f4), ("window_descriptors", _u64)]
+
+
+class KfPair(C.Structure):
+    """vg_kf_pair (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("cur_slot", C.c_int), ("old_slot", C.c_int)]
+
+
+class KfMatchOut(C.Structure):
+    """vg_kf_match_out (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("n_window", C.c_int), ("n_matched", C.c_int), ("best_idx", _i4), ("best_dist", _i4), ("status", _u8),
+                ("matched_2d_old", _f4), ("matched_2d_old_norm", _f4), ("matched_index", _i4), ("matched_old_xy", _f4),
+                ("matched_old_norm", _f4), ("device_ms", _f4)]
+
+
+def read_brief_pattern(path):
+    """The four integer lists x1 y1 x2 y2 of an OpenCV-FileStorage yml (support_files/brief_pattern.yml) as int16 [4, 256]."""
+    lists, key = {}, None
+    with open(path) as f:
+        for line in f:
+            t = line.strip()
+            if t.endswith(":") and not t.startswith("-"):
+                key = t[:-1]
+                lists[key] = []
+            elif t.startswith("- ") and key is not None:
+                lists[key].append(int(t[2:]))
+    return np.array([lists[k] for k in ("x1", "y1", "x2", "y2")], np.int16)
+
+
+class KeyFrames:
+    """Resident keyframe records of the pose graph on one vg_handle (ba.Handle): vg_kf_configure / _add / _get / _set / _match.
+    Independent of FrontEnd.  Arrays in and out are NumPy; descriptors are uint64 [n, 4]."""
+
+    def __init__(self, handle, width, height, max_keypoints, max_window_points, n_slots, pattern):
+        self.hd, self.lib, self.h = handle, handle.lib, handle.h
+        L = self.lib
+        L.vg_kf_configure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int16)]
+        L.vg_kf_add.argtypes = [C.c_void_p, C.c_int, C.POINTER(KfIn), C.POINTER(KfOut)]
+        L.vg_kf_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(KfRecord)]
+        L.vg_kf_set.argtypes = [C.c_void_p, C.c_int, C.POINTER(KfRecord)]
+        L.vg_kf_match.argtypes = [C.c_void_p, C.c_int, C.POINTER(KfPair), C.POINTER(KfMatchOut)]
+        self.configure(width, height, max_keypoints, max_window_points, n_slots, pattern)
+
+    def configure(self, width, height, max_keypoints, max_window_points, n_slots, pattern):
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int16).reshape(4, 256)
+        self.hd._chk(self.lib.vg_kf_configure(self.h, int(width), int(height), int(max_keypoints), int(max_window_points), int(n_slots),
+                                              None if pat is None else pat.ctypes.data_as(C.POINTER(C.c_int16))), "vg_kf_configure")
+        self.W, self.H, self.MK, self.MW, self.NS = int(width), int(height), int(max_keypoints), int(max_window_points), int(n_slots)
+
+    def add(self, slots, images, cameras, window_xy, arrays=True, timed=False):
+        """vg_kf_add for len(slots) keyframes in one call.  images[i]: uint8 [H, W] (any row stride); cameras[i]: a Camera;
+        window_xy[i]: float32 [n_window, 2].  Returns one dict per entry: n_keypoints (the true count), status, and with `arrays`
+        keypoints, scores, norm, descriptors, window_descriptors; with `timed` the first dict also holds device_ms [KF_ADD_LAUNCHES]."""
+        n = len(slots)
+        ins, outs, keep = (KfIn * n)(), (KfOut * n)(), []
+        ms = np.zeros(KF_ADD_LAUNCHES, np.float32)
+        for i in range(n):
+            img = np.asarray(images[i])
+            if img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1:
+                img = np.ascontiguousarray(img, np.uint8)
+            assert img.shape == (self.H, self.W)
+            w = np.ascontiguousarray(window_xy[i], np.float32).reshape(-1, 2)
+            a, o = ins[i], outs[i]
+            a.struct_size, a.slot, a.img, a.stride = C.sizeof(KfIn), int(slots[i]), img.ctypes.data_as(_u8), img.strides[0]
+            a.n_window, a.window_xy, a.camera = len(w), w.ctypes.data_as(_f4), cameras[i]
+            o.struct_size = C.sizeof(KfOut)
+            bufs = None
+            if arrays:
+                bufs = (np.zeros((self.MK, 2), np.float32), np.zeros(self.MK, np.uint8), np.zeros((self.MK, 2), np.float32),
+                        np.zeros((self.MK, 4), np.uint64), np.zeros((self.MW, 4), np.uint64))
+                o.keypoints_xy, o.scores, o.norm_xy = bufs[0].ctypes.data_as(_f4), bufs[1].ctypes.data_as(_u8), bufs[2].ctypes.data_as(_f4)
+                o.descriptors, o.window_descriptors = bufs[3].ctypes.data_as(_u64), bufs[4].ctypes.data_as(_u64)
+            keep.append((img, w, bufs))
+        if timed and n:
+            outs[0].device_ms = ms.ctypes.data_as(_f4)
+        self.hd._chk(self.lib.vg_kf_add(self.h, n, ins, outs), "vg_kf_add")
+        res = []
+        for i in range(n):
+            o, (_, w, bufs) = outs[i], keep[i]
+            d = {"n_keypoints": o.n_keypoints, "status": o.status, "n_kept": o.n_kept}
+            if arrays:
+                k = o.n_kept
+                d.update(keypoints=bufs[0][:k].copy(), scores=bufs[1][:k].copy(), norm=bufs[2][:k].copy(), descriptors=bufs[3][:k].copy(),
+                         window_descriptors=bufs[4][:len(w)].copy())
+            res.append(d)
+        if timed and n:
+            res[0]["device_ms"] = ms.copy()
+        return res
+
+    def get(self, slot):
+        """vg_kf_get: the record of `slot` as a dict of arrays"""
+        r = KfRecord()
+        r.struct_size = C.sizeof(KfRecord)
+        b = (np.zeros((self.MK, 2), np.float32), np.zeros(self.MK, np.uint8), np.zeros((self.MK, 2), np.float32), np.zeros((self.MK, 4), np.uint64),
+             np.zeros((self.MW, 2), np.float32), np.zeros((self.MW, 4), np.uint64))
+        r.keypoints_xy, r.scores, r.norm_xy = b[0].ctypes.data_as(_f4), b[1].ctypes.data_as(_u8), b[2].ctypes.data_as(_f4)
+        r.descriptors, r.window_xy, r.window_descriptors = b[3].ctypes.data_as(_u64), b[4].ctypes.data_as(_f4), b[5].ctypes.data_as(_u64)
+        self.hd._chk(self.lib.vg_kf_get(self.h, int(slot), C.byref(r)), "vg_kf_get")
+        k, w = r.n_keypoints, r.n_window
+        return {"n_true": r.n_true, "keypoints": b[0][:k].copy(), "scores": b[1][:k].copy(), "norm": b[2][:k].copy(), "descriptors": b[3][:k].copy(),
+                "window_xy": b[4][:w].copy(), "window_descriptors": b[5][:w].copy()}
+
+    def set(self, slot, keypoints, scores, norm, descriptors, window_xy, window_descriptors, n_true=0):
+        """vg_kf_set: upload a whole record (stored keypoints and descriptors, or planted ones)"""
+        kp = np.ascontiguousarray(keypoints, np.float32).reshape(-1, 2)
+        sc = np.ascontiguousarray(scores, np.uint8).reshape(-1)
+        nm = np.ascontiguousarray(norm, np.float32).reshape(-1, 2)
+        de = np.ascontiguousarray(descriptors, np.uint64).reshape(-1, 4)
+        wx = np.ascontiguousarray(window_xy, np.float32).reshape(-1, 2)
+        wd = np.ascontiguousarray(window_descriptors, np.uint64).reshape(-1, 4)
+        assert len(kp) == len(sc) == len(nm) == len(de) and len(wx) == len(wd)
+        r = KfRecord()
+        r.struct_size, r.n_keypoints, r.n_window, r.n_true = C.sizeof(KfRecord), len(kp), len(wx), int(n_true)
+        r.keypoints_xy, r.scores, r.norm_xy = kp.ctypes.data_as(_f4), sc.ctypes.data_as(_u8), nm.ctypes.data_as(_f4)
+        r.descriptors, r.window_xy, r.window_descriptors = de.ctypes.data_as(_u64), wx.ctypes.data_as(_f4), wd.ctypes.data_as(_u64)
+        self.hd._chk(self.lib.vg_kf_set(self.h, int(slot), C.byref(r)), "vg_kf_set")
+
+    def match(self, pairs, timed=False):
+        """vg_kf_match for a list of (current slot, old slot).  One dict per pair: best_idx, best_dist, status, matched_2d_old,
+        matched_2d_old_norm (per window point) and the compacted matched_index, matched_old_xy, matched_old_norm, n_matched."""
+        n = len(pairs)
+        ins, outs, keep = (KfPair * n)(), (KfMatchOut * n)(), []
+        ms = np.zeros(1, np.float32)
+        for i, (c, o) in enumerate(pairs):
+            ins[i].struct_size, ins[i].cur_slot, ins[i].old_slot = C.sizeof(KfPair), int(c), int(o)
+            b = (np.zeros(self.MW, np.int32), np.zeros(self.MW, np.int32), np.zeros(self.MW, np.uint8), np.zeros((self.MW, 2), np.float32),
+                 np.zeros((self.MW, 2), np.float32), np.zeros(self.MW, np.int32), np.zeros((self.MW, 2), np.float32), np.zeros((self.MW, 2), np.float32))
+            q = outs[i]
+            q.struct_size = C.sizeof(KfMatchOut)
+            q.best_idx, q.best_dist, q.status = b[0].ctypes.data_as(_i4), b[1].ctypes.data_as(_i4), b[2].ctypes.data_as(_u8)
+            q.matched_2d_old, q.matched_2d_old_norm, q.matched_index = b[3].ctypes.data_as(_f4), b[4].ctypes.data_as(_f4), b[5].ctypes.data_as(_i4)
+            q.matched_old_xy, q.matched_old_norm = b[6].ctypes.data_as(_f4), b[7].ctypes.data_as(_f4)
+            keep.append(b)
+        if timed and n:
+            outs[0].device_ms = ms.ctypes.data_as(_f4)
+        self.hd._chk(self.lib.vg_kf_match(self.h, n, ins, outs), "vg_kf_match")
+        res = []
+        for i in range(n):
+            b, w, m = keep[i], outs[i].n_window, outs[i].n_matched
+            res.append({"n_window": w, "n_matched": m, "best_idx": b[0][:w].copy(), "best_dist": b[1][:w].copy(), "status": b[2][:w].copy(),
+                        "matched_2d_old": b[3][:w].copy(), "matched_2d_old_norm": b[4][:w].copy(), "matched_index": b[5][:m].copy(),
+                        "matched_old_xy": b[6][:m].copy(), "matched_old_norm": b[7][:m].copy()})
+        if timed and n:
+            res[0]["device_ms"] = float(ms[0])
+        return res

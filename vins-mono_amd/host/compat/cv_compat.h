@@ -14,6 +14,11 @@ struct Point2f {
     Point2f() : x(0), y(0) {}
     Point2f(float x_, float y_) : x(x_), y(y_) {}
 };
+// (the two members the pose graph's KeyFrame reads)
+struct KeyPoint {
+    Point2f pt;
+    float response = 0.f;
+};
 typedef unsigned char uchar;
 enum { CV_8UC1 = 0 };
 // ref-counted 8-bit single-channel image view

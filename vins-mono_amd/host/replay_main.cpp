@@ -37,6 +37,10 @@
 //     Estimator::initialStructure(l, relative_R, relative_T) (vg_init_sfm, then visualInitialAlign) over f_manager.feature and one
 //     all_image_frame map from a file; writes the statuses, every entry's is_key_frame / R / T and what `align` writes (replay_sfm below).
 //
+//   vins_replay kf <in.bin> <out.txt> <brief_pattern.yml>
+//     keyframes and loop candidates of the pose graph through class KeyFrame (host/keyframe.h, vg_kf_*; replay_kf below).
+//   vins_replay kf_pattern <brief_pattern.yml>
+//     host only: prints the four lists of 256 integers that BriefExtractor reads from the yml.
 //   vins_replay exrot <in.bin> <out.txt>
 //     the extrinsic-rotation calibration of processImage, one vg_init_exrot call per frame (replay_exrot below).
 //   vins_replay relpose <in.bin> <out.txt>
@@ -55,6 +59,7 @@
 #include <vector>
 #include "estimator.h"
 #include "feature_tracker.h"
+#include "keyframe.h"
 #include "resident_estimator.h"
 #include "vg_pack.h"
 
@@ -497,6 +502,78 @@ static int replay_relpose(const char* in, const char* out) {
     return 0;
 }
 
+// vins_replay kf <in.bin> <out.txt> <brief_pattern.yml>: class KeyFrame (host/keyframe.h, BriefExtractor, vg_pack_kf) over a file of
+// keyframes and pairs (tests/kf_brief_ref.write_replay_file): int32 'KFR1', W, H, max_keypoints, max_window_points, n_frames, n_pairs; per
+// frame int32 n_window, the points (float32), int32 camera model, p[8] and xi (float64), the image; then the pairs (current, old).  Writes
+// per keyframe "kf <i> <true count> <status> <kept> <n_window>", a "k" line per keypoint (x y score, the norm's bits, the four words) and a
+// "w" line per window descriptor; per pair "pair <p> <cur> <old> <n_matched> <findConnection's return value>", an "s" line per window
+// point (status, best index and distance, the matched point and norm as bits) and an "m" line per survivor of reduceVector.
+static unsigned kf_bits(float v) { unsigned u; memcpy(&u, &v, 4); return u; }
+static int replay_kf(const char* in, const char* out, const char* pattern_file) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("kf file"); return 2; }
+    int hdr[7];
+    rd.i(hdr, 7);
+    if (hdr[0] != 0x3152464B) { fprintf(stderr, "not a KFR1 file\n"); return 2; }
+    const int W = hdr[1], H = hdr[2], MK = hdr[3], MW = hdr[4], NF = hdr[5], NP = hdr[6];
+    if (W < 1 || H < 1 || NF < 1 || NP < 0) { fprintf(stderr, "bad header\n"); return 2; }
+    vg_handle* h = nullptr;
+    if (vg_create(&h) != VG_OK) { fprintf(stderr, "vg_create failed\n"); return 1; }
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    {
+        BriefExtractor extractor(pattern_file);
+        KeyFrame::configure(h, extractor, W, H, MK, MW, NF);
+        std::vector<std::unique_ptr<KeyFrame>> kfs;
+        for (int i = 0; i < NF; ++i) {
+            int nw = 0, model = 0;
+            rd.i(&nw, 1);
+            std::vector<cv::Point2f> uv((size_t)nw);
+            if (nw && fread(uv.data(), sizeof(cv::Point2f), nw, rd.f) != (size_t)nw) throw std::runtime_error("kf file truncated");
+            rd.i(&model, 1);
+            vg_fe_camera cam;
+            memset(&cam, 0, sizeof(cam));
+            cam.struct_size = (int)sizeof(cam); cam.model = model;
+            rd.d(cam.p, 8); rd.d(&cam.xi, 1);
+            cv::Mat img(H, W, cv::CV_8UC1, (uchar)0);
+            if (fread(img.data, 1, (size_t)W * H, rd.f) != (size_t)W * H) throw std::runtime_error("kf file truncated");
+            kfs.emplace_back(new KeyFrame(h, i, 0.05 * i, i, img, uv, cam));
+            const KeyFrame& k = *kfs.back();
+            fprintf(o, "kf %d %d %d %d %d\n", i, k.n_true, k.kf_status, (int)k.keypoints.size(), (int)k.window_brief_descriptors.size());
+            for (size_t q = 0; q < k.keypoints.size(); ++q) {
+                const BRIEF::bitset& d = k.brief_descriptors[q];
+                fprintf(o, "k %.9g %.9g %d %08x %08x %016llx %016llx %016llx %016llx\n", k.keypoints[q].pt.x, k.keypoints[q].pt.y, (int)k.keypoints[q].response,
+                        kf_bits(k.keypoints_norm[q].pt.x), kf_bits(k.keypoints_norm[q].pt.y), (unsigned long long)d[0], (unsigned long long)d[1],
+                        (unsigned long long)d[2], (unsigned long long)d[3]);
+            }
+            for (const BRIEF::bitset& d : k.window_brief_descriptors)
+                fprintf(o, "w %016llx %016llx %016llx %016llx\n", (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[3]);
+        }
+        for (int p = 0; p < NP; ++p) {
+            int pr[2];
+            rd.i(pr, 2);
+            if (pr[0] < 0 || pr[0] >= NF || pr[1] < 0 || pr[1] >= NF) throw std::runtime_error("a pair names no keyframe");
+            KeyFrame& cur = *kfs[pr[0]];
+            std::vector<cv::Point2f> m_old, m_old_norm, c_cur, c_old, c_old_norm;
+            std::vector<uchar> status;
+            std::vector<int> index;
+            cur.searchByBRIEFDes(m_old, m_old_norm, status, *kfs[pr[1]]);
+            const bool ok = cur.findConnection(*kfs[pr[1]], c_cur, c_old, c_old_norm, index);
+            fprintf(o, "pair %d %d %d %d %d\n", p, pr[0], pr[1], (int)index.size(), ok ? 1 : 0);
+            for (size_t w = 0; w < status.size(); ++w)
+                fprintf(o, "s %d %d %d %08x %08x %08x %08x\n", (int)status[w], cur.best_idx[w], cur.best_dist[w], kf_bits(m_old[w].x), kf_bits(m_old[w].y),
+                        kf_bits(m_old_norm[w].x), kf_bits(m_old_norm[w].y));
+            for (size_t k = 0; k < index.size(); ++k)
+                fprintf(o, "m %d %08x %08x %08x %08x %08x %08x\n", index[k], kf_bits(c_cur[k].x), kf_bits(c_cur[k].y), kf_bits(c_old[k].x), kf_bits(c_old[k].y),
+                        kf_bits(c_old_norm[k].x), kf_bits(c_old_norm[k].y));
+        }
+    }
+    fclose(rd.f);
+    fclose(o);
+    vg_destroy(h);
+    return 0;
+}
+
 // vins_replay exrot <in.bin> <out.txt>: the ESTIMATE_EXTRINSIC == 2 block of processImage (Estimator::calibrateExtrinsicRotation, class
 // InitialEXRotation, vg_pack_exrot) fed ONE FRAME AT A TIME from a file (tests/init_exrot_ref.write_file): int32 'VEX1', S (steps), rows;
 // S + 1 int32 first rows; rows x0 y0 x1 y1; S rows w x y z.  Per step it writes "step <k> <return value> <VG_EXROT_*> <ESTIMATE_EXTRINSIC
@@ -837,6 +914,19 @@ int main(int argc, char** argv) {
         try { return replay_align(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay align: %s\n", e.what()); return 1; }
     }
+    if (argc >= 3 && !strcmp(argv[1], "kf_pattern")) {          // host only: the four lists BriefExtractor reads, one line each
+        try {
+            BriefExtractor extractor(argv[2]);
+            for (int k = 0; k < 4; ++k) {
+                for (int i = 0; i < 256; ++i) printf("%d%c", (int)extractor.pattern[k][i], i == 255 ? '\n' : ' ');
+            }
+            return 0;
+        } catch (const std::exception& e) { fprintf(stderr, "vins_replay kf_pattern: %s\n", e.what()); return 1; }
+    }
+    if (argc >= 5 && !strcmp(argv[1], "kf")) {
+        try { return replay_kf(argv[2], argv[3], argv[4]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay kf: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "exrot")) {
         try { return replay_exrot(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay exrot: %s\n", e.what()); return 1; }
@@ -849,6 +939,6 @@ int main(int argc, char** argv) {
         try { return replay_sfm(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml>\n");
     return 2;
 }

@@ -538,8 +538,48 @@ template <class T> void take_setmask_result(T& t, const typename OrderCtx<T>::So
     }
 }
 
+// ---- vg_kf_*: the pose graph's KeyFrame (host/keyframe.h, or the reference's own class with a slot beside it)
+// one entry of vg_kf_add from a keyframe's image and point_2d_uv
+template <class KF>
+void pack_kf(const KF& kf, int slot, const vg_fe_camera& camera, vg_kf_in& in) {
+    std::memset(&in, 0, sizeof(in));
+    in.struct_size = (int)sizeof(in);
+    in.slot = slot; in.img = kf.image.data; in.stride = (int)kf.image.step;
+    in.n_window = (int)kf.point_2d_uv.size(); in.window_xy = kf.point_2d_uv.empty() ? nullptr : &kf.point_2d_uv[0].x;
+    in.camera = camera;
+}
+// a whole record for vg_kf_set from stored keypoints, keypoints_norm and brief_descriptors (the constructor of loadPoseGraph); the
+// vectors of `r` hold what rec points to
+struct KfRecord {
+    std::vector<float> kp, nm;
+    std::vector<uint8_t> sc;
+    std::vector<uint64_t> de;
+    vg_kf_record rec;
+};
+template <class KF>
+void pack_kf_record(const KF& kf, KfRecord& r) {
+    const size_t n = kf.keypoints.size();
+    if (kf.keypoints_norm.size() != n || kf.brief_descriptors.size() != n) throw std::runtime_error("pack_kf_record: the three lists differ in length");
+    r.kp.assign(2 * n + 2, 0.f); r.nm.assign(2 * n + 2, 0.f); r.sc.assign(n + 1, 0); r.de.assign(4 * n + 4, 0);
+    for (size_t i = 0; i < n; ++i) {
+        r.kp[2 * i] = kf.keypoints[i].pt.x; r.kp[2 * i + 1] = kf.keypoints[i].pt.y;
+        r.nm[2 * i] = kf.keypoints_norm[i].pt.x; r.nm[2 * i + 1] = kf.keypoints_norm[i].pt.y;
+        r.sc[i] = (uint8_t)kf.keypoints[i].response;
+        for (int q = 0; q < 4; ++q) r.de[4 * i + q] = kf.brief_descriptors[i][q];
+    }
+    std::memset(&r.rec, 0, sizeof(r.rec));
+    r.rec.struct_size = (int)sizeof(r.rec);
+    r.rec.n_keypoints = (int)n;
+    r.rec.keypoints_xy = r.kp.data(); r.rec.scores = r.sc.data(); r.rec.norm_xy = r.nm.data(); r.rec.descriptors = r.de.data();
+}
+
 }  // namespace vg_pack
 
+// (the packer of vg_kf_add under the name the integration guide uses)
+template <class KF>
+void vg_pack_kf(const KF& kf, int slot, const vg_fe_camera& camera, vg_kf_in& in) {
+    vg_pack::pack_kf(kf, slot, camera, in);
+}
 // (the packer of vg_init_sfm under the name the integration guide uses)
 template <class Features, class Map, class M3, class V3>
 void vg_pack_sfm(const Features& features, const Map& frames, const double* stamps, int n_stamps, int l, const M3& relative_R, const V3& relative_T,

@@ -7,7 +7,8 @@
 //   %YAML:1.0 header, `#` comments (also trailing), blank lines;
 //   top-level scalars     key: value            numbers, bare words, "quoted strings";
 //   one level of mapping  key:\n   child: value   -> addressed as "key.child" (distortion_parameters.k1 ...);
-//   OpenCV matrices       key: !!opencv-matrix\n   rows: R\n   cols: C\n   dt: d\n   data: [ ... ]   (data may span lines).
+//   OpenCV matrices       key: !!opencv-matrix\n   rows: R\n   cols: C\n   dt: d\n   data: [ ... ]   (data may span lines);
+//   block sequences       key:\n   - 0\n   - -4 ...   numbers under a key, one `- value` line each (support_files/brief_pattern.yml).
 // Header-only; used by the host shims (readParameters / readIntrinsicParameter) and — through the cv::FileStorage stand-in of
 // oracle/ref_stubs — by the reference's own parameters.cpp in the parity test.
 #pragma once
@@ -36,7 +37,7 @@ class VinsYaml {
     }
 
     bool parse(const std::string& text) {
-        scalars_.clear(); matrices_.clear(); opened_ = false;
+        scalars_.clear(); matrices_.clear(); sequences_.clear(); opened_ = false;
         std::vector<std::string> lines;
         {
             std::stringstream ss(text);
@@ -51,6 +52,14 @@ class VinsYaml {
             const std::string t = trim(raw);
             if (t.empty() || t[0] == '%' || t == "---") continue;
             const int indent = (int)raw.find_first_not_of(" \t");
+            if (t[0] == '-' && (t.size() == 1 || t[1] == ' ') && !parent.empty() && !mat && indent > parent_indent) {     // an entry of a block sequence
+                const std::string item = trim(t.substr(1));
+                char* end = nullptr;
+                const double v = strtod(item.c_str(), &end);
+                if (item.empty() || end == item.c_str() || *end) return false;
+                sequences_[parent].push_back(v);
+                continue;
+            }
             const size_t colon = find_colon(t);
             if (colon == std::string::npos) return false;                 // not `key: ...`
             const std::string key = trim(t.substr(0, colon));
@@ -87,7 +96,12 @@ class VinsYaml {
     }
 
     bool opened() const { return opened_; }
-    bool has(const std::string& key) const { return scalars_.count(key) || matrices_.count(key); }
+    bool has(const std::string& key) const { return scalars_.count(key) || matrices_.count(key) || sequences_.count(key); }
+    // the numbers of a block sequence, or nullptr
+    const std::vector<double>* sequence(const std::string& key) const {
+        auto it = sequences_.find(key);
+        return it == sequences_.end() ? nullptr : &it->second;
+    }
     bool is_matrix(const std::string& key) const { return matrices_.count(key) != 0; }
     std::string str(const std::string& key, const std::string& dflt = "") const {
         auto it = scalars_.find(key);
@@ -109,6 +123,7 @@ class VinsYaml {
   private:
     std::map<std::string, std::string> scalars_;
     std::map<std::string, Matrix> matrices_;
+    std::map<std::string, std::vector<double>> sequences_;
     bool opened_ = false;
 
     static std::string trim(const std::string& s) {
