@@ -32,7 +32,7 @@ extern "C" {
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
                              * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot;
-                             * vg_kf_configure / _add / _get / _set / _match) */
+                             * vg_kf_configure / _add / _get / _set / _match; vg_kf_pnp, vg_kf_pnp_defaults) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -1309,7 +1309,7 @@ int vg_vio_end(vg_handle* h);
 /* ---- Loop closure: keyframe BRIEF descriptors and matching (added within ABI 12, nothing existing changed) ----------------------------
  * The integer-exact, batchable part of the pose graph's KeyFrame (pose_graph/src/keyframe.cpp): computeWindowBRIEFPoint and
  * computeBRIEFPoint with keypoints_norm (vg_kf_add), searchByBRIEFDes with the reduceVector step of findConnection:301-312
- * (vg_kf_match).  NOT here: PnPRANSAC (cv::solvePnPRansac), the loop_info arithmetic behind it, DBoW2 loop detection, the 4-DoF
+ * (vg_kf_match).  PnPRANSAC and the loop_info arithmetic behind it are vg_kf_pnp (the next block).  NOT here: DBoW2 loop detection, the 4-DoF
  * pose-graph optimisation, thumbnails and debug images.  Independent of vg_fe_configure: the pose graph's image is not the front
  * end's current frame.
  *
@@ -1408,6 +1408,114 @@ int vg_kf_add(vg_handle* h, int n, const vg_kf_in* in /* [n] */, vg_kf_out* out 
 int vg_kf_get(vg_handle* h, int slot, vg_kf_record* rec);
 int vg_kf_set(vg_handle* h, int slot, const vg_kf_record* rec);
 int vg_kf_match(vg_handle* h, int n_pairs, const vg_kf_pair* in /* [n_pairs] */, vg_kf_match_out* out /* [n_pairs] */);
+
+/* ---- Loop closure: PnPRANSAC and findConnection's loop gate, batched (added within ABI 12, nothing existing changed) -------------------
+ * What KeyFrame::findConnection runs between searchByBRIEFDes (vg_kf_match) and the lists it publishes (vg_ba_seq_set_relo):
+ * KeyFrame::PnPRANSAC (pose_graph/src/keyframe.cpp:200-256), the second reduceVector round (:406-415) and the loop_info arithmetic
+ * with its yaw / distance gate (:472-516), for n_pairs (current, old) pairs in one call.  Needs no vg_kf_configure; plain arrays in
+ * and out.  Synchronous: one upload, VG_KF_PNP_LAUNCHES launches over the whole batch, one download.  A pair's status never touches
+ * its neighbours; a batch equals the single calls bit for bit.
+ *
+ * cv::solvePnPRansac is third-party and not pinned here: everything below is RECALLED for OpenCV 3.3-era solvepnp.cpp / epnp.cpp /
+ * ptsetreg.cpp, NOT PINNED.  Parts marked [FIXED] are this library's choice where the
+ * recalled code leaves the result to rounding noise or to a general-purpose solver; [DEVIATION] where it knowingly differs.
+ *  1 Camera   K = I, no distortion.  R_inital = (origin_vio_R qic)^-1 (3x3 inverse by cofactors over the determinant, as Eigen's),
+ *             P_inital = -(R_inital (origin_vio_T + origin_vio_R tic)), rvec0 = Rodrigues(R_inital) (regular branch, as vg_init_sfm
+ *             states it; the near-pi branch is VG_KF_PNP_NUMERIC).  They enter step 5 and the NO_MODEL case only.
+ *  2 Registrator  5 model points.  Samples: cv::RNG((uint64)-1), five rng.uniform(0, n) per sample, an index already in the sample is
+ *             redrawn; PnPRansacCallback has no checkSubset, so the schedule depends on n alone (no host fallback path).  At most
+ *             max_iters iterations.  A model replaces the best one when its inlier count exceeds max(best, 4); then niters =
+ *             RANSACUpdateNumIters(0.99, (n - good) / n, 5, niters).  Iterations at or beyond niters do not count.
+ *  3 Error    of a model (rvec, tvec) at point i: R = Rodrigues(rvec); X = R P_i + tvec in double (P_i widened from float32);
+ *             z = X[2] != 0 ? 1 / X[2] : 1; the projection (X[0] z, X[1] z) rounded to float32; dx, dy = its float32 difference to the
+ *             float32 observation; err = (float)((double)dx dx + (double)dy dy); inlier iff err <= (float)(threshold threshold).
+ *  4 runKernel  solvePnP(SOLVEPNP_EPNP) on the five points widened to double (the guess is ignored by EPnP):
+ *             control points: c0 = the centroid, c_i = c0 + sqrt(lambda_i / 5) e_i for the eigenpairs of PW0^T PW0 (PW0 = the
+ *               centred points) in descending lambda.  [FIXED] The 3x3 eigenproblem is the one-sided Jacobi of vg_init_relpose on
+ *               the columns of PW0^T PW0 (lambda = the column norm); each e_i has its largest-magnitude entry positive (lowest index
+ *               on a tie).  Barycentric coordinates through the 3x3 inverse (cofactors over the determinant) of [c1-c0 c2-c0 c3-c0].
+ *             M (10 x 12) with fu = fv = 1, uc = vc = 0: rows [a_j, 0, -a_j u] and [0, a_j, -a_j v] per control point j.
+ *               [FIXED] The eigenvectors of M^T M for its four smallest eigenvalues are the right singular vectors of M by the
+ *               one-sided Jacobi on its 12 columns (pairs (i, j) with i + j = r mod 12 in round r = 0 .. 11 of a sweep, threshold
+ *               1e-15, at most 40 sweeps, eigenvalue = squared column norm, ascending, lowest index on a tie): v1 the smallest .. v4.
+ *             [DEVIATION] the null-space basis.  M^T M of 5 points has rank at most 10: v1, v2 are an arbitrary orthonormal basis of a
+ *               plane, in OpenCV whatever rounding noise its SVD leaves, and the non-converged Gauss-Newton makes the pose depend on
+ *               it.  Here, with (a, b) the computed pair, k the row of largest a[k]^2 + b[k]^2 (lowest index first) and r its root:
+ *               v1 = (b[k] a - a[k] b) / r (0 at row k), v2 = (a[k] a + b[k] b) / r (r > 0 at row k); then every one of v1 .. v4 has
+ *               its largest-magnitude entry made positive.  This is the library's choice: no OpenCV build is reproduced bit for bit at
+ *               this step; the result depends continuously on the input wherever the row choice is not tied.
+ *             compute_L_6x10, compute_rho as recalled; find_betas_approx_1 / 2 / 3 ([FIXED] their 6x4, 6x3, 6x5 least-squares solves
+ *               are by the Householder QR of qr_solve, where OpenCV calls cvSolve(CV_SVD)), each followed by gauss_newton (5
+ *               iterations, the 6x4 step by qr_solve) and compute_R_and_t: solve_for_sign, Arun's 3x3 SVD ([FIXED] the same one-sided
+ *               Jacobi, U from the normalised columns, singular values descending) with R = U V^T, its third ROW negated when det R <
+ *               0, t = pc0 - R pw0.  The candidate of the smallest mean reprojection error wins (2 against 1, then 3 against the
+ *               better of them, strict <).  rvec = Rodrigues(R), regular branch.
+ *             [DEVIATION] A sample whose control-point matrix has a determinant that is zero or not finite, a QR column that is all
+ *               zero, a Rodrigues in the near-pi branch, or any value of rvec / tvec that is not finite yields NO model (count -1).
+ *               The reference goes on with a pseudo-inverse.
+ *  5 Returned pose  `refine` selects (recollections of the 3.x releases differ and nothing here can settle it):
+ *             0  the winning sample's model goes out unchanged: recalled for the releases (3.2 - 3.4.x) that refit the inliers by
+ *                solvePnP(EPNP / no guess) and then return the sample's model when the call is made through the RANSAC result;
+ *             1  solvePnP(inliers, useExtrinsicGuess = 1, SOLVEPNP_ITERATIVE) started from R_inital / P_inital: recalled for 3.0 - 3.1
+ *                and for builds that pass the caller's flags to the final solvePnP.  Exactly vg_init_sfm's PnP over the inliers in input
+ *                order (points rounded to float32); VG_SFM_NUMERIC there is VG_KF_PNP_NUMERIC here.  That PnP hands its rotation on as a
+ *                matrix: the returned rvec is its Rodrigues vector (regular branch; near pi: VG_KF_PNP_NUMERIC).
+ *             The refit WITHOUT a guess (DLT / homography start of SOLVEPNP_ITERATIVE) is NOT offered.
+ *             No model at all: solvePnPRansac returns false and leaves the caller's rvec0 / P_inital in place; so does this call
+ *             (VG_KF_PNP_NO_MODEL, mask all zero, n_inliers 0).
+ *  6 After the pose  :245-254 as written: r = Rodrigues(rvec); R_w_c_old = r^T; T_w_c_old = R_w_c_old (-tvec); PnP_R_old = R_w_c_old
+ *             qic^T; PnP_T_old = T_w_c_old - PnP_R_old tic.  n_inliers > min_loop_num gates loop_info: relative_t = PnP_R_old^T
+ *             (origin_vio_T - PnP_T_old); relative_q = the library's R_to_q (Eigen's Quaterniond(Matrix3d)) of PnP_R_old^T origin_vio_R,
+ *             negated as a whole when w < 0 (w >= 0 on output), as w x y z; relative_yaw = normalizeAngle(R2ypr(origin_vio_R).x -
+ *             R2ypr(PnP_R_old).x) in degrees.  has_loop = |relative_yaw| < max_yaw_deg && |relative_t| < max_dist, both strict.
+ *             Without the gate loop_info is zero and has_loop 0.  The compacted lists (the inliers in input order) are filled whenever
+ *             the RANSAC found a model, whatever has_loop says.
+ * n <= min_loop_num: findConnection never calls PnPRANSAC: VG_KF_PNP_SKIPPED, everything else zero.
+ * Refused with VG_ERR_BAD_ARG before anything is uploaded, no output touched, the handle usable: a wrong struct_size, n outside 6 ..
+ * VG_KF_MAX_WINDOW, a NULL table (point_3d, old_norm), a non-finite input, reproj_threshold / max_yaw_deg / max_dist not positive,
+ * min_loop_num < 0, max_iters outside 1 .. VG_KF_PNP_MAX_ITERS, a confidence other than 0.99, refine outside {0, 1}. */
+#define VG_KF_PNP_OK 0
+#define VG_KF_PNP_SKIPPED 1
+#define VG_KF_PNP_NO_MODEL 2
+#define VG_KF_PNP_NUMERIC 3
+#define VG_KF_PNP_MAX_ITERS 1000
+#define VG_KF_PNP_LAUNCHES 7         /* samples, counts, bookkeeping of the first chunk; the same of the rest; mask + refit + pose tail */
+typedef struct vg_kf_pnp_in {
+    size_t struct_size;          /* sizeof(vg_kf_pnp_in); vg_kf_pnp_defaults sets it */
+    int n;                       /* matched_2d_cur.size() after vg_kf_match, 6 .. VG_KF_MAX_WINDOW */
+    const float* point_3d;       /* [n][3] matched_3d (cv::Point3f) */
+    const float* old_norm;       /* [n][2] matched_2d_old_norm (matched_old_norm of vg_kf_match) */
+    const int* point_id;         /* [n] matched_id, or NULL: match_id is then the input index */
+    double origin_vio_T[3], origin_vio_R[9], tic[3], qic[9];      /* row-major */
+    int min_loop_num;            /* 25 (MIN_LOOP_NUM) */
+    int max_iters;               /* 100 */
+    int refine;                  /* step 5; default 0 */
+    double reproj_threshold;     /* 10.0 / 460.0 */
+    double confidence;           /* 0.99; nothing else is accepted */
+    double max_yaw_deg;          /* 30 */
+    double max_dist;             /* 20 */
+} vg_kf_pnp_in;
+typedef struct vg_kf_pnp_out {
+    size_t struct_size;          /* sizeof(vg_kf_pnp_out), set by the caller */
+    int status;                  /* VG_KF_PNP_* */
+    int n_inliers;
+    int ransac_best;             /* iteration whose model won, -1: none */
+    int ransac_iter;             /* the last iteration the loop looked at */
+    int ransac_bound;            /* the bound niters ended with */
+    int refit_iters, refit_up;   /* refine == 1: iterations and lambda raises of the PnP (pnp_iters / pnp_up of vg_init_sfm) */
+    int has_loop;
+    double sample_rvec[3], sample_tvec[3];     /* the winning sample's model */
+    double rvec[3], tvec[3];                   /* the returned pose */
+    double PnP_R_old[9], PnP_T_old[3];
+    double loop_info[8];         /* relative_t 3 | relative_q w x y z | relative_yaw (degrees) */
+    unsigned char* mask;         /* [n] status of PnPRANSAC, or NULL */
+    int* matched_index;          /* [n] capacity each, or NULL: the n_inliers surviving input indices, ascending */
+    int* match_id;               /* point_id of the survivors: vg_ba_relo_frame::match_id */
+    double* match_xy;            /* [..][2] old_norm of the survivors widened: vg_ba_relo_frame::match_xy */
+    float* device_ms;            /* out[0] only: VG_KF_PNP_LAUNCHES event intervals of the batch, or NULL */
+} vg_kf_pnp_out;
+void vg_kf_pnp_defaults(vg_kf_pnp_in* in);        /* zero, struct_size and the defaults above; qic and origin_vio_R the identity */
+int vg_kf_pnp(vg_handle* h, int n_pairs, const vg_kf_pnp_in* in /* [n_pairs] */, vg_kf_pnp_out* out /* [n_pairs] */);
 
 #ifdef __cplusplus
 }

@@ -412,3 +412,6 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
 
 // ---- vg_kf_*: keyframe BRIEF descriptors and matching for the pose graph (blur, FAST, BRIEF, the lift, Hamming matching), the host entries
 #include "kf_brief.h"
+
+// ---- vg_kf_pnp: PnPRANSAC (EPnP samples, the 5-point registrator, the refit) and findConnection's loop gate for a batch of pairs
+#include "kf_pnp.h"

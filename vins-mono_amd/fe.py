@@ -737,3 +737,86 @@ class KeyFrames:
         if timed and n:
             res[0]["device_ms"] = float(ms[0])
         return res
+
+
+# ---- loop closure: PnPRANSAC and findConnection's loop gate (vg_kf_pnp) ------------------------------------------------------------------
+KF_PNP_OK, KF_PNP_SKIPPED, KF_PNP_NO_MODEL, KF_PNP_NUMERIC = 0, 1, 2, 3
+KF_PNP_LAUNCHES = 7
+KF_PNP_KERNELS = ("sample_0", "count_0", "pick_0", "sample_1", "count_1", "pick_1", "tail")
+_f8 = C.POINTER(C.c_double)
+
+
+class KfPnpIn(C.Structure):
+    """vg_kf_pnp_in (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("n", C.c_int), ("point_3d", _f4), ("old_norm", _f4), ("point_id", _i4),
+                ("origin_vio_T", C.c_double * 3), ("origin_vio_R", C.c_double * 9), ("tic", C.c_double * 3), ("qic", C.c_double * 9),
+                ("min_loop_num", C.c_int), ("max_iters", C.c_int), ("refine", C.c_int), ("reproj_threshold", C.c_double),
+                ("confidence", C.c_double), ("max_yaw_deg", C.c_double), ("max_dist", C.c_double)]
+
+
+class KfPnpOut(C.Structure):
+    """vg_kf_pnp_out (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("status", C.c_int), ("n_inliers", C.c_int), ("ransac_best", C.c_int), ("ransac_iter", C.c_int),
+                ("ransac_bound", C.c_int), ("refit_iters", C.c_int), ("refit_up", C.c_int), ("has_loop", C.c_int),
+                ("sample_rvec", C.c_double * 3), ("sample_tvec", C.c_double * 3), ("rvec", C.c_double * 3), ("tvec", C.c_double * 3),
+                ("PnP_R_old", C.c_double * 9), ("PnP_T_old", C.c_double * 3), ("loop_info", C.c_double * 8), ("mask", _u8),
+                ("matched_index", _i4), ("match_id", _i4), ("match_xy", _f8), ("device_ms", _f4)]
+
+
+_KF_PNP_SCALARS = ("min_loop_num", "max_iters", "refine", "reproj_threshold", "confidence", "max_yaw_deg", "max_dist")
+
+
+def kf_pnp(handle, pairs, timed=False):
+    """vg_kf_pnp for a list of pairs on a ba.Handle.  A pair is a dict: point_3d [n, 3] and old_norm [n, 2] (float32), optionally point_id
+    [n], origin_vio_T, origin_vio_R, tic, qic and any of min_loop_num, max_iters, refine, reproj_threshold, confidence, max_yaw_deg,
+    max_dist (vg_kf_pnp_defaults otherwise); `n` overrides the row count (the refusal tests).  One dict per pair: status, n_inliers, mask,
+    the RANSAC taps, sample_rvec / sample_tvec, rvec / tvec, refit_iters / refit_up, PnP_R_old [3, 3], PnP_T_old, loop_info [8], has_loop
+    and the compacted matched_index, match_id (int32) and match_xy (float64 [n_inliers, 2]: vg_ba_relo_frame's fields); with `timed`
+    the first dict also holds device_ms [KF_PNP_LAUNCHES]."""
+    L = handle.lib
+    L.vg_kf_pnp_defaults.argtypes = [C.POINTER(KfPnpIn)]
+    L.vg_kf_pnp_defaults.restype = None
+    L.vg_kf_pnp.argtypes = [C.c_void_p, C.c_int, C.POINTER(KfPnpIn), C.POINTER(KfPnpOut)]
+    n = len(pairs)
+    ins, outs, keep = (KfPnpIn * max(n, 1))(), (KfPnpOut * max(n, 1))(), []
+    ms = np.zeros(KF_PNP_LAUNCHES, np.float32)
+    for i, p in enumerate(pairs):
+        a, o = ins[i], outs[i]
+        L.vg_kf_pnp_defaults(C.byref(a))
+        p3 = None if p.get("point_3d") is None else np.ascontiguousarray(p["point_3d"], np.float32).reshape(-1, 3)
+        p2 = None if p.get("old_norm") is None else np.ascontiguousarray(p["old_norm"], np.float32).reshape(-1, 2)
+        ids = None if p.get("point_id") is None else np.ascontiguousarray(p["point_id"], np.int32).reshape(-1)
+        m = int(p["n"]) if "n" in p else len(p3)
+        a.n = m
+        a.point_3d = None if p3 is None else p3.ctypes.data_as(_f4)
+        a.old_norm = None if p2 is None else p2.ctypes.data_as(_f4)
+        a.point_id = None if ids is None else ids.ctypes.data_as(_i4)
+        for k, cnt in (("origin_vio_T", 3), ("origin_vio_R", 9), ("tic", 3), ("qic", 9)):
+            if k in p:
+                setattr(a, k, (C.c_double * cnt)(*np.asarray(p[k], np.float64).reshape(-1)))
+        for k in _KF_PNP_SCALARS:
+            if k in p:
+                setattr(a, k, p[k])
+        if "struct_size" in p:
+            a.struct_size = int(p["struct_size"])
+        cap = max(m, 1) if 0 < m <= 1024 else 1
+        bufs = (np.zeros(cap, np.uint8), np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros((cap, 2), np.float64))
+        o.struct_size = int(p.get("out_struct_size", C.sizeof(KfPnpOut)))
+        o.mask, o.matched_index, o.match_id, o.match_xy = (bufs[0].ctypes.data_as(_u8), bufs[1].ctypes.data_as(_i4), bufs[2].ctypes.data_as(_i4),
+                                                           bufs[3].ctypes.data_as(_f8))
+        keep.append((p3, p2, ids, bufs, m))
+    if timed and n:
+        outs[0].device_ms = ms.ctypes.data_as(_f4)
+    handle._chk(L.vg_kf_pnp(handle.h, n, ins, outs), "vg_kf_pnp")
+    res = []
+    for i in range(n):
+        o, (_, _, _, bufs, m) = outs[i], keep[i]
+        k = o.n_inliers
+        res.append({"status": o.status, "n_inliers": k, "ransac_best": o.ransac_best, "ransac_iter": o.ransac_iter, "ransac_bound": o.ransac_bound,
+                    "refit_iters": o.refit_iters, "refit_up": o.refit_up, "has_loop": o.has_loop,
+                    "sample_rvec": np.array(o.sample_rvec), "sample_tvec": np.array(o.sample_tvec), "rvec": np.array(o.rvec), "tvec": np.array(o.tvec),
+                    "PnP_R_old": np.array(o.PnP_R_old).reshape(3, 3), "PnP_T_old": np.array(o.PnP_T_old), "loop_info": np.array(o.loop_info),
+                    "mask": bufs[0][:m].copy(), "matched_index": bufs[1][:k].copy(), "match_id": bufs[2][:k].copy(), "match_xy": bufs[3][:k].copy()})
+    if timed and n:
+        res[0]["device_ms"] = ms.copy()
+    return res

@@ -14,6 +14,11 @@ struct Point2f {
     Point2f() : x(0), y(0) {}
     Point2f(float x_, float y_) : x(x_), y(y_) {}
 };
+struct Point3f {
+    float x, y, z;
+    Point3f() : x(0), y(0), z(0) {}
+    Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
+};
 // (the two members the pose graph's KeyFrame reads)
 struct KeyPoint {
     Point2f pt;

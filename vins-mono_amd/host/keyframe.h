@@ -1,17 +1,20 @@
-// keyframe.h — the pose graph's KeyFrame (pose_graph/src/keyframe.h, keyframe.cpp) up to the MIN_LOOP_NUM test of findConnection, on the
-// device through vg_kf_* (include/vinsgpu.h): computeWindowBRIEFPoint, computeBRIEFPoint with keypoints_norm, searchByBRIEFDes and the
-// reduceVector step behind it.  Stand-alone and header-only; the reference's member names.  A KeyFrame owns one SLOT of the handle's
-// resident records (KeyFrame::configure allocates them once); its descriptors stay on the device, the members below are the host copies
-// the reference's callers read.  What follows in the reference's findConnection -- PnPRANSAC and the loop_info arithmetic -- stays with
-// the caller, who gets the compacted lists.
+// keyframe.h — the pose graph's KeyFrame (pose_graph/src/keyframe.h, keyframe.cpp) with its findConnection, on the device through
+// vg_kf_* (include/vinsgpu.h): computeWindowBRIEFPoint, computeBRIEFPoint with keypoints_norm, searchByBRIEFDes and the reduceVector step
+// behind it (vg_kf_add, vg_kf_match), PnPRANSAC, the second reduceVector round and the loop_info arithmetic with its gate (vg_kf_pnp).
+// Stand-alone and header-only; the reference's member names.  A KeyFrame owns one SLOT of the handle's resident records
+// (KeyFrame::configure allocates them once); its descriptors stay on the device, the members below are the host copies the reference's
+// callers read.  Where the reference publishes a ROS message (pub_match_points) the class fills the plain struct match_points.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
 #include "../../include/vinsgpu.h"
 #include "compat/cv_compat.h"
+#include "compat/eigen_compat.h"
 #include "vg_pack.h"
 #include "yaml_config.h"
 
@@ -61,6 +64,58 @@ class KeyFrame {
         added = true;
     }
 
+    // a keyframe that only verifies: the members PnPRANSAC and findConnection's second half read, no record on the device
+    KeyFrame(vg_handle* h_, double _time_stamp, int _index, const Eigen::Vector3d& _vio_T_w_i, const Eigen::Matrix3d& _vio_R_w_i,
+             const std::vector<cv::Point3f>& _point_3d, const std::vector<double>& _point_id)
+        : time_stamp(_time_stamp), index(_index), point_3d(_point_3d), point_id(_point_id), vio_T_w_i(_vio_T_w_i), vio_R_w_i(_vio_R_w_i), T_w_i(_vio_T_w_i),
+          R_w_i(_vio_R_w_i), origin_vio_T(_vio_T_w_i), origin_vio_R(_vio_R_w_i), slot(-1), h(h_) { added = true; }
+
+    // KeyFrame::PnPRANSAC (keyframe.cpp:200-256) with the reference's signature: status is appended to, as there.  One vg_kf_pnp; the
+    // call's loop gate is set below the list's length so that the member always runs (findConnection tests MIN_LOOP_NUM before it)
+    void PnPRANSAC(const std::vector<cv::Point2f>& matched_2d_old_norm, const std::vector<cv::Point3f>& matched_3d, std::vector<uchar>& status,
+                   Eigen::Vector3d& PnP_T_old, Eigen::Matrix3d& PnP_R_old) {
+        pnp(matched_2d_old_norm, matched_3d, std::vector<int>(), std::min((int)MIN_LOOP_NUM, (int)matched_3d.size() - 1));
+        for (size_t i = 0; i < matched_3d.size(); ++i) status.push_back(p_mask[i]);
+        for (int r = 0; r < 3; ++r) { PnP_T_old(r) = pout.PnP_T_old[r]; for (int c = 0; c < 3; ++c) PnP_R_old(r, c) = pout.PnP_R_old[3 * r + c]; }
+    }
+    // findConnection (keyframe.cpp:259-520) as the reference declares it: the match, the first reduceVector round, PnPRANSAC with the
+    // second, loop_info and the gate; sets has_loop, loop_index, loop_info and match_points.  point_3d / point_id are per window point.
+    bool findConnection(KeyFrame* old_kf) {
+        std::vector<cv::Point2f> matched_2d_cur, matched_2d_old, matched_2d_old_norm;
+        std::vector<int> matched_index;
+        std::vector<cv::Point3f> matched_3d;
+        std::vector<double> matched_id;
+        if (point_3d.size() != point_2d_uv.size() || point_id.size() != point_2d_uv.size()) throw std::runtime_error("KeyFrame::findConnection: point_3d / point_id per window point");
+        findConnection(*old_kf, matched_2d_cur, matched_2d_old, matched_2d_old_norm, matched_index);
+        for (int i : matched_index) { matched_3d.push_back(point_3d[i]); matched_id.push_back(point_id[i]); }
+        return findConnection(old_kf, matched_2d_old_norm, matched_3d, matched_id);
+    }
+    // its second half (:401-520) from the lists the first reduceVector round left; the lists are reduced in place as there
+    bool findConnection(KeyFrame* old_kf, std::vector<cv::Point2f>& matched_2d_old_norm, std::vector<cv::Point3f>& matched_3d, std::vector<double>& matched_id) {
+        pnp_status = VG_KF_PNP_SKIPPED;
+        if ((int)matched_3d.size() <= MIN_LOOP_NUM) return false;
+        std::vector<int> ids;
+        for (double v : matched_id) ids.push_back((int)v);
+        pnp(matched_2d_old_norm, matched_3d, ids, MIN_LOOP_NUM);
+        std::vector<cv::Point2f> n2;
+        std::vector<cv::Point3f> n3;
+        std::vector<double> nid;
+        for (int k = 0; k < pout.n_inliers; ++k) { n2.push_back(matched_2d_old_norm[p_index[k]]); n3.push_back(matched_3d[p_index[k]]); nid.push_back(matched_id[p_index[k]]); }
+        matched_2d_old_norm.swap(n2); matched_3d.swap(n3); matched_id.swap(nid);
+        if (!pout.has_loop) return false;
+        has_loop = true;
+        loop_index = old_kf->index;
+        for (int k = 0; k < 8; ++k) loop_info(k, 0) = pout.loop_info[k];
+        // FAST_RELOCALIZATION: what pub_match_points carries, ready for vg_ba_relo_frame (match_id / match_xy)
+        match_points.stamp = time_stamp;
+        match_points.match_id.assign(p_id.begin(), p_id.begin() + pout.n_inliers);
+        match_points.match_xy.assign(p_xy.begin(), p_xy.begin() + 2 * (size_t)pout.n_inliers);
+        const Eigen::Quaterniond Q(old_kf->R_w_i);
+        const double tq[8] = {old_kf->T_w_i.x(), old_kf->T_w_i.y(), old_kf->T_w_i.z(), Q.w(), Q.x(), Q.y(), Q.z(), (double)index};
+        for (int k = 0; k < 8; ++k) match_points.t_q_index[k] = tq[k];
+        return true;
+    }
+
     void computeWindowBRIEFPoint() {
         add();
         window_keypoints.clear();
@@ -102,6 +157,22 @@ class KeyFrame {
     std::vector<BRIEF::bitset> brief_descriptors, window_brief_descriptors;
     vg_fe_camera camera = {};
     int slot;
+    std::vector<cv::Point3f> point_3d;  // per window point, like point_2d_uv
+    std::vector<double> point_id;
+    Eigen::Vector3d vio_T_w_i, T_w_i, origin_vio_T, tic;
+    Eigen::Matrix3d vio_R_w_i, R_w_i, origin_vio_R, qic;          // (tic / qic: the reference's globals, per keyframe here)
+    bool has_loop = false;
+    int loop_index = -1;
+    Eigen::Matrix<double, 8, 1> loop_info;
+    struct MatchPoints {                // sensor_msgs::PointCloud of pub_match_points as plain data
+        double stamp = 0.0;
+        std::vector<int> match_id;      // points[k].z
+        std::vector<double> match_xy;   // points[k].x, .y
+        double t_q_index[8] = {0, 0, 0, 1, 0, 0, 0, 0};      // the old keyframe's T_w_i, Q (w x y z), this keyframe's index
+    } match_points;
+    int pnp_refine = 0;                 // vg_kf_pnp_in::refine
+    int pnp_status = VG_KF_PNP_SKIPPED; // VG_KF_PNP_* of the last PnPRANSAC
+    vg_kf_pnp_out pout = {};            // the last vg_kf_pnp (taps included); its pointers are the class's own
     int n_true = 0;                     // corners cv::FAST lists; above max_keypoints the record keeps the first max_keypoints (kf_status)
     int kf_status = VG_KF_OK;
     std::vector<int> best_idx, best_dist;      // of the last match, per window point
@@ -114,6 +185,20 @@ class KeyFrame {
     std::vector<float> m_old, m_old_norm, c_old, c_old_norm;
     std::vector<int> m_index;
 
+    std::vector<uchar> p_mask;
+    std::vector<int> p_index, p_id;
+    std::vector<double> p_xy;
+    void pnp(const std::vector<cv::Point2f>& norm, const std::vector<cv::Point3f>& p3, const std::vector<int>& ids, int min_loop_num) {
+        vg_kf_pnp_in in;
+        vg_pack_kf_pnp(*this, p3, norm, ids, in);
+        in.min_loop_num = min_loop_num; in.refine = pnp_refine;
+        const size_t n = p3.size();
+        p_mask.assign(n + 1, 0); p_index.assign(n + 1, 0); p_id.assign(n + 1, 0); p_xy.assign(2 * n + 2, 0.0);
+        std::memset(&pout, 0, sizeof(pout));
+        pout.struct_size = sizeof(pout); pout.mask = p_mask.data(); pout.matched_index = p_index.data(); pout.match_id = p_id.data(); pout.match_xy = p_xy.data();
+        if (vg_kf_pnp(h, 1, &in, &pout) != VG_OK) throw std::runtime_error(vg_last_error(h));
+        pnp_status = pout.status;
+    }
     // (max_keypoints, max_window_points) of the handle's configuration
     static std::pair<int, int> capacity(vg_handle* h, int mk = 0, int mw = 0, bool set = false) {
         static std::vector<std::pair<vg_handle*, std::pair<int, int>>> table;

@@ -43,6 +43,9 @@
 //     host only: prints the four lists of 256 integers that BriefExtractor reads from the yml.
 //   vins_replay exrot <in.bin> <out.txt>
 //     the extrinsic-rotation calibration of processImage, one vg_init_exrot call per frame (replay_exrot below).
+//   vins_replay kfpnp <in.bin> <out.txt>
+//     KeyFrame::PnPRANSAC and findConnection's second half (vg_kf_pnp through vg_pack_kf_pnp) over the matched lists of a file
+//     (replay_kfpnp below).
 //   vins_replay relpose <in.bin> <out.txt>
 //     Estimator::relativePose(relative_R, relative_T, l) (vg_init_relpose) over f_manager.feature from a file; writes the return value,
 //     the VG_RELPOSE_* status, l, relative_R and relative_T and, when no frame passes, what the zero-argument initialStructure() returns
@@ -889,7 +892,75 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
     return 0;
 }
 
+// vins_replay kfpnp <in.bin> <out.txt>: KeyFrame::PnPRANSAC and the second half of KeyFrame::findConnection (host/keyframe.h,
+// vg_pack_kf_pnp) over a KPN1 file (tests/kf_pnp_ref.write_file: the lists findConnection holds behind its first reduceVector round).
+// The file's min_loop_num must be KeyFrame::MIN_LOOP_NUM and its other gates the defaults, which is what the class passes.  Writes
+// "pnp <VG_KF_PNP_*> <inliers>", "status" with the mask, "R" nine and "T" three numbers of PnPRANSAC (17 digits); then of findConnection
+// "connection <return value> <VG_KF_PNP_*> <has_loop> <loop_index> <survivors>", "loop_info" with eight numbers, "taps" (best, last
+// iteration, bound, refit iterations and raises), "pose" (rvec, tvec), an "m <id> <x> <y>" line per entry of match_points and "tq" with its eight numbers.
+static int replay_kfpnp(const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("kfpnp file"); return 2; }
+    int hdr[5];
+    double d[27];
+    rd.i(hdr, 5); rd.d(d, 27);
+    if (hdr[0] != 0x314E504B) { fprintf(stderr, "not a KPN1 file\n"); return 2; }
+    const int n = hdr[1];
+    if (n < 0 || hdr[2] != KeyFrame::MIN_LOOP_NUM || hdr[3] != 100) { fprintf(stderr, "the class runs MIN_LOOP_NUM %d and 100 iterations\n", (int)KeyFrame::MIN_LOOP_NUM); return 2; }
+    std::vector<cv::Point3f> p3((size_t)n);
+    std::vector<cv::Point2f> p2((size_t)n);
+    std::vector<int> ids((size_t)n);
+    if (n && (fread(p3.data(), sizeof(cv::Point3f), n, rd.f) != (size_t)n || fread(p2.data(), sizeof(cv::Point2f), n, rd.f) != (size_t)n))
+        throw std::runtime_error("kfpnp file truncated");
+    rd.i(ids.data(), n);
+    fclose(rd.f);
+    vg_handle* h = nullptr;
+    if (vg_create(&h) != VG_OK) { fprintf(stderr, "vg_create failed\n"); return 1; }
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    {
+        Vector3d T(d[3], d[4], d[5]), tic(d[15], d[16], d[17]);
+        Matrix3d R, qic;
+        for (int e = 0; e < 9; ++e) { R(e / 3, e % 3) = d[6 + e]; qic(e / 3, e % 3) = d[18 + e]; }
+        std::vector<double> pid(ids.begin(), ids.end());
+        KeyFrame cur(h, 1.5, 7, T, R, p3, pid), old_kf(h, 0.5, 3, Vector3d(0.1, 0.2, 0.3), Matrix3d(), std::vector<cv::Point3f>(), std::vector<double>());
+        cur.tic = tic; cur.qic = qic; cur.pnp_refine = hdr[4];
+        std::vector<uchar> status;
+        Vector3d PT;
+        Matrix3d PR;
+        if (n >= 6) {
+            cur.PnPRANSAC(p2, p3, status, PT, PR);
+            fprintf(o, "pnp %d %d\nstatus", cur.pnp_status, cur.pout.n_inliers);
+            for (uchar s : status) fprintf(o, " %d", (int)s);
+            fprintf(o, "\nR");
+            for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", PR(e / 3, e % 3));
+            fprintf(o, "\nT %.17g %.17g %.17g\n", PT.x(), PT.y(), PT.z());
+        }
+        std::vector<cv::Point2f> m2 = p2;
+        std::vector<cv::Point3f> m3 = p3;
+        std::vector<double> mid = pid;
+        const bool ok = cur.findConnection(&old_kf, m2, m3, mid);
+        fprintf(o, "connection %d %d %d %d %d\nloop_info", ok ? 1 : 0, cur.pnp_status, cur.has_loop ? 1 : 0, cur.loop_index, (int)m3.size());
+        for (int k = 0; k < 8; ++k) fprintf(o, " %.17g", cur.has_loop ? cur.loop_info(k, 0) : 0.0);
+        const vg_kf_pnp_out& q = cur.pout;
+        fprintf(o, "\ntaps %d %d %d %d %d\n", q.ransac_best, q.ransac_iter, q.ransac_bound, q.refit_iters, q.refit_up);
+        fprintf(o, "pose %.17g %.17g %.17g %.17g %.17g %.17g\n", q.rvec[0], q.rvec[1], q.rvec[2], q.tvec[0], q.tvec[1], q.tvec[2]);
+        for (size_t k = 0; k < cur.match_points.match_id.size(); ++k)
+            fprintf(o, "m %d %.17g %.17g\n", cur.match_points.match_id[k], cur.match_points.match_xy[2 * k], cur.match_points.match_xy[2 * k + 1]);
+        fprintf(o, "tq");
+        for (int k = 0; k < 8; ++k) fprintf(o, " %.17g", cur.match_points.t_q_index[k]);
+        fprintf(o, "\n");
+    }
+    fclose(o);
+    vg_destroy(h);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 4 && !strcmp(argv[1], "kfpnp")) {
+        try { return replay_kfpnp(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay kfpnp: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "fe")) {
         try { return replay_fe(argv[2], argv[3], argc >= 5 ? argv[4] : nullptr); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay fe: %s\n", e.what()); return 1; }
@@ -939,6 +1010,6 @@ int main(int argc, char** argv) {
         try { return replay_sfm(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml> | vins_replay kfpnp <in.bin> <out.txt>\n");
     return 2;
 }

@@ -573,8 +573,32 @@ void pack_kf_record(const KF& kf, KfRecord& r) {
     r.rec.keypoints_xy = r.kp.data(); r.rec.scores = r.sc.data(); r.rec.norm_xy = r.nm.data(); r.rec.descriptors = r.de.data();
 }
 
+// one entry of vg_kf_pnp from the lists findConnection holds behind its first reduceVector round (cv::Point3f / cv::Point2f are three / two
+// packed floats; the vectors must outlive the call) and the keyframe's origin_vio_T / origin_vio_R, tic, qic; matched_id: ints, the
+// reference's vector<double> narrowed by the caller.  Everything else keeps the defaults of vg_kf_pnp_defaults.
+template <class KF, class P3, class P2>
+void pack_kf_pnp(const KF& kf, const std::vector<P3>& matched_3d, const std::vector<P2>& matched_2d_old_norm, const std::vector<int>& matched_id, vg_kf_pnp_in& in) {
+    static_assert(sizeof(P3) == 3 * sizeof(float) && sizeof(P2) == 2 * sizeof(float), "packed float points");
+    if (matched_3d.size() != matched_2d_old_norm.size() || (!matched_id.empty() && matched_id.size() != matched_3d.size()))
+        throw std::runtime_error("pack_kf_pnp: the lists differ in length");
+    vg_kf_pnp_defaults(&in);
+    in.n = (int)matched_3d.size();
+    in.point_3d = matched_3d.empty() ? nullptr : &matched_3d[0].x;
+    in.old_norm = matched_2d_old_norm.empty() ? nullptr : &matched_2d_old_norm[0].x;
+    in.point_id = matched_id.empty() ? nullptr : matched_id.data();
+    for (int r = 0; r < 3; ++r) {
+        in.origin_vio_T[r] = kf.origin_vio_T(r); in.tic[r] = kf.tic(r);
+        for (int c = 0; c < 3; ++c) { in.origin_vio_R[3 * r + c] = kf.origin_vio_R(r, c); in.qic[3 * r + c] = kf.qic(r, c); }
+    }
+}
+
 }  // namespace vg_pack
 
+// (the packer of vg_kf_pnp under the name the integration guide uses)
+template <class KF, class P3, class P2>
+void vg_pack_kf_pnp(const KF& kf, const std::vector<P3>& matched_3d, const std::vector<P2>& matched_2d_old_norm, const std::vector<int>& matched_id, vg_kf_pnp_in& in) {
+    vg_pack::pack_kf_pnp(kf, matched_3d, matched_2d_old_norm, matched_id, in);
+}
 // (the packer of vg_kf_add under the name the integration guide uses)
 template <class KF>
 void vg_pack_kf(const KF& kf, int slot, const vg_fe_camera& camera, vg_kf_in& in) {
