@@ -32,7 +32,8 @@ extern "C" {
                              * (added within 12, nothing existing changed: vg_fe_read_image_batch; vg_fe_camera, vg_fe_set_camera, vg_fe_lift;
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
                              * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot;
-                             * vg_kf_configure / _add / _get / _set / _match; vg_kf_pnp, vg_kf_pnp_defaults) */
+                             * vg_kf_configure / _add / _get / _set / _match; vg_kf_pnp, vg_kf_pnp_defaults; vg_voc_load, vg_bow_configure / _reset / _count / _get,
+                             * vg_kf_loop_detect) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -1309,7 +1310,8 @@ int vg_vio_end(vg_handle* h);
 /* ---- Loop closure: keyframe BRIEF descriptors and matching (added within ABI 12, nothing existing changed) ----------------------------
  * The integer-exact, batchable part of the pose graph's KeyFrame (pose_graph/src/keyframe.cpp): computeWindowBRIEFPoint and
  * computeBRIEFPoint with keypoints_norm (vg_kf_add), searchByBRIEFDes with the reduceVector step of findConnection:301-312
- * (vg_kf_match).  PnPRANSAC and the loop_info arithmetic behind it are vg_kf_pnp (the next block).  NOT here: DBoW2 loop detection, the 4-DoF
+ * (vg_kf_match).  PnPRANSAC and the loop_info arithmetic behind it are vg_kf_pnp (the next block), DBoW2 loop detection is vg_kf_loop_detect (the
+ * block after it).  NOT here: the 4-DoF
  * pose-graph optimisation, thumbnails and debug images.  Independent of vg_fe_configure: the pose graph's image is not the front
  * end's current frame.
  *
@@ -1516,6 +1518,116 @@ typedef struct vg_kf_pnp_out {
 } vg_kf_pnp_out;
 void vg_kf_pnp_defaults(vg_kf_pnp_in* in);        /* zero, struct_size and the defaults above; qic and origin_vio_R the identity */
 int vg_kf_pnp(vg_handle* h, int n_pairs, const vg_kf_pnp_in* in /* [n_pairs] */, vg_kf_pnp_out* out /* [n_pairs] */);
+
+/* ---- Loop closure: DBoW2 loop detection, batched (added within ABI 12, nothing existing changed) ----------------------------------------
+ * PoseGraph::detectLoop (pose_graph/src/pose_graph.cpp:304-386) and addKeyFrameIntoVoc for a batch of pose graphs: the vocabulary tree,
+ * one resident database per pose graph, the query, the decision and the add.  The input of a request is a filled vg_kf_* record: its
+ * `descriptors` are brief_descriptors of computeBRIEFPoint and never leave the device.  The returned loop_index goes to vg_kf_match as
+ * the old keyframe (the caller maps the database's entry ids, which are the keyframe indices when every keyframe is added in order, to
+ * its slots).  NOT offered, and left with the caller: optimize4DoF, thumbnails and debug images.
+ *
+ * DBoW2 is vendored in the reference (pose_graph/src/ThirdParty/DBoW, VocabularyBinary.*): READ from the reference as the definition, not
+ * recalled, and restated in tests/kf_bow_ref.py (the reference's DBoW2 is not compiled into the oracle).  Only what PoseGraph uses is
+ * offered: weighting TF_IDF (enum value 0), scoring L1_NORM (0), no direct index (db.setVocabulary(*voc, false, 0)).  That the shipped
+ * brief_k10L6.bin carries TF_IDF / L1_NORM is DBoW2's default and UNVERIFIED here (the file was not available).
+ *
+ *   vocabulary  (VocabularyBinary.hpp, TemplatedVocabulary::loadBin:1509-1561) the file's records: vg_voc_node x n_nodes, vg_voc_word x
+ *               n_words.  Node 0 is the root and has no record.  The children of a node are the records naming it as parent, IN RECORD
+ *               ORDER.  A node without children is a leaf.  Bit i of a descriptor is word i / 64, position i % 64, as in vg_kf_*.  The
+ *               tree need not be uniform.
+ *   word        (transform:1217-1258) start at the root; among the current node's children take the one with the smallest Hamming
+ *               distance to the descriptor, on a tie the FIRST in child order (the reference updates on d < best_d only); repeat until the
+ *               chosen node is a leaf: its word_id and weight.
+ *   BoW vector  (transform:1065-1121, BowVector::addWeight, normalize) over the descriptors in keypoint order: a word whose weight is not
+ *               > 0 is skipped ("stopped"), else v[word] += weight: for a word seen c times c - 1 sequential additions of the same
+ *               double, NOT c * weight.  Then norm = sum of fabs(v) in ascending word id, sequentially from 0; every value is divided by
+ *               norm if norm > 0.
+ *   query       (queryL1:656-723, db.query(desc, ret, 4, frame_index - 50)) max_id = frame_index - 50; entry e takes part iff e < max_id ||
+ *               max_id == -1 || e == n_entries - 1, n_entries counted BEFORE this frame is added: the last entry added always takes
+ *               part (ret[0], "the nearest neighbour's score"), and frame_index == 49 admits every entry.  For an entry with at least
+ *               one word in common, value = the sum over the common words in ascending word id of fabs(q - d) - fabs(q) - fabs(d),
+ *               accumulated sequentially, starting from the first term.  Entries without a common word do not appear.  Sorted ascending
+ *               by value, the first 4 kept; Score = -value / 2.0.  std::sort leaves the order of equal values to the platform: THIS
+ *               LIBRARY breaks ties by ascending entry id.
+ *   decision    (detectLoop:348-385) find_loop = n_results >= 1 && Score[0] > 0.05 && some i >= 1 has Score[i] > 0.015.  If find_loop &&
+ *               frame_index > 50: min_index = Id[0] unconditionally, lowered to every Id[i] < min_index with Score[i] > 0.015; loop_index =
+ *               min_index.  Otherwise loop_index = -1.
+ *   add         (db.add) the frame's vector becomes entry n_entries++, after the query.
+ * Additions, fabs, one division per word and one halving: nothing is multiplied and added in one expression, and the device result
+ * equals a float64 restatement bit for bit.
+ *
+ * vg_voc_load       validates on the host, then uploads the tree renumbered so that the children of a node are contiguous and in child
+ *                   order (one sibling group = one contiguous read of n_children x 32 bytes).  Word ids that leave the library are the
+ *                   file's.  k and L are the file's header: no node may have more than k children (k <= 65535), no leaf may lie deeper
+ *                   than L.  A second call replaces the vocabulary and empties every database.  Refused before anything is touched: a
+ *                   node id outside 1 .. n_nodes or repeated, a parent that is not a node or the root, a node not reachable from the
+ *                   root, a word on a node with children, a leaf without a word or with two, a word id outside 0 .. n_words - 1 or
+ *                   repeated, an empty root, more than k children, a leaf below level L, k or L < 1, a scoring / weighting other than
+ *                   VG_BOW_L1_NORM / VG_BOW_TF_IDF, a NULL table.
+ * vg_bow_configure  n_db independent resident databases (one pose graph each) of at most max_entries entries; a database stores its
+ *                   entries back to back in a pool of pool_words (word id, value) pairs with an offset table.  Calling it again replaces
+ *                   them.  Needs a vocabulary.  Refused: n_db, max_entries or pool_words < 1.
+ * vg_bow_reset      empties database db.
+ * vg_bow_get        one entry's vector (savePoseGraph, tests): n_words always; words / values (ascending word id) when non-NULL, refused
+ *                   when `capacity` is below n_words.
+ * vg_kf_loop_detect n requests in one call: one upload (the requests), VG_BOW_LAUNCHES launches over the batch, one download.
+ *                   flags: VG_BOW_QUERY | VG_BOW_ADD is detectLoop, VG_BOW_ADD alone is addKeyFrameIntoVoc, VG_BOW_QUERY alone queries
+ *                   without adding.  A record with no keypoints gives an empty vector: no results, and an empty entry if ADD.  The pool
+ *                   advances by the true word count.  Refused with VG_ERR_BAD_ARG before anything is touched: no vocabulary, no
+ *                   vg_bow_configure, no vg_kf_configure, a wrong struct_size, flags without QUERY and ADD or with other bits, db or slot
+ *                   out of range, a slot never filled, the same db twice in one call (the order would matter), ADD on a database with
+ *                   max_entries entries or with fewer free pool words than the record's keypoints (the upper bound of its distinct
+ *                   words, known before the launch). */
+#define VG_BOW_TF_IDF 0              /* DBoW2::WeightingType */
+#define VG_BOW_L1_NORM 0             /* DBoW2::ScoringType */
+#define VG_BOW_QUERY 1
+#define VG_BOW_ADD 2
+#define VG_BOW_MAX_RESULTS 4
+#define VG_BOW_STOPPED 0xFFFFFFFFu   /* word_of_keypoint of a descriptor that lands on a word whose weight is not > 0 */
+#define VG_BOW_LAUNCHES 4            /* walk, vector, score, tail */
+typedef struct vg_voc_node {         /* VINSLoop::Node, the file's record */
+    int32_t node_id, parent_id;
+    double weight;
+    uint64_t descriptor[4];
+} vg_voc_node;
+typedef struct vg_voc_word {         /* VINSLoop::Word */
+    int32_t node_id, word_id;
+} vg_voc_word;
+typedef struct vg_bow_entry {
+    int struct_size;             /* sizeof(vg_bow_entry) */
+    int capacity;                /* of words / values */
+    int n_words;                 /* out */
+    uint32_t* words;             /* ascending, or NULL */
+    double* values;              /* or NULL */
+} vg_bow_entry;
+typedef struct vg_bow_in {
+    int struct_size;             /* sizeof(vg_bow_in) */
+    int db;
+    int slot;                    /* a filled vg_kf_* record */
+    int frame_index;             /* detectLoop's frame_index (VG_BOW_QUERY) */
+    int flags;                   /* VG_BOW_QUERY | VG_BOW_ADD */
+} vg_bow_in;
+typedef struct vg_bow_out {
+    int struct_size;             /* sizeof(vg_bow_out), set by the caller */
+    int entry_id;                /* the entry this frame became, -1 without VG_BOW_ADD */
+    int n_results;               /* 0 .. VG_BOW_MAX_RESULTS (0 without VG_BOW_QUERY) */
+    int ids[VG_BOW_MAX_RESULTS]; /* ret[i].Id, -1 beyond n_results */
+    double scores[VG_BOW_MAX_RESULTS];   /* ret[i].Score, 0 beyond n_results */
+    int find_loop;
+    int loop_index;              /* detectLoop's return value */
+    int n_words;                 /* entries of the frame's BoW vector */
+    uint32_t* word_of_keypoint;  /* [n_keypoints of the record] taps, or NULL: the file's word id or VG_BOW_STOPPED */
+    uint32_t* bow_word;          /* [n_keypoints] capacity: the vector's word ids, ascending */
+    double* bow_value;           /* [n_keypoints] capacity: its values */
+    float* device_ms;            /* out[0] only: VG_BOW_LAUNCHES event intervals of the batch, or NULL */
+} vg_bow_out;
+int vg_voc_load(vg_handle* h, int k, int L, int scoring, int weighting, int n_nodes, const vg_voc_node* nodes /* [n_nodes] */, int n_words,
+                const vg_voc_word* words /* [n_words] */);
+int vg_bow_configure(vg_handle* h, int n_db, int max_entries, int pool_words);
+int vg_bow_reset(vg_handle* h, int db);
+int vg_bow_count(vg_handle* h, int db, int* n_entries, int* pool_used);     /* what database db holds (either pointer may be NULL) */
+int vg_bow_get(vg_handle* h, int db, int entry, vg_bow_entry* out);
+int vg_kf_loop_detect(vg_handle* h, int n, const vg_bow_in* in /* [n] */, vg_bow_out* out /* [n] */);
 
 #ifdef __cplusplus
 }

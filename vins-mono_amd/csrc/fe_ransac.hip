@@ -415,3 +415,6 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
 
 // ---- vg_kf_pnp: PnPRANSAC (EPnP samples, the 5-point registrator, the refit) and findConnection's loop gate for a batch of pairs
 #include "kf_pnp.h"
+
+// ---- vg_voc_load / vg_bow_* / vg_kf_loop_detect: DBoW2 loop detection (the vocabulary walk, the BoW vector, the L1 query, the decision, the add)
+#include "kf_bow.h"

@@ -341,6 +341,7 @@ struct KfState {
     char* rec = nullptr;              // the records, then the pattern
     short* pat = nullptr;
     std::vector<char> filled;
+    std::vector<int> kept;            // per slot: the record's n_keypoints as the host last saw it (vg_kf_add / vg_kf_set; kf_bow.h sizes by it)
     char* buf = nullptr;              // scratch of vg_kf_add / vg_kf_match, grown on demand
     size_t buf_cap = 0;
     PinnedBuf<char> h_up, h_down;
@@ -395,6 +396,7 @@ extern "C" int vg_kf_configure(vg_handle* h, int width, int height, int max_keyp
     s->pat = (short*)(s->rec + recs);
     h->kf = s;
     s->filled.assign(n_slots, 0);
+    s->kept.assign(n_slots, 0);
     if ((e = hipMemsetAsync(s->rec, 0, recs, h->stream)) != hipSuccess) return fail(e);
     short pat4[1024];                                       // test i: x1 y1 x2 y2 side by side, one 8-byte load
     for (int i = 0; i < 256; ++i)
@@ -518,6 +520,7 @@ extern "C" int vg_kf_add(vg_handle* h, int n, const vg_kf_in* in, vg_kf_out* out
     for (int k = 0; k < n; ++k) {
         vg_kf_out& o = out[k];
         o.n_keypoints = hd[4 * k]; o.status = hd[4 * k + 1]; o.n_kept = hd[4 * k + 2];
+        s->kept[in[k].slot] = o.n_kept;
         if (!want) continue;
         const KfView v(s, down + 16 * (size_t)n + (size_t)s->rec_bytes * k);
         const size_t nk = (size_t)o.n_kept, nw = (size_t)in[k].n_window;
@@ -588,6 +591,7 @@ extern "C" int vg_kf_set(vg_handle* h, int slot, const vg_kf_record* rec) {
     if ((e = hipMemcpyAsync(s->rec + (size_t)slot * s->rec_bytes, r, s->rec_bytes, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail(e);
     s->filled[slot] = 1;
+    s->kept[slot] = rec->n_keypoints;
     return VG_OK;
 }
 

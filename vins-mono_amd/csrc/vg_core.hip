@@ -13,6 +13,7 @@ extern "C" void ba_seq_release(vg_handle* h);
 extern "C" int vg_ba_rccl_finalize(vg_handle* h) __attribute__((weak));
 // (weak: a program linked without csrc/fe_ransac.hip has no keyframe records to release)
 extern "C" void kf_release(vg_handle* h) __attribute__((weak));
+extern "C" void bow_release(vg_handle* h) __attribute__((weak));
 
 extern "C" int vg_abi_version(void) { return VG_ABI_VERSION; }
 
@@ -81,6 +82,7 @@ extern "C" int vg_destroy(vg_handle* h) {
     (void)hipFree(P.mout); (void)hipFree(P.miout); (void)hipFree(P.mscr); (void)hipFree(P.rb1); (void)hipFree(P.rb2);
     if (h->fe) fe_state_destroy(h->fe);
     if (kf_release) kf_release(h);
+    if (bow_release) bow_release(h);
     (void)hipFree(h->ransac_buf);
     (void)hipFree(h->relpose_buf);
     (void)hipFree(h->relpose_tab);

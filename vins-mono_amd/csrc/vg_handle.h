@@ -162,4 +162,5 @@ struct vg_handle {
     void* relpose_tab = nullptr;                  // its resident RANSAC tables: the n-only schedules and the bounds for n = 15 .. relpose_nmax
     int relpose_nmax = 0;
     void* kf = nullptr;                           // KfState of vg_kf_configure (csrc/kf_brief.h): the resident keyframe records
+    void* bow = nullptr;                          // BowState of vg_voc_load / vg_bow_configure (csrc/kf_bow.h): the vocabulary tree and the databases
 };

@@ -820,3 +820,125 @@ def kf_pnp(handle, pairs, timed=False):
     if timed and n:
         res[0]["device_ms"] = ms.copy()
     return res
+
+
+# ---- loop closure: DBoW2 loop detection (vg_voc_load, vg_bow_*, vg_kf_loop_detect) -----------------------------------------------------------
+BOW_TF_IDF, BOW_L1_NORM = 0, 0
+BOW_QUERY, BOW_ADD = 1, 2
+BOW_STOPPED = 0xFFFFFFFF
+BOW_LAUNCHES = 4
+BOW_KERNELS = ("walk", "vector", "score", "tail")
+_u32 = C.POINTER(C.c_uint32)
+VOC_NODE = np.dtype([("node_id", "<i4"), ("parent_id", "<i4"), ("weight", "<f8"), ("descriptor", "<u8", (4,))])      # VINSLoop::Node
+VOC_WORD = np.dtype([("node_id", "<i4"), ("word_id", "<i4")])                                                        # VINSLoop::Word
+
+
+class BowEntry(C.Structure):
+    """vg_bow_entry (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("capacity", C.c_int), ("n_words", C.c_int), ("words", _u32), ("values", _f8)]
+
+
+class BowIn(C.Structure):
+    """vg_bow_in (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("db", C.c_int), ("slot", C.c_int), ("frame_index", C.c_int), ("flags", C.c_int)]
+
+
+class BowOut(C.Structure):
+    """vg_bow_out (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_int), ("entry_id", C.c_int), ("n_results", C.c_int), ("ids", C.c_int * 4), ("scores", C.c_double * 4),
+                ("find_loop", C.c_int), ("loop_index", C.c_int), ("n_words", C.c_int), ("word_of_keypoint", _u32), ("bow_word", _u32),
+                ("bow_value", _f8), ("device_ms", _f4)]
+
+
+def _bow_lib(handle):
+    L = handle.lib
+    L.vg_voc_load.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.vg_bow_configure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.vg_bow_reset.argtypes = [C.c_void_p, C.c_int]
+    L.vg_bow_count.argtypes = [C.c_void_p, C.c_int, _i4, _i4]
+    L.vg_bow_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(BowEntry)]
+    L.vg_kf_loop_detect.argtypes = [C.c_void_p, C.c_int, C.POINTER(BowIn), C.POINTER(BowOut)]
+    return L
+
+
+def read_voc_bin(path):
+    """The reference's binary vocabulary (VocabularyBinary.hpp): 6 x int32 k L scoring weighting nNodes nWords, the node records, the
+    word records.  Returns (k, L, scoring, weighting, nodes [VOC_NODE], words [VOC_WORD])."""
+    with open(path, "rb") as f:
+        k, L, scoring, weighting, n_nodes, n_words = np.frombuffer(f.read(24), "<i4")
+        nodes = np.frombuffer(f.read(VOC_NODE.itemsize * int(n_nodes)), VOC_NODE)
+        words = np.frombuffer(f.read(VOC_WORD.itemsize * int(n_words)), VOC_WORD)
+    if len(nodes) != n_nodes or len(words) != n_words:
+        raise ValueError(path + ": truncated")
+    return int(k), int(L), int(scoring), int(weighting), nodes, words
+
+
+def voc_load(handle, k, L, nodes, words, scoring=BOW_L1_NORM, weighting=BOW_TF_IDF, n_nodes=None, n_words=None):
+    """vg_voc_load: nodes a VOC_NODE array (the file's records, in file order), words a VOC_WORD array"""
+    nodes = None if nodes is None else np.ascontiguousarray(nodes, VOC_NODE)
+    words = None if words is None else np.ascontiguousarray(words, VOC_WORD)
+    nn = (0 if nodes is None else len(nodes)) if n_nodes is None else int(n_nodes)
+    nw = (0 if words is None else len(words)) if n_words is None else int(n_words)
+    handle._chk(_bow_lib(handle).vg_voc_load(handle.h, int(k), int(L), int(scoring), int(weighting), nn, None if nodes is None else nodes.ctypes.data,
+                                             nw, None if words is None else words.ctypes.data), "vg_voc_load")
+
+
+def bow_configure(handle, n_db, max_entries, pool_words):
+    handle._chk(_bow_lib(handle).vg_bow_configure(handle.h, int(n_db), int(max_entries), int(pool_words)), "vg_bow_configure")
+
+
+def bow_reset(handle, db):
+    handle._chk(_bow_lib(handle).vg_bow_reset(handle.h, int(db)), "vg_bow_reset")
+
+
+def bow_count(handle, db):
+    """(entries, pool words in use) of database db"""
+    ne, pu = C.c_int(0), C.c_int(0)
+    handle._chk(_bow_lib(handle).vg_bow_count(handle.h, int(db), C.byref(ne), C.byref(pu)), "vg_bow_count")
+    return ne.value, pu.value
+
+
+def bow_get(handle, db, entry):
+    """vg_bow_get: (words uint32 ascending, values float64) of one entry"""
+    L = _bow_lib(handle)
+    e = BowEntry()
+    e.struct_size = C.sizeof(BowEntry)
+    handle._chk(L.vg_bow_get(handle.h, int(db), int(entry), C.byref(e)), "vg_bow_get")
+    w, v = np.zeros(max(e.n_words, 1), np.uint32), np.zeros(max(e.n_words, 1), np.float64)
+    e.capacity, e.words, e.values = len(w), w.ctypes.data_as(_u32), v.ctypes.data_as(_f8)
+    handle._chk(L.vg_bow_get(handle.h, int(db), int(entry), C.byref(e)), "vg_bow_get")
+    return w[:e.n_words].copy(), v[:e.n_words].copy()
+
+
+def kf_loop_detect(handle, requests, taps=None, timed=False):
+    """vg_kf_loop_detect for a list of requests (db, slot, frame_index, flags) on a ba.Handle with vg_kf_* records.  taps: the capacity of
+    the tap arrays (the records' max_keypoints), or None for no taps.  One dict per request: entry_id, n_results, ids, scores (float64,
+    n_results of them), find_loop, loop_index, n_words and with taps word_of_keypoint (capacity-long: the caller knows the record's
+    count), bow_word, bow_value; with `timed` the first dict also holds device_ms [BOW_LAUNCHES]."""
+    L = _bow_lib(handle)
+    n = len(requests)
+    ins, outs, keep = (BowIn * max(n, 1))(), (BowOut * max(n, 1))(), []
+    ms = np.zeros(BOW_LAUNCHES, np.float32)
+    for i, (db, slot, frame_index, flags) in enumerate(requests):
+        a, o = ins[i], outs[i]
+        a.struct_size, a.db, a.slot, a.frame_index, a.flags = C.sizeof(BowIn), int(db), int(slot), int(frame_index), int(flags)
+        o.struct_size = C.sizeof(BowOut)
+        bufs = None
+        if taps is not None:
+            bufs = (np.full(max(int(taps), 1), 0xDEADBEEF, np.uint32), np.zeros(max(int(taps), 1), np.uint32), np.zeros(max(int(taps), 1), np.float64))
+            o.word_of_keypoint, o.bow_word, o.bow_value = bufs[0].ctypes.data_as(_u32), bufs[1].ctypes.data_as(_u32), bufs[2].ctypes.data_as(_f8)
+        keep.append(bufs)
+    if timed and n:
+        outs[0].device_ms = ms.ctypes.data_as(_f4)
+    handle._chk(L.vg_kf_loop_detect(handle.h, n, ins, outs), "vg_kf_loop_detect")
+    res = []
+    for i in range(n):
+        o, bufs = outs[i], keep[i]
+        d = {"entry_id": o.entry_id, "n_results": o.n_results, "ids": np.array(o.ids[:o.n_results], np.int32),
+             "scores": np.array(o.scores[:o.n_results], np.float64), "find_loop": o.find_loop, "loop_index": o.loop_index, "n_words": o.n_words}
+        if bufs is not None:
+            d.update(word_of_keypoint=bufs[0].copy(), bow_word=bufs[1][:o.n_words].copy(), bow_value=bufs[2][:o.n_words].copy())
+        res.append(d)
+    if timed and n:
+        res[0]["device_ms"] = ms.copy()
+    return res

@@ -43,6 +43,8 @@
 //     host only: prints the four lists of 256 integers that BriefExtractor reads from the yml.
 //   vins_replay exrot <in.bin> <out.txt>
 //     the extrinsic-rotation calibration of processImage, one vg_init_exrot call per frame (replay_exrot below).
+//   vins_replay bow <voc.bin> <frames.bin> <out.txt>
+//     BriefVocabulary and PoseGraph::loadVocabulary / detectLoop (host/pose_graph.h, vg_kf_loop_detect through vg_pack_bow; replay_bow below).
 //   vins_replay kfpnp <in.bin> <out.txt>
 //     KeyFrame::PnPRANSAC and findConnection's second half (vg_kf_pnp through vg_pack_kf_pnp) over the matched lists of a file
 //     (replay_kfpnp below).
@@ -63,6 +65,7 @@
 #include "estimator.h"
 #include "feature_tracker.h"
 #include "keyframe.h"
+#include "pose_graph.h"
 #include "resident_estimator.h"
 #include "vg_pack.h"
 
@@ -956,7 +959,62 @@ static int replay_kfpnp(const char* in, const char* out) {
     return 0;
 }
 
+// vins_replay bow <voc.bin> <frames.bin> <out.txt>: BriefVocabulary, PoseGraph::loadVocabulary and PoseGraph::detectLoop (host/pose_graph.h,
+// vg_pack_bow) over a BOW1 file (tests/kf_bow_ref.write_frames: int32 'BOW1', n_frames, the first frame_index; per frame n and n x 4
+// 64-bit words).  Every frame becomes a KeyFrame of stored descriptors in slot 0 and goes through detectLoop on one database.  A line per
+// frame: frame_index, the return value, find_loop, the entry id, n_words, n_results, then id:score (the double's bits, hexadecimal) each.
+static int replay_bow(const char* voc_path, const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("bow file"); return 2; }
+    int hdr[3];
+    rd.i(hdr, 3);
+    if (hdr[0] != 0x31574F42 || hdr[1] < 0) { fprintf(stderr, "not a BOW1 file\n"); return 2; }
+    std::vector<std::vector<BRIEF::bitset>> frames((size_t)hdr[1]);
+    size_t most = 1, total = 1;
+    for (auto& fr : frames) {
+        int n = 0;
+        rd.i(&n, 1);
+        if (n < 0) throw std::runtime_error("bow file: a negative count");
+        fr.resize((size_t)n);
+        if (n && fread(fr.data(), sizeof(BRIEF::bitset), n, rd.f) != (size_t)n) throw std::runtime_error("bow file truncated");
+        most = std::max(most, (size_t)n); total += (size_t)n;
+    }
+    fclose(rd.f);
+    vg_handle* h = nullptr;
+    if (vg_create(&h) != VG_OK) { fprintf(stderr, "vg_create failed\n"); return 1; }
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    int rc = 0;
+    try {
+        int16_t pattern[1024] = {0};
+        if (vg_kf_configure(h, 64, 64, (int)most, 1, 1, pattern) != VG_OK) throw std::runtime_error(vg_last_error(h));
+        PoseGraph pg(h, 0);
+        pg.loadVocabulary(voc_path);
+        PoseGraph::configure(h, 1, (int)frames.size() + 1, (int)total);
+        for (size_t i = 0; i < frames.size(); ++i) {
+            const std::vector<cv::KeyPoint> kp(frames[i].size());
+            KeyFrame kf(h, 0, 0.05 * (double)i, hdr[2] + (int)i, kp, kp, frames[i]);
+            const int loop = pg.detectLoop(&kf, kf.index);
+            const vg_bow_out& q = pg.last;
+            fprintf(o, "%d %d %d %d %d %d", kf.index, loop, q.find_loop, q.entry_id, q.n_words, q.n_results);
+            for (int k = 0; k < q.n_results; ++k) {
+                unsigned long long u;
+                memcpy(&u, &q.scores[k], 8);
+                fprintf(o, " %d:%016llx", q.ids[k], u);
+            }
+            fprintf(o, "\n");
+        }
+    } catch (const std::exception& e) { fprintf(stderr, "vins_replay bow: %s\n", e.what()); rc = 1; }
+    fclose(o);
+    vg_destroy(h);
+    return rc;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && !strcmp(argv[1], "bow")) {
+        try { return replay_bow(argv[2], argv[3], argv[4]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay bow: %s\n", e.what()); return 1; }
+    }
     if (argc >= 4 && !strcmp(argv[1], "kfpnp")) {
         try { return replay_kfpnp(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay kfpnp: %s\n", e.what()); return 1; }
@@ -1010,6 +1068,6 @@ int main(int argc, char** argv) {
         try { return replay_sfm(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml> | vins_replay kfpnp <in.bin> <out.txt>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml> | vins_replay kfpnp <in.bin> <out.txt> | vins_replay bow <voc.bin> <frames.bin> <out.txt>\n");
     return 2;
 }

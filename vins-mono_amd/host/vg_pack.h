@@ -592,8 +592,23 @@ void pack_kf_pnp(const KF& kf, const std::vector<P3>& matched_3d, const std::vec
     }
 }
 
+// one request of vg_kf_loop_detect for a keyframe whose record is resident (kf.slot): flags VG_BOW_QUERY | VG_BOW_ADD is detectLoop,
+// VG_BOW_ADD alone addKeyFrameIntoVoc.  `out` is zeroed and gets its struct_size; the caller adds tap arrays if it wants them.
+template <class KF>
+void pack_bow(const KF& kf, int db, int frame_index, int flags, vg_bow_in& in, vg_bow_out& out) {
+    std::memset(&in, 0, sizeof(in));
+    std::memset(&out, 0, sizeof(out));
+    in.struct_size = (int)sizeof(in); out.struct_size = (int)sizeof(out);
+    in.db = db; in.slot = kf.slot; in.frame_index = frame_index; in.flags = flags;
+}
+
 }  // namespace vg_pack
 
+// (the packer of vg_kf_loop_detect under the name the integration guide uses)
+template <class KF>
+void vg_pack_bow(const KF& kf, int db, int frame_index, int flags, vg_bow_in& in, vg_bow_out& out) {
+    vg_pack::pack_bow(kf, db, frame_index, flags, in, out);
+}
 // (the packer of vg_kf_pnp under the name the integration guide uses)
 template <class KF, class P3, class P2>
 void vg_pack_kf_pnp(const KF& kf, const std::vector<P3>& matched_3d, const std::vector<P2>& matched_2d_old_norm, const std::vector<int>& matched_id, vg_kf_pnp_in& in) {
