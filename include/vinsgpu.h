@@ -33,7 +33,7 @@ extern "C" {
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
                              * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot;
                              * vg_kf_configure / _add / _get / _set / _match; vg_kf_pnp, vg_kf_pnp_defaults; vg_voc_load, vg_bow_configure / _reset / _count / _get,
-                             * vg_kf_loop_detect) */
+                             * vg_kf_loop_detect; vg_pg_optimize, vg_pg_defaults) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -1524,7 +1524,7 @@ int vg_kf_pnp(vg_handle* h, int n_pairs, const vg_kf_pnp_in* in /* [n_pairs] */,
  * one resident database per pose graph, the query, the decision and the add.  The input of a request is a filled vg_kf_* record: its
  * `descriptors` are brief_descriptors of computeBRIEFPoint and never leave the device.  The returned loop_index goes to vg_kf_match as
  * the old keyframe (the caller maps the database's entry ids, which are the keyframe indices when every keyframe is added in order, to
- * its slots).  NOT offered, and left with the caller: optimize4DoF, thumbnails and debug images.
+ * its slots).  optimize4DoF is vg_pg_optimize (the last block).  NOT offered, and left with the caller: thumbnails and debug images.
  *
  * DBoW2 is vendored in the reference (pose_graph/src/ThirdParty/DBoW, VocabularyBinary.*): READ from the reference as the definition, not
  * recalled, and restated in tests/kf_bow_ref.py (the reference's DBoW2 is not compiled into the oracle).  Only what PoseGraph uses is
@@ -1628,6 +1628,113 @@ int vg_bow_reset(vg_handle* h, int db);
 int vg_bow_count(vg_handle* h, int db, int* n_entries, int* pool_used);     /* what database db holds (either pointer may be NULL) */
 int vg_bow_get(vg_handle* h, int db, int entry, vg_bow_entry* out);
 int vg_kf_loop_detect(vg_handle* h, int n, const vg_bow_in* in /* [n] */, vg_bow_out* out /* [n] */);
+
+/* ---- Loop closure: 4-DoF pose-graph optimisation, batched (added within ABI 12, nothing existing changed) -------------------------------
+ * One pass of the body of PoseGraph::optimize4DoF (pose_graph/src/pose_graph.cpp:403-579) for n_graphs independent pose graphs in one
+ * call: the graph, the solve, updatePose of the optimised keyframes, the drift, and the drift applied to the keyframes behind cur_index.
+ * Plain arrays in and out, no configure call.  Synchronous: one upload, VG_PG_LAUNCHES launch over the whole batch (one workgroup per
+ * graph, all iterations inside it), one download; device scratch grows on demand inside the handle.  A graph's status never touches its
+ * neighbours; a batch equals the single calls bit for bit.
+ *
+ * The graph and the cost functors are READ from the reference; Ceres (problem, loss corrector, trust region) is RECALLED, NOT PINNED, as
+ * for vg_init_sfm.  [FIXED]: this library's choice where Ceres leaves the result to a general-purpose solver; [DEVIATION]: knowingly
+ * different.
+ *  input     The slice of keyframelist that optimize4DoF walks, in list order: the n_kf keyframes with index >= first_looped_index
+ *            through the END of the list; the first n_opt of them (up to and including cur_index) are optimised, the others only receive
+ *            the drift (:562-571).  loop_info is vg_kf_pnp_out::loop_info: relative_t | relative_q | relative_yaw (degrees); has_loop,
+ *            loop_index and loop_info are read for the optimised keyframes only.
+ *  graph     (:445-519) local index i over the optimised keyframes.  Variables per node: yaw_i (degrees) and t_i; pitch_i, roll_i are
+ *            constants; (yaw, pitch, roll) = Utility::R2ypr(vio_R_i), t_i = vio_T_i.  A node is CONSTANT when index == first_looped_index or
+ *            sequence == 0.  Chain edges (i-j) -> i for j = 1 .. 4 while i-j >= 0 and the sequences are equal: relative_t = vio_R_{i-j}^T
+ *            (t_i - t_{i-j}), relative_yaw = yaw_i - yaw_{i-j}, NOT normalised, no loss.  Loop edge of a node with has_loop: from the node
+ *            whose index == loop_index to i, relative_t = loop_info[0..2], relative_yaw = loop_info[7], HuberLoss(huber_delta).  Edge slot
+ *            5 i + (j - 1) is the chain edge from i-j, slot 5 i + 4 the loop edge; a slot without an edge counts as zero everywhere.
+ *            [DEVIATION] the reference passes vio_R through a quaternion and back (tmp_q = tmp_r; q.toRotationMatrix(); q.inverse() * v):
+ *            the matrix is used directly, the difference is rounding.
+ *  residual  (pose_graph.h:88-247, as written) edge a -> b with R = YawPitchRollToRotationMatrix(yaw_a, pitch_a, roll_a) (degrees,
+ *            x / 180 * pi): e[c] = (R[c] d0 + R[3+c] d1 + R[6+c] d2) - relative_t[c], d = t_b - t_a; e[3] = NormalizeAngle(yaw_b - yaw_a -
+ *            relative_yaw), divided by 10 on a loop edge (FourDOFWeightError, weight 1).  NormalizeAngle is the reference's one
+ *            conditional wrap (> 180: - 360; < -180: + 360), slope 1.  Parameters of a node in the order yaw, t.  The Jacobian is the exact
+ *            derivative: d e[c] / d t_b = (R[c], R[3+c], R[6+c]) = -d e[c] / d t_a; d e[c] / d yaw_a = (R[c] d1 - R[3+c] d0) (pi / 180);
+ *            d e[3] / d yaw_b = 1 (loop: 1 / 10) = -d e[3] / d yaw_a.  AngleLocalParameterization: Plus = NormalizeAngle(yaw + delta),
+ *            Jacobian 1.
+ *  loss      s = e.e (ascending).  Huber: s <= delta^2: rho = s, rho' = 1; else rho = 2 delta sqrt(s) - delta^2, rho' = max(DBL_MIN,
+ *            delta / sqrt(s)).  rho'' <= 0 everywhere, so Ceres' Corrector takes its first branch: residual and Jacobian rows times
+ *            sqrt(rho'), no alpha term.  cost = (sum of rho over the edge slots) / 2; edges between two constant nodes count in the cost.
+ *  sums      [FIXED] a SUM OVER A LIST (edge slots, parameters) is: thread t of 256 adds the entries t, t + 256, ... in ascending order;
+ *            the 256 partial sums are folded by halves (p[t] += p[t + h], h = 128, 64 .. 1).  A product of small matrices sums its inner
+ *            index ascending from the first term.  The terms of a node are gathered in the order: its own edge slots 0 .. 4 (as b), the
+ *            chain edges leaving it to i+1 .. i+4 (as a), the loop edges arriving at it in ascending source (as a); every term is formed
+ *            first and then added.  Nothing is multiplied and added in one rounding (-ffp-contract=off).
+ *  minimiser Exactly the loop of the vg_init_sfm block with the cap max_iters: radius 1e4, Jacobi scale 1 / (1 + column norm) from the
+ *            FIRST Jacobian, D = sqrt(clamp(diag, 1e-6, 1e32) / radius) and D D added, gradient tolerance 1e-10 (unscaled, max-norm over the
+ *            free nodes) at the start and after every accepted step, parameter tolerance 1e-8 and function tolerance 1e-6 in this order
+ *            before the step is judged, rho > 1e-3, the radius rules, five invalid steps in a row: FAILURE.  x and |x| run over the free
+ *            nodes.  [FIXED] the blocks of JtJ are formed from the unscaled Jacobian and scaled afterwards, s_p (A_pq s_q), the diagonal
+ *            blocks mirrored from their lower triangle; the model change is -sum over the edge slots of u.(r + u / 2), u = Ja da + Jb db
+ *            with d = scale * y the step in the parameters.  max_solver_time stays out, as in the reference (commented out).
+ *  step      [FIXED] (Ceres: SPARSE_NORMAL_CHOLESKY; the step is the same to the residual below.)  A = JtJ + D D over the free nodes in
+ *            list order, 4x4 blocks.  M = the block band of A of half-width 4 blocks: every chain edge in full, both diagonal blocks of
+ *            every loop edge, its off-diagonal block only inside the band; positive definite as a sum of positive semidefinite terms
+ *            plus D D > 0.  Band block (f, f-d): the chain edge between the two nodes, then the loop edge.  Unpivoted Cholesky of M as a
+ *            scalar band of half-width 19, column by column (every entry loses its products in ascending column order): a pivot that is
+ *            not positive and finite makes the step invalid; the inverse 1 / sqrt(pivot) is kept and MULTIPLIED with, in the
+ *            factorisation and in both sweeps.  A y = -g by conjugate gradients preconditioned with M from y = 0: r = b, z = M^-1 r,
+ *            p = z; per iteration q = A p, alpha = r.z / p.q (p.q not > 0: invalid), y += alpha p, r -= alpha q, z = M^-1 r, done when
+ *            r.z <= 1e-24 r0.z0 (sqrt(r.z) <= 1e-12 sqrt(r0.z0)), else p = z + (r.z / previous r.z) p.  VG_PG_MAX_CG iterations without
+ *            that make the step invalid.  q = A p by rows: band blocks d = 4 .. 1, the diagonal block, the transposed blocks of the rows
+ *            f+1 .. f+4, the node's own out-of-band loop block, the transposed ones of the loops arriving in ascending source, D D p.
+ *  after     (:532-571) T = t_i, R = Utility::ypr2R(yaw_i, pitch_i, roll_i) ((Rz Ry) Rx) for the optimised keyframes, constant ones
+ *            included; yaw_drift = R2ypr(R_cur).x - R2ypr(vio_R_cur).x, r_drift = ypr2R(yaw_drift, 0, 0), t_drift = t_cur - r_drift
+ *            vio_T_cur; behind cur_index T = r_drift vio_T + t_drift, R = r_drift vio_R.
+ * status: VG_PG_OK; VG_PG_NO_EDGES nothing is free: the poses are the VIO poses through the same formulas, the drift is computed all the
+ * same, iterations 0; VG_PG_NUMERIC the initial cost or a returned number is not finite: T, R and the drift come back as zeros.
+ * VG_PG_OK says that the numbers are finite, not that the solve went well: five invalid steps in a row (VG_PG_MAX_CG iterations without
+ * convergence is one way to an invalid step) end with VG_PG_OK and termination VG_TERM_FAILURE; read termination and it_cg.
+ * Refused with VG_ERR_BAD_ARG before anything is uploaded (vg_last_error names the cause; no output is touched, the handle stays usable): a
+ * wrong struct_size, n_kf outside 1 .. VG_PG_MAX_KEYFRAMES, n_opt outside 1 .. n_kf, a NULL table, index not strictly ascending, a first
+ * keyframe below first_looped_index, sequence < 0, a loop_index below first_looped_index, not in the slice or not before its own
+ * keyframe, a non-finite input, max_iters outside 1 .. VG_PG_MAX_ITERS, huber_delta not positive.
+ * NOT offered, and left with the caller: the thread around the pass and its 2 s sleep, thumbnails, debug images, map save / load, ROS. */
+#define VG_PG_OK 0
+#define VG_PG_NO_EDGES 1
+#define VG_PG_NUMERIC 2
+#define VG_PG_MAX_KEYFRAMES 2048
+#define VG_PG_MAX_ITERS 8
+#define VG_PG_MAX_CG 128
+#define VG_PG_LAUNCHES 1
+typedef struct vg_pg_in {
+    size_t struct_size;          /* sizeof(vg_pg_in); vg_pg_defaults sets it */
+    int n_kf;                    /* 1 .. VG_PG_MAX_KEYFRAMES */
+    int n_opt;                   /* 1 .. n_kf: the keyframes up to and including cur_index */
+    int first_looped_index;
+    int max_iters;               /* 5 */
+    double huber_delta;          /* 0.1 */
+    const int* index;            /* [n_kf] strictly ascending */
+    const int* sequence;         /* [n_kf] */
+    const int* has_loop;         /* [n_kf] */
+    const int* loop_index;       /* [n_kf] a global index (read where has_loop) */
+    const double* vio_T;         /* [n_kf][3] */
+    const double* vio_R;         /* [n_kf][9] row-major */
+    const double* loop_info;     /* [n_kf][8] (read where has_loop) */
+} vg_pg_in;
+typedef struct vg_pg_out {
+    size_t struct_size;          /* sizeof(vg_pg_out), set by the caller */
+    int status;                  /* VG_PG_* */
+    int termination;             /* VG_TERM_* */
+    int iterations;
+    int n_edges, n_loop_edges, n_free;
+    double initial_cost, final_cost;
+    double yaw_drift, r_drift[9], t_drift[3];
+    double it_cost[VG_PG_MAX_ITERS], it_radius[VG_PG_MAX_ITERS], it_cost_cand[VG_PG_MAX_ITERS], it_model[VG_PG_MAX_ITERS];
+    int it_flags[VG_PG_MAX_ITERS];       /* bit0 valid, bit1 accepted */
+    int it_cg[VG_PG_MAX_ITERS];          /* conjugate-gradient iterations of the row's solve */
+    double* T;                   /* [n_kf][3] what updatePose receives, or NULL */
+    double* R;                   /* [n_kf][9] or NULL */
+    float* device_ms;            /* out[0] only: VG_PG_LAUNCHES event intervals of the batch, or NULL */
+} vg_pg_out;
+void vg_pg_defaults(vg_pg_in* in);                /* zero, struct_size, max_iters 5, huber_delta 0.1 */
+int vg_pg_optimize(vg_handle* h, int n_graphs, const vg_pg_in* in /* [n_graphs] */, vg_pg_out* out /* [n_graphs] */);
 
 #ifdef __cplusplus
 }

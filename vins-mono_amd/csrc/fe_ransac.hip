@@ -418,3 +418,6 @@ extern "C" int vg_fe_reject_with_f(vg_handle* h, const float* cur_un_xy, const f
 
 // ---- vg_voc_load / vg_bow_* / vg_kf_loop_detect: DBoW2 loop detection (the vocabulary walk, the BoW vector, the L1 query, the decision, the add)
 #include "kf_bow.h"
+
+// ---- vg_pg_optimize: one pass of optimize4DoF (the 4-DoF graph, Ceres' trust region, a banded Cholesky inside conjugate gradients, the drift)
+#include "kf_pgo.h"

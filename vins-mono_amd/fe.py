@@ -942,3 +942,91 @@ def kf_loop_detect(handle, requests, taps=None, timed=False):
     if timed and n:
         res[0]["device_ms"] = ms.copy()
     return res
+
+
+# ---- loop closure: 4-DoF pose-graph optimisation (vg_pg_optimize) -----------------------------------------------------------------------
+PG_OK, PG_NO_EDGES, PG_NUMERIC = 0, 1, 2
+PG_MAX_KEYFRAMES, PG_MAX_ITERS, PG_MAX_CG, PG_LAUNCHES = 2048, 8, 128, 1
+PG_KERNELS = ("solve",)
+
+
+class PgIn(C.Structure):
+    """vg_pg_in (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("n_kf", C.c_int), ("n_opt", C.c_int), ("first_looped_index", C.c_int), ("max_iters", C.c_int),
+                ("huber_delta", C.c_double), ("index", _i4), ("sequence", _i4), ("has_loop", _i4), ("loop_index", _i4), ("vio_T", _f8),
+                ("vio_R", _f8), ("loop_info", _f8)]
+
+
+class PgOut(C.Structure):
+    """vg_pg_out (include/vinsgpu.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("status", C.c_int), ("termination", C.c_int), ("iterations", C.c_int), ("n_edges", C.c_int),
+                ("n_loop_edges", C.c_int), ("n_free", C.c_int), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("yaw_drift", C.c_double), ("r_drift", C.c_double * 9), ("t_drift", C.c_double * 3),
+                ("it_cost", C.c_double * PG_MAX_ITERS), ("it_radius", C.c_double * PG_MAX_ITERS), ("it_cost_cand", C.c_double * PG_MAX_ITERS),
+                ("it_model", C.c_double * PG_MAX_ITERS), ("it_flags", C.c_int * PG_MAX_ITERS), ("it_cg", C.c_int * PG_MAX_ITERS),
+                ("T", _f8), ("R", _f8), ("device_ms", _f4)]
+
+
+_PG_TABLES = (("index", np.int32, 1), ("sequence", np.int32, 1), ("has_loop", np.int32, 1), ("loop_index", np.int32, 1),
+              ("vio_T", np.float64, 3), ("vio_R", np.float64, 9), ("loop_info", np.float64, 8))
+
+
+def pg_fill(L, a, o, g):
+    """one vg_pg_in / vg_pg_out pair from a graph dict (see pg_optimize); returns the arrays that must outlive the call"""
+    L.vg_pg_defaults(C.byref(a))
+    keep = []
+    for k, dt, w in _PG_TABLES:
+        arr = None if g.get(k) is None else np.ascontiguousarray(g[k], dt).reshape(-1)
+        setattr(a, k, None if arr is None else arr.ctypes.data_as(_i4 if dt is np.int32 else _f8))
+        keep.append(arr)
+    a.n_kf = int(g["n_kf"]) if "n_kf" in g else len(keep[0])
+    a.n_opt = int(g["n_opt"]) if "n_opt" in g else a.n_kf
+    a.first_looped_index = int(g["first_looped_index"])
+    for k in ("max_iters", "huber_delta"):
+        if k in g:
+            setattr(a, k, g[k])
+    if "struct_size" in g:
+        a.struct_size = int(g["struct_size"])
+    cap = a.n_kf if 0 < a.n_kf <= PG_MAX_KEYFRAMES else 1
+    T, R = np.zeros((cap, 3), np.float64), np.zeros((cap, 3, 3), np.float64)
+    o.struct_size = int(g.get("out_struct_size", C.sizeof(PgOut)))
+    o.T, o.R = T.ctypes.data_as(_f8), R.ctypes.data_as(_f8)
+    return keep, T, R
+
+
+def pg_lib(handle):
+    L = handle.lib
+    L.vg_pg_defaults.argtypes = [C.POINTER(PgIn)]
+    L.vg_pg_defaults.restype = None
+    L.vg_pg_optimize.argtypes = [C.c_void_p, C.c_int, C.POINTER(PgIn), C.POINTER(PgOut)]
+    return L
+
+
+def pg_optimize(handle, graphs, timed=False):
+    """vg_pg_optimize for a list of pose graphs on a ba.Handle.  A graph is a dict: index, sequence, has_loop, loop_index [n_kf] (int32),
+    vio_T [n_kf, 3], vio_R [n_kf, 3, 3], loop_info [n_kf, 8], first_looped_index, optionally n_opt (n_kf otherwise), max_iters, huber_delta
+    (vg_pg_defaults otherwise); `n_kf` overrides the row count (the refusal tests).  One dict per graph: status, termination, iterations,
+    n_edges, n_loop_edges, n_free, initial_cost, final_cost, T [n_kf, 3], R [n_kf, 3, 3], yaw_drift, r_drift [3, 3], t_drift and the trace
+    rows it_cost, it_radius, it_cost_cand, it_model, it_flags, it_cg (`iterations` of them); with `timed` the first dict also holds
+    device_ms [PG_LAUNCHES]."""
+    L = pg_lib(handle)
+    n = len(graphs)
+    ins, outs, keep = (PgIn * max(n, 1))(), (PgOut * max(n, 1))(), []
+    ms = np.zeros(PG_LAUNCHES, np.float32)
+    for i, g in enumerate(graphs):
+        keep.append(pg_fill(L, ins[i], outs[i], g))
+    if timed and n:
+        outs[0].device_ms = ms.ctypes.data_as(_f4)
+    handle._chk(L.vg_pg_optimize(handle.h, n, ins, outs), "vg_pg_optimize")
+    res = []
+    for i in range(n):
+        o, (_, T, R) = outs[i], keep[i]
+        k = o.iterations
+        res.append({"status": o.status, "termination": o.termination, "iterations": k, "n_edges": o.n_edges, "n_loop_edges": o.n_loop_edges,
+                    "n_free": o.n_free, "initial_cost": o.initial_cost, "final_cost": o.final_cost, "T": T, "R": R, "yaw_drift": o.yaw_drift,
+                    "r_drift": np.array(o.r_drift).reshape(3, 3), "t_drift": np.array(o.t_drift),
+                    "it_cost": np.array(o.it_cost[:k]), "it_radius": np.array(o.it_radius[:k]), "it_cost_cand": np.array(o.it_cost_cand[:k]),
+                    "it_model": np.array(o.it_model[:k]), "it_flags": np.array(o.it_flags[:k], np.int32), "it_cg": np.array(o.it_cg[:k], np.int32)})
+    if timed and n:
+        res[0]["device_ms"] = ms.copy()
+    return res

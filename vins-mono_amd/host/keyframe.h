@@ -149,8 +149,19 @@ class KeyFrame {
         return (int)matched_2d_cur.size() > MIN_LOOP_NUM;
     }
 
+    // the pose members PoseGraph::addKeyFrame and optimize4DoF go through (keyframe.cpp:522-575)
+    void getVioPose(Eigen::Vector3d& _T_w_i, Eigen::Matrix3d& _R_w_i) const { _T_w_i = vio_T_w_i; _R_w_i = vio_R_w_i; }
+    void getPose(Eigen::Vector3d& _T_w_i, Eigen::Matrix3d& _R_w_i) const { _T_w_i = T_w_i; _R_w_i = R_w_i; }
+    void updatePose(const Eigen::Vector3d& _T_w_i, const Eigen::Matrix3d& _R_w_i) { T_w_i = _T_w_i; R_w_i = _R_w_i; }
+    void updateVioPose(const Eigen::Vector3d& _T_w_i, const Eigen::Matrix3d& _R_w_i) { vio_T_w_i = _T_w_i; vio_R_w_i = _R_w_i; T_w_i = vio_T_w_i; R_w_i = vio_R_w_i; }
+    Eigen::Vector3d getLoopRelativeT() const { return Eigen::Vector3d(loop_info(0, 0), loop_info(1, 0), loop_info(2, 0)); }
+    Eigen::Quaterniond getLoopRelativeQ() const { return Eigen::Quaterniond(loop_info(3, 0), loop_info(4, 0), loop_info(5, 0), loop_info(6, 0)); }
+    double getLoopRelativeYaw() const { return loop_info(7, 0); }
+
     double time_stamp;
     int index;
+    int local_index = 0;                // optimize4DoF's position in its slice
+    int sequence = 1;
     cv::Mat image;
     std::vector<cv::Point2f> point_2d_uv;
     std::vector<cv::KeyPoint> keypoints, keypoints_norm, window_keypoints;

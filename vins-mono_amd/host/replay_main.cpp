@@ -48,6 +48,9 @@
 //   vins_replay kfpnp <in.bin> <out.txt>
 //     KeyFrame::PnPRANSAC and findConnection's second half (vg_kf_pnp through vg_pack_kf_pnp) over the matched lists of a file
 //     (replay_kfpnp below).
+//   vins_replay pgo <in.bin> <out.txt>
+//     PoseGraph's pose bookkeeping and ONE pass of optimize4DoF (host/pose_graph.h, vg_pg_optimize through vg_pack_pg) over the slice of
+//     a keyframe list from a file: every keyframe goes through shiftToBase / addLoop / appendKeyFrame, then the pass (replay_pgo below).
 //   vins_replay relpose <in.bin> <out.txt>
 //     Estimator::relativePose(relative_R, relative_T, l) (vg_init_relpose) over f_manager.feature from a file; writes the return value,
 //     the VG_RELPOSE_* status, l, relative_R and relative_T and, when no frame passes, what the zero-argument initialStructure() returns
@@ -1010,7 +1013,72 @@ static int replay_bow(const char* voc_path, const char* in, const char* out) {
     return rc;
 }
 
+// The graph file of tests/kf_pgo_ref.write_file: int32 n_kf n_opt first_looped_index max_iters, float64 huber_delta, the tables.  The
+// class runs the reference's 5 iterations and HuberLoss(0.1).
+static int replay_pgo(const char* in, const char* out) {
+    Reader rd{fopen(in, "rb")};
+    if (!rd.f) { perror("pgo file"); return 2; }
+    int hdr[4];
+    double delta;
+    rd.i(hdr, 4); rd.d(&delta, 1);
+    const int n = hdr[0];
+    if (n < 1 || hdr[3] != 5 || delta != 0.1) { fprintf(stderr, "the class runs 5 iterations and HuberLoss(0.1)\n"); return 2; }
+    std::vector<int> index(n), sequence(n), has_loop(n), loop_index(n);
+    std::vector<double> T(3 * (size_t)n), R(9 * (size_t)n), info(8 * (size_t)n);
+    rd.i(index.data(), n); rd.i(sequence.data(), n); rd.i(has_loop.data(), n); rd.i(loop_index.data(), n);
+    rd.d(T.data(), 3 * n); rd.d(R.data(), 9 * n); rd.d(info.data(), 8 * n);
+    fclose(rd.f);
+    vg_handle* h = nullptr;
+    if (vg_create(&h) != VG_OK) { fprintf(stderr, "vg_create failed\n"); return 1; }
+    FILE* o = fopen(out, "w");
+    if (!o) { perror("out"); return 2; }
+    {
+        PoseGraph pg(h, 0);
+        pg.earliest_loop_index = hdr[2];                        // (an earlier pass found it: the file holds the slice from there on)
+        std::vector<std::unique_ptr<KeyFrame>> kfs;
+        for (int i = 0; i < n; ++i) {
+            Vector3d t(T[3 * i], T[3 * i + 1], T[3 * i + 2]);
+            Matrix3d r;
+            for (int e = 0; e < 9; ++e) r(e / 3, e % 3) = R[9 * (size_t)i + e];
+            kfs.emplace_back(new KeyFrame(h, 0.1 * i, index[i], t, r, std::vector<cv::Point3f>(), std::vector<double>()));
+            KeyFrame* kf = kfs.back().get();
+            kf->sequence = sequence[i];
+            pg.global_index = index[i];                         // (the file's indices need not be consecutive)
+            pg.shiftToBase(kf);
+            if (has_loop[i] && i < hdr[1]) {
+                KeyFrame* old_kf = pg.getKeyFrame(loop_index[i]);
+                if (!old_kf) throw std::runtime_error("pgo file: a loop_index that is not an earlier keyframe");
+                kf->has_loop = true; kf->loop_index = loop_index[i];
+                for (int k = 0; k < 8; ++k) kf->loop_info(k, 0) = info[8 * (size_t)i + k];
+                pg.addLoop(kf, old_kf);
+            }
+            pg.appendKeyFrame(kf);
+        }
+        const bool ran = pg.optimize4DoF();
+        const vg_pg_out& q = pg.pg;
+        fprintf(o, "pass %d %d %d %d %d %d %d\n", ran ? 1 : 0, q.status, q.termination, q.iterations, q.n_edges, q.n_loop_edges, q.n_free);
+        fprintf(o, "cost %.17g %.17g\ndrift %.17g", q.initial_cost, q.final_cost, pg.yaw_drift);
+        for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", pg.r_drift(e / 3, e % 3));
+        fprintf(o, " %.17g %.17g %.17g\n", pg.t_drift.x(), pg.t_drift.y(), pg.t_drift.z());
+        for (KeyFrame* kf : pg.keyframelist) {
+            Vector3d t;
+            Matrix3d r;
+            kf->getPose(t, r);
+            fprintf(o, "kf %d %d %.17g %.17g %.17g", kf->index, kf->local_index, t.x(), t.y(), t.z());
+            for (int e = 0; e < 9; ++e) fprintf(o, " %.17g", r(e / 3, e % 3));
+            fprintf(o, "\n");
+        }
+    }
+    fclose(o);
+    vg_destroy(h);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 4 && !strcmp(argv[1], "pgo")) {
+        try { return replay_pgo(argv[2], argv[3]); }
+        catch (const std::exception& e) { fprintf(stderr, "vins_replay pgo: %s\n", e.what()); return 1; }
+    }
     if (argc >= 5 && !strcmp(argv[1], "bow")) {
         try { return replay_bow(argv[2], argv[3], argv[4]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay bow: %s\n", e.what()); return 1; }
@@ -1068,6 +1136,6 @@ int main(int argc, char** argv) {
         try { return replay_sfm(argv[2], argv[3]); }
         catch (const std::exception& e) { fprintf(stderr, "vins_replay sfm: %s\n", e.what()); return 1; }
     }
-    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml> | vins_replay kfpnp <in.bin> <out.txt> | vins_replay bow <voc.bin> <frames.bin> <out.txt>\n");
+    fprintf(stderr, "usage: vins_replay fe <frames.bin> <out.txt> [config.yaml] | vins_replay fe_batch <list.txt> <out_prefix> [config.yaml] | vins_replay ba <sequence.bin> <out.csv> | vins_replay seq <frames.bin> <out.csv> | vins_replay vio <window.bin> <frames.bin> <out.csv> | vins_replay align <in.bin> <out.txt> | vins_replay sfm <in.bin> <out.txt> | vins_replay relpose <in.bin> <out.txt> | vins_replay exrot <in.bin> <out.txt> | vins_replay kf <in.bin> <out.txt> <brief_pattern.yml> | vins_replay kfpnp <in.bin> <out.txt> | vins_replay bow <voc.bin> <frames.bin> <out.txt> | vins_replay pgo <in.bin> <out.txt>\n");
     return 2;
 }

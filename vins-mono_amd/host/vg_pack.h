@@ -602,8 +602,42 @@ void pack_bow(const KF& kf, int db, int frame_index, int flags, vg_bow_in& in, v
     in.db = db; in.slot = kf.slot; in.frame_index = frame_index; in.flags = flags;
 }
 
+// one graph of vg_pg_optimize: the slice of keyframelist (a list of pointers to keyframes with index, sequence, has_loop, loop_index,
+// loop_info, vio_T_w_i, vio_R_w_i) that optimize4DoF walks -- index >= first_looped_index through the END of the list; the keyframes up
+// to and including cur_index are the optimised ones.  Sets local_index as the reference does.  The tables live in `p`.
+struct PgIn {
+    vg_pg_in in;
+    std::vector<int> index, sequence, has_loop, loop_index;
+    std::vector<double> T, R, info;
+};
+template <class List>
+void pack_pg(List& keyframelist, int first_looped_index, int cur_index, PgIn& p) {
+    p.index.clear(); p.sequence.clear(); p.has_loop.clear(); p.loop_index.clear(); p.T.clear(); p.R.clear(); p.info.clear();
+    int n_opt = 0;
+    bool past = false;                  // behind cur_index: the keyframes that only receive the drift
+    for (auto it = keyframelist.begin(); it != keyframelist.end(); ++it) {
+        auto& kf = **it;
+        if (kf.index < first_looped_index) continue;
+        if (!past) { kf.local_index = n_opt++; past = kf.index == cur_index; }
+        p.index.push_back(kf.index); p.sequence.push_back(kf.sequence); p.has_loop.push_back(kf.has_loop ? 1 : 0); p.loop_index.push_back(kf.loop_index);
+        for (int r = 0; r < 3; ++r) p.T.push_back(kf.vio_T_w_i(r));
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) p.R.push_back(kf.vio_R_w_i(r, c));
+        for (int k = 0; k < 8; ++k) p.info.push_back(kf.has_loop ? kf.loop_info(k, 0) : 0.0);
+    }
+    if (!past) throw std::runtime_error("pack_pg: cur_index is not in the slice");
+    vg_pg_defaults(&p.in);
+    p.in.n_kf = (int)p.index.size(); p.in.n_opt = n_opt; p.in.first_looped_index = first_looped_index;
+    p.in.index = p.index.data(); p.in.sequence = p.sequence.data(); p.in.has_loop = p.has_loop.data(); p.in.loop_index = p.loop_index.data();
+    p.in.vio_T = p.T.data(); p.in.vio_R = p.R.data(); p.in.loop_info = p.info.data();
+}
+
 }  // namespace vg_pack
 
+// (the packer of vg_pg_optimize under the name the integration guide uses)
+template <class List>
+void vg_pack_pg(List& keyframelist, int first_looped_index, int cur_index, vg_pack::PgIn& p) {
+    vg_pack::pack_pg(keyframelist, first_looped_index, cur_index, p);
+}
 // (the packer of vg_kf_loop_detect under the name the integration guide uses)
 template <class KF>
 void vg_pack_bow(const KF& kf, int db, int frame_index, int flags, vg_bow_in& in, vg_bow_out& out) {
