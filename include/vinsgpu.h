@@ -33,7 +33,7 @@ extern "C" {
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
                              * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot;
                              * vg_kf_configure / _add / _get / _set / _match; vg_kf_pnp, vg_kf_pnp_defaults; vg_voc_load, vg_bow_configure / _reset / _count / _get,
-                             * vg_kf_loop_detect; vg_pg_optimize, vg_pg_defaults) */
+                             * vg_kf_loop_detect; vg_pg_optimize, vg_pg_defaults; vg_ba_batch_marg_info) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -939,6 +939,27 @@ int vg_ba_seq_get_relo(vg_handle* h, int window, vg_ba_relo_result* out);
  * Takes effect at the next upload / vg_ba_optimize. */
 enum { VG_MARG_SQRT = 0, VG_MARG_EIGEN = 1 };
 int vg_ba_set_marg_mode(vg_handle* h, int mode);
+/* Added within ABI 12, nothing existing changed.  Which variants of the marginalization kernel a window of the uploaded batch ran
+ * through -- read-only, for tests and diagnosis; valid once the priors of the run are on the host (vg_ba_batch_download with priors,
+ * vg_ba_batch_download_prior, vg_ba_optimize), VG_ERR_BAD_ARG before.  out[0..3] = prior valid, n, m, kept blocks; out[4] = sweeps |
+ * attempts << 8 of the eigen-decomposition of the dropped block (0: it left by elimination); out[5] = rank << 16 of the square-root
+ * factor, or sweeps | attempts << 8 of the kept block's eigen-decomposition; out[6] = the path word below (0 for a window that
+ * produced no prior; builds with -DBA_PROFILE keep a cycle stamp there instead); out[7] = 0.
+ *   stage 1, the dropped block leaves (VG_MARGPATH_S1_MASK):  _DIRECT two-stage elimination on the matrix cores, A' written into the
+ *       square root's tile; _BLOCK_LDS / _BLOCK_GLB certified block elimination with its right-hand sides staged in LDS / read from
+ *       global memory; _VH_EIG / _JACOBI_LDS / _JACOBI_GLB eigen pseudo-inverse (16-lane groups / one-sided Jacobi in LDS / in global memory);
+ *   certificate lambda_min(Amm) > 1e-7 (VG_MARGPATH_CERT_MASK): 0 not evaluated, _PASSED, _FAILED (every elimination that evaluated it was
+ *       refused: the eigen pseudo-inverse ran);
+ *   Schur product A' = Arr - Arm Amm^+ Amr behind stage 1 (VG_MARGPATH_SCHUR_MASK): 0 none (_DIRECT forms A' itself), _LDS, _GLB operands;
+ *   stage 2, the factor of the kept block (VG_MARGPATH_S2_MASK): _SQRT / _SQRT_GLB pivoted Cholesky in LDS / global memory,
+ *       _VH_EIG / _JACOBI_LDS / _JACOBI_GLB the eigen form. */
+enum { VG_MARGPATH_S1_MASK = 0xf, VG_MARGPATH_S1_DIRECT = 1, VG_MARGPATH_S1_BLOCK_LDS = 2, VG_MARGPATH_S1_BLOCK_GLB = 3, VG_MARGPATH_S1_VH_EIG = 4,
+       VG_MARGPATH_S1_JACOBI_LDS = 5, VG_MARGPATH_S1_JACOBI_GLB = 6,
+       VG_MARGPATH_CERT_MASK = 0x30, VG_MARGPATH_CERT_PASSED = 0x10, VG_MARGPATH_CERT_FAILED = 0x20,
+       VG_MARGPATH_SCHUR_MASK = 0xc0, VG_MARGPATH_SCHUR_LDS = 0x40, VG_MARGPATH_SCHUR_GLB = 0x80,
+       VG_MARGPATH_S2_MASK = 0xf00, VG_MARGPATH_S2_SQRT = 0x100, VG_MARGPATH_S2_SQRT_GLB = 0x200, VG_MARGPATH_S2_VH_EIG = 0x300,
+       VG_MARGPATH_S2_JACOBI_LDS = 0x400, VG_MARGPATH_S2_JACOBI_GLB = 0x500 };
+int vg_ba_batch_marg_info(vg_handle* h, int window, int out[8]);
 /* ABI 12.  Form of the IMU factors' weight sqrt_info = LLT(covariance^-1).matrixL()^T (factor/imu_factor.h:64).  The Cholesky factor of
  * the inverse is unique, so both forms are the same matrix up to rounding -- the covariance is badly conditioned, and the rounding of
  * this factor is one of the inputs of the trust-region decisions (profiles/r06_flip_stats.json):

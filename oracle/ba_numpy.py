@@ -885,7 +885,9 @@ def marginalize(prob, st, flag, eps=1e-8):
 def schur_extended(A, bvec, m):
     """Schur complement of the leading m x m block in 80-bit extended precision (np.longdouble), exact inverse
     (no eps cut).  NOT part of the reference algorithm: a yardstick that tells whose double-precision
-    eigen-based pseudo-inverse (numpy's or the device's) is closer to the truth when they disagree at 1e-8."""
+    eigen-based pseudo-inverse (numpy's or the device's) is closer to the truth when they disagree at 1e-8.  It assumes a positive
+    definite dropped block: on a rank-deficient one (MARGIN_SECOND_NEW) it divides by rounding-noise pivots -- tests/marg_ref.py has the
+    generalised Schur complement for that case."""
     Al = np.array(A, dtype=np.longdouble)
     bl = np.array(bvec, dtype=np.longdouble)
     M = 0.5 * (Al[:m, :m] + Al[:m, :m].T)

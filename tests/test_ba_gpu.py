@@ -459,6 +459,18 @@ def test_marginalize_second_new_parity(handle):
     st_g, sm, pr_g = handle.ba_optimize(prob2, ba.VG_MARGIN_SECOND_NEW)
     _check_prior(pr_g, pr_o)
     assert (B.KIND_POSE, K - 2) not in pr_g['blocks'] and pr_g['n'] == prob2['prior']['n'] - 6
+    # schur_extended (inside _check_prior) assumes a definite dropped block; a MARGIN_SECOND_NEW pose block need not be one.  The yardstick
+    # that is valid either way: the generalised Schur complement of tests/marg_ref.py, entry by entry in the prior's own scale, bounded by
+    # marg_ref.M x the float64 loss of the same reference on THIS window (floored; only the linear prior is evaluated)
+    import marg_ref as R
+    ref = R.reference_prior(prob2, B.MARGIN_SECOND_NEW, np.longdouble, ('sqrt',))
+    assert R.has_gap(ref)
+    r64 = R.reference_prior(prob2, B.MARGIN_SECOND_NEW, np.float64, ('sqrt',))
+    amb = R.cut_ambiguity(ref, r64, R.NOISE_FACTOR)
+    e, e64 = R.prior_error(pr_g, ref, amb, state=st_g), R.prior_error(r64['sqrt'], ref, amb)
+    assert e['same_shape'] and e['x0_equal'] and e['rank_ok'] and e['tail_zero'], e
+    for k in ('H', 'g', 'c'):
+        assert e[k] <= R.M['gpu'][k] * max(R.FLOOR_PRIOR_ONLY, e64[k]), (k, R.describe(e))
 
 
 def test_marginalize_second_new_keeps_old_prior_when_pose_absent(handle):

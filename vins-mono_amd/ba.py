@@ -11,6 +11,11 @@ from . import lib
 VG_MAX_ITERS = 32
 VG_MARGIN_OLD, VG_MARGIN_SECOND_NEW, VG_MARGIN_NONE = 0, 1, 2
 VG_MARG_SQRT, VG_MARG_EIGEN = 0, 1     # vg_ba_set_marg_mode
+# fields of the marginalization path word (vg_ba_batch_marg_info, include/vinsgpu.h VG_MARGPATH_*)
+MARGPATH_STAGE1 = (None, 'direct', 'block_lds', 'block_glb', 'vh_eig', 'jacobi_lds', 'jacobi_glb') + (None,) * 9
+MARGPATH_CERT = (None, 'passed', 'failed', None)
+MARGPATH_SCHUR = (None, 'lds', 'glb', None)
+MARGPATH_STAGE2 = (None, 'sqrt', 'sqrt_glb', 'vh_eig', 'jacobi_lds', 'jacobi_glb') + (None,) * 10
 VG_IMU_INFO_FACTOR, VG_IMU_INFO_REFERENCE = 0, 1     # vg_ba_set_imu_info_mode
 VG_OK = 0
 VG_ABI_VERSION = 12         # include/vinsgpu.h
@@ -479,6 +484,17 @@ class Handle:
     def ba_set_marg_mode(self, mode):
         """VG_MARG_SQRT (0, default) / VG_MARG_EIGEN (1): form of the prior factor (include/vinsgpu.h)."""
         self._chk(self.lib.vg_ba_set_marg_mode(self.h, int(mode)), "vg_ba_set_marg_mode")
+
+    def ba_marg_info(self, window=0):
+        """vg_ba_batch_marg_info of a window of the downloaded batch: dict(valid, n, m, nblocks, eig1, eig2, word = the raw path word,
+        stage1, cert, schur, stage2 = its fields by name; include/vinsgpu.h VG_MARGPATH_*)."""
+        self.lib.vg_ba_batch_marg_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        out = (C.c_int * 8)()
+        self._chk(self.lib.vg_ba_batch_marg_info(self.h, int(window), out), "vg_ba_batch_marg_info")
+        w = int(out[6])
+        return dict(valid=int(out[0]), n=int(out[1]), m=int(out[2]), nblocks=int(out[3]), eig1=int(out[4]), eig2=int(out[5]), word=w,
+                    stage1=MARGPATH_STAGE1[w & 0xf], cert=MARGPATH_CERT[(w >> 4) & 3], schur=MARGPATH_SCHUR[(w >> 6) & 3],
+                    stage2=MARGPATH_STAGE2[(w >> 8) & 0xf])
 
     def ba_set_imu_info_mode(self, mode):
         """VG_IMU_INFO_FACTOR (0, default) / VG_IMU_INFO_REFERENCE (1): form of the IMU factors' sqrt_info (include/vinsgpu.h)."""

@@ -409,7 +409,7 @@ extern "C" int vg_ba_batch_upload(vg_handle* h, int nwin, const vg_ba_problem* c
         ba_seq_release(h);
     }
     B.uploaded = false;              // a failed upload must not leave the previous batch's flags next to the new layout
-    B.solved_recorded = false;
+    B.solved_recorded = false; B.marg_info_ready = false;
     static const bool debug_upload = getenv("VG_DEBUG_UPLOAD") != nullptr;      // phase times of this call on stderr
     const auto t_0 = std::chrono::steady_clock::now();
     auto t_prev = t_0;
@@ -619,7 +619,7 @@ extern "C" int vg_ba_batch_upload(vg_handle* h, int nwin, const vg_ba_problem* c
     }
     B.any_margin = false;
     for (int w = 0; w < nwin; ++w) B.any_margin = B.any_margin || B.margin[w] != VG_MARGIN_NONE;
-    B.solved_recorded = false;
+    B.solved_recorded = false; B.marg_info_ready = false;
     B.uploaded = true;
     return VG_OK;
 }
@@ -727,6 +727,14 @@ extern "C" int vg_ba_set_fused_min_windows(vg_handle* h, int min_windows) {
 extern "C" int vg_ba_batch_is_fused(vg_handle* h) {
     if (!h || !h->ba.uploaded) return VG_ERR_BAD_ARG;
     return h->ba.L.la_on ? 1 : 0;
+}
+extern "C" int vg_ba_batch_marg_info(vg_handle* h, int window, int out[8]) {
+    if (!h || !out || !h->ba.uploaded || window < 0 || window >= h->ba.nwin) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    if (!B.marg_info_ready) { h->err = "vg_ba_batch_marg_info before the priors of this run were downloaded"; return VG_ERR_BAD_ARG; }
+    const int* mi = B.h_miout.data() + (size_t)window * B.L.mi_stride;
+    for (int k = 0; k < 8; ++k) out[k] = mi[k];
+    return VG_OK;
 }
 extern "C" int vg_ba_launch_stats(vg_handle* h, int* mode, long long* graph_launches, long long* graph_captures) {
     if (!h) return VG_ERR_BAD_ARG;
@@ -915,6 +923,7 @@ static int unpack_priors(vg_handle* h, int nwin, vg_ba_prior* const* pri) {
     BaBatch& B = h->ba;
     const BaLayout& L = B.L;
     static const bool debug_marg = getenv("VG_DEBUG_MARG") != nullptr;      // phase stamps of -DBA_PROFILE builds
+    B.marg_info_ready = B.any_margin;        // (every caller has copied and synchronised miout by now)
     std::vector<int> too_small(64, 0);
     tl_pack_cap = h->ba.pack_threads;
     for_windows(nwin, [&](int t, int w) {
@@ -1253,7 +1262,7 @@ extern "C" int vg_ba_seq_begin(vg_handle* h, int nwin, const vg_ba_seq_config* c
     HIPCHK(h, hipMemcpy(D.sp, sp.data(), sp.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     Q.nwin = nwin; Q.cur = 0; Q.active = true;
-    B.solved_recorded = false;
+    B.solved_recorded = false; B.marg_info_ready = false;
     return VG_OK;
 }
 

@@ -1534,6 +1534,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
     MPROF(3);
     // ---- M4: Amm^+ [Amr | bmm], Schur complement
     bool direct = false;                   // (uniform) A' / b' already stand in the square root's LDS tile / gV
+    int pw = 0;                            // (uniform) which variants ran: VG_MARGPATH_* fields (include/vinsgpu.h), stored in mi[6] at the end
     {
         const bool in_lds = m <= ld;
         double* Mm = in_lds ? eM : gM;
@@ -1549,6 +1550,9 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
         // when every eigenvalue exceeds 1e-8; that is certified here by  lambda_min(Amm) >= 1 / ||Amm^-1||_F > 1e-7, the norm
         // summed block by block (Amm^-1 = [B11 B12; B12^T B22], B11 = P'^-1, B12 = -P'^-1 W D^-1, B22 = D^-1 - D^-1 W^T B12)
         // without storing B22.  Otherwise (or if P' is not positive definite) the eigen-decomposition below runs.
+        // D^-1 is the pseudo-inverse at the reference's cut: a landmark with d_l <= eps (a track seen under no translation; its coupling row
+        // is of the order sqrt(d_l)) takes 1 / d_l := 0 in both eliminations -- the direction the eigen pseudo-inverse drops -- and the
+        // certificate speaks for the rest of the block.
         const int md = m - n0, ml = n0;
         // ---- Round 6: the Schur complement of the dropped block in two stages on the matrix cores, without Amm^-1 [Amr | bmm].
         // With C = the md dropped camera columns followed by the n kept columns and the gradient (q = md + n + 1 indices), Z = the
@@ -1579,9 +1583,13 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 if (c.tid == 0) *okf = 1;
                 double bad = 0.0;
                 for (int l = c.tid; l < ml; l += MG_NT) {
+                    // (a landmark whose own information is at or below the cut -- a track seen under no translation -- is an eigen-direction
+                    //  the reference's pseudo-inverse drops, its coupling row being of the order sqrt(d): it leaves with 1 / d := 0, NOT
+                    //  through the eigen pseudo-inverse of the whole block, whose float64 resolution u |Amm| (~0.05 with IMU weights of
+                    //  1e14) is coarser than the bias entries of A')
                     const double d = Ag[(size_t)(md + l) * posmax + md + l];
-                    bad += (d > 0.0 && d < 1e300) ? 0.0 : 1.0;
-                    dinv[l] = 1.0 / d;
+                    bad += (d >= 0.0 && d < 1e300) ? 0.0 : 1.0;
+                    dinv[l] = d > MG_EPS ? 1.0 / d : 0.0;
                 }
                 for (int k = c.tid; k < md * ml; k += MG_NT) {
                     const int p = k / ml, l = k - p * ml;
@@ -1728,7 +1736,9 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 direct = *okf != 0 && bad == 0.0 && fro > 0.0 && fro < 1e14;              // 1 / sqrt(fro) > 1e-7
                 __syncthreads();
                 MPROF(15);
+                pw |= VG_MARGPATH_CERT_FAILED;                                            // (replaced below by whichever elimination passes)
                 if (direct) {
+                    pw = VG_MARGPATH_S1_DIRECT | VG_MARGPATH_CERT_PASSED;
                     // ---- [A' | b'] = G'[md:, md:] - X^T X  ->  the square root's tile (eM, leading dimension ld) and b' (gV)
                     const int nt = ldx >> 4, ntile = nt * (nt + 1) / 2;
                     const int jc = c.lane & 15, kq = c.lane >> 4;
@@ -1764,7 +1774,10 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
             double* B12 = eV;                // [md][ml]
             int* okf = (int*)(red + 18);
             if (c.tid == 0) *okf = 1;
-            for (int l = c.tid; l < ml; l += MG_NT) dl[l] = A[(size_t)(md + l) * posmax + md + l];
+            for (int l = c.tid; l < ml; l += MG_NT) {            // (d <= eps: cut as above -- every x / d below is 0 for that landmark)
+                const double d = A[(size_t)(md + l) * posmax + md + l];
+                dl[l] = (d >= 0.0 && d <= MG_EPS) ? __builtin_huge_val() : d;
+            }
             for (int k = c.tid; k < md * ml; k += MG_NT) {
                 const int p = k / ml, l = k - p * ml;
                 Wl[k] = 0.5 * (A[(size_t)p * posmax + md + l] + A[(size_t)(md + l) * posmax + p]);
@@ -1848,6 +1861,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
             bad = mg_block_sum(c, red, bad);
             inverse_ok = *okf != 0 && bad == 0.0 && fro > 0.0 && fro < 1e14;      // 1 / sqrt(fro) > 1e-7
             __syncthreads();
+            pw |= VG_MARGPATH_CERT_FAILED;
             if (inverse_ok) {
                 // T2 = Amm^-1 [Amr | bmm]: column j of the right-hand side is A[:, m + j] (j < n) or bv (j == n)
                 const int nc = n + 1;
@@ -1858,6 +1872,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 double* U = stage ? B12 + md * ml : T1;      // [md][nc]  u = R1 - W D^-1 R2, then X1 = P'^-1 u
                 double* X1 = stage ? U : T2;
                 const int ldx = stage ? nc : mcap + 1;
+                pw = (stage ? VG_MARGPATH_S1_BLOCK_LDS : VG_MARGPATH_S1_BLOCK_GLB) | VG_MARGPATH_CERT_PASSED;
                 if (stage) {
                     for (int k = c.tid; k < m * nc; k += MG_NT) {
                         const int r = k / nc, j = k - r * nc;
@@ -1920,6 +1935,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
 #ifdef BA_PROFILE
         if (c.tid == 0) { mi[6] = (int)((clock64() - _t1) >> 10); mi[7] = (int)((_t1 - _tstart) >> 10); }
 #endif
+        pw |= fast1 ? VG_MARGPATH_S1_VH_EIG : in_lds ? VG_MARGPATH_S1_JACOBI_LDS : VG_MARGPATH_S1_JACOBI_GLB;
         if (c.tid == 0) mi[4] = sw1;        // sweeps | Cholesky attempts << 8 of the Amm eigen-decomposition
         MPROF(4);
         // T1 = Lambda^+ V^T [Amr | bmm]   (m x (n+1))
@@ -1951,6 +1967,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
         if (n * m <= ld * ld && m * (n + 1) <= ld * ld) {
             // both operands through LDS (the two eigen-solver tiles are free here): the m-term dot product of every entry used to
             // be a chain of global round trips (125K of the kernel's 850K cycles)
+            pw |= VG_MARGPATH_SCHUR_LDS;
             double* Arm = eM;                    // [n][m]
             double* T2s = eV;                    // [m][n + 1]
             __syncthreads();
@@ -1967,6 +1984,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
                 if (j < n) gM[i * posmax + j] = s; else gV[i] = s;
             }
         } else {
+            pw |= VG_MARGPATH_SCHUR_GLB;
             for (int k = c.tid; k < n * (n + 1); k += MG_NT) {
                 const int i = k / (n + 1), j = k % (n + 1);
                 double s = (j < n) ? A[(m + i) * posmax + m + j] : bv[m + i];
@@ -1998,6 +2016,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
         const int rk = fast2 ? sqrt_factor(c, 0, ld * ld, n, ld2, offcs2, offred2, bp)
                              : sqrt_factor_glb(c, M2, V2, n, ld2, offcs2, bp);
         const double* yv = cs + 2 * n + 1;
+        pw |= fast2 ? VG_MARGPATH_S2_SQRT : VG_MARGPATH_S2_SQRT_GLB;
         if (c.tid == 0) mi[5] = rk << 16;        // rank of the factor (the eigen path reports sweeps | attempts << 8 here)
         MPROF(6);
         for (int k = c.tid; k < n * n; k += MG_NT) {
@@ -2022,6 +2041,7 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
 #else
     (void)sw2;
 #endif
+    pw |= fast2_eig ? VG_MARGPATH_S2_VH_EIG : n_lds ? VG_MARGPATH_S2_JACOBI_LDS : VG_MARGPATH_S2_JACOBI_GLB;
     if (c.tid == 0) mi[5] = sw2;            // sweeps | Cholesky attempts << 8 of the kept-block eigen-decomposition
     MPROF(6);
     // ascending order like SelfAdjointEigenSolver: rank of each eigenvalue
@@ -2079,6 +2099,8 @@ extern "C" __global__ __launch_bounds__(MG_NT) void ba_marg_kernel(const BaLayou
         mi[0] = 1; mi[1] = n; mi[2] = m; mi[3] = nb;
 #ifdef BA_PROFILE
         mi[7] = (int)((clock64() - _tstart) >> 10);
+#else
+        mi[6] = pw;                         // the path word (BA_PROFILE builds keep their cycle stamp there)
 #endif
     }
 }

@@ -102,6 +102,7 @@ struct BaBatch {
     int rounds = 0;                  // launches of the linearise / accumulate / solve triple = max over windows of max_iters
     bool uploaded = false, any_margin = false;
     bool solved_recorded = false;    // ev_fork recorded behind ba_final_kernel of the current run
+    bool marg_info_ready = false;    // h_miout holds the marginalization words of the current run (vg_ba_batch_marg_info)
     bool force_large = false;        // vg_ba_set_large_window: take the large-window path whatever the size
     int marg_mode = 0;               // vg_ba_set_marg_mode: VG_MARG_SQRT (default) / VG_MARG_EIGEN
     int imu_info_mode = 0;           // vg_ba_set_imu_info_mode: VG_IMU_INFO_FACTOR (default) / VG_IMU_INFO_REFERENCE
