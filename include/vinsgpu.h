@@ -977,7 +977,9 @@ int vg_ba_reduce_layout(vg_handle* h, size_t* count_system, size_t* count_norms)
  *   proj_r  [F x 2], proj_J [F x 2 x 20] columns = [pose_i(6) pose_j(6) ex(6) lambda(1) td(1)]
  *   imu_r   [(K-1) x 15], imu_J [(K-1) x 15 x 30] columns = [pose_i(6) sb_i(9) pose_j(6) sb_j(9)]
  *   prior_r [prior_n]
- * F = sum(lm_nobs - 1) + relo_n.  Any output pointer may be NULL. */
+ * F = sum(lm_nobs - 1) + relo_n, landmark by landmark; a landmark's relocalisation factor follows its
+ * window factors.  Any output pointer may be NULL.  The rows of an IMU factor the solve leaves out
+ * (valid == 0 or sum_dt > 10) are zero. */
 int vg_ba_eval_factors(vg_handle* h, const vg_ba_problem* in, double* proj_r, double* proj_J,
                        double* imu_r, double* imu_J, double* prior_r);
 

@@ -1072,7 +1072,9 @@ extern "C" int vg_ba_eval_factors(vg_handle* h, const vg_ba_problem* in, double*
     HIPCHK(h, hipMalloc((void**)&d, tot * sizeof(double)));
     double* d_pr = d; double* d_pJ = d_pr + (size_t)F * 2; double* d_ir = d_pJ + (size_t)F * 40;
     double* d_iJ = d_ir + nimu * 15; double* d_qr = d_iJ + nimu * 450;
-    hipError_t e = ba_launch_eval_factors(L, B.dL, B.P, d_pr, d_pJ, d_ir, d_iJ, d_qr, h->stream);
+    // an IMU factor the kernel skips (vg_imu_preint::valid == 0 or sum_dt > 10) writes nothing: its rows of imu_r / imu_J are zero
+    hipError_t e = hipMemsetAsync(d, 0, tot * sizeof(double), h->stream);
+    if (e == hipSuccess) e = ba_launch_eval_factors(L, B.dL, B.P, d_pr, d_pJ, d_ir, d_iJ, d_qr, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && proj_r) e = hipMemcpy(proj_r, d_pr, (size_t)F * 2 * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess && proj_J) e = hipMemcpy(proj_J, d_pJ, (size_t)F * 40 * 8, hipMemcpyDeviceToHost);
