@@ -33,7 +33,7 @@ extern "C" {
                              * vg_fe_tracks_begin / _step / _get / _set; vg_ba_seq_imu_begin / _get / _set / _timing / _times, vg_ba_seq_step_imu_async;
                              * vg_vio_begin / _step_async / _get_frame / _end; vg_init_align; vg_init_sfm; vg_init_relpose; vg_init_exrot;
                              * vg_kf_configure / _add / _get / _set / _match; vg_kf_pnp, vg_kf_pnp_defaults; vg_voc_load, vg_bow_configure / _reset / _count / _get,
-                             * vg_kf_loop_detect; vg_pg_optimize, vg_pg_defaults; vg_ba_batch_marg_info) */
+                             * vg_kf_loop_detect; vg_pg_optimize, vg_pg_defaults; vg_ba_batch_marg_info; vg_ba_seq_outputs_reserve / _async, vg_ba_seq_get_outputs) */
 #define VG_MAX_ITERS 32          /* capacity of the per-iteration trace in vg_ba_summary */
 
 typedef enum {
@@ -929,6 +929,59 @@ typedef struct vg_ba_relo_result {
 int vg_ba_seq_relo_reserve(vg_handle* h, int max_match);
 int vg_ba_seq_set_relo(vg_handle* h, int window, const vg_ba_relo_frame* r);
 int vg_ba_seq_get_relo(vg_handle* h, int window, vg_ba_relo_result* out);
+
+/* ---- What the estimator publishes between two frames: keyframe message and point clouds (added within ABI 12, nothing existing changed) ---
+ * After every frame the estimator node (estimator_node.cpp:321-328) calls pubKeyframe (vins_estimator/src/utility/visualization.cpp:
+ * 348-404) and pubPointCloud (:240-296); the pose graph builds its KeyFrame from the first.  A sequence forms both on the device
+ * (ba_seq_publish_kernel, csrc/ba_seq.hip) from the CURRENT track table and the window's states as they stand between two frames --
+ * after slideWindow() and removeFailures(), i.e. what vg_ba_seq_get_tracks and vg_ba_seq_export return -- and changes nothing resident.
+ * With W = WINDOW_SIZE = K - 1, per window, every list in track-list order:
+ *   keyframe list   tracks with start_frame < W - 2 && start_frame + n_obs - 1 >= W - 2 && solve_flag == 1 (:378): the world point,
+ *                   the observation in frame W - 2 (row W - 2 - start_frame of the track: normalised x y, pixel u v) and the feature id.
+ *                   The reference sends the id through a float channel (:397); here it stays the int it is: the two agree below 2^24.
+ *   point cloud     n_obs >= 2 && start_frame < W - 2 && !(start_frame > W * 3.0 / 4.0) && solve_flag == 1 (:251-254): the world point
+ *   margin cloud    n_obs >= 2 && start_frame < W - 2 && start_frame == 0 && n_obs <= 2 && solve_flag == 1 (:276-282): the world point
+ *   world point     Rs[s] (ric (point0 estimated_depth) + tic) + Ps[s], s = start_frame, point0 = the first observation (x, y, z);
+ *                   Rs / ric are the matrices of the normalised state quaternions.  Formed in double, rounded to float once, by the
+ *                   store (geometry_msgs::Point32, ChannelFloat32; KeyFrame takes cv::Point3f / cv::Point2f).
+ *   pose            of frame W - 2 (px py pz qx qy qz qw) and ex_pose (tic, ric), the resident doubles as they are.
+ *   keyframe_valid  1 iff the last step of the sequence chose VG_MARGIN_OLD for this window (info[VG_SEQ_FLAG]): the
+ *                   marginalization_flag == 0 gate of :351.  0 before the first step.  The keyframe list is formed either way; the flag
+ *                   says whether the reference would publish it.  The caller owns the stamps (Headers[W - 2]): a sequence keeps none.
+ *   status          VG_OK; the status of the window's last step when that step was void (info[VG_SEQ_STATUS] != VG_OK): the three
+ *                   counts are 0 then; VG_SEQ_OUT_TRUNCATED when a list selects more tracks than max_points: the first max_points
+ *                   of that list are stored, in list order, and n_* still report the true counts.
+ *   vg_ba_seq_outputs_reserve  any time a sequence is live, 1 <= max_points <= 1024 (the kernels' track capacity): the device block
+ *                              and the pinned staging for max_points rows per list and window.  Again: replaces the reservation
+ *                              (what an earlier _async produced is gone).  The call WAITS for the handle's stream (a step
+ *                              enqueued before it finishes first): reserve once, outside the frame loop.  vg_ba_seq_end frees it;
+ *                              vg_ba_seq_begin starts without one.
+ *   vg_ba_seq_outputs_async    enqueues the kernel and ONE download (headers + packed lists of every window) on the handle's stream,
+ *                              behind whatever step was enqueued last; works after vg_ba_seq_step_async, vg_ba_seq_step_imu_async and
+ *                              vg_vio_step_async alike, and right after vg_ba_seq_begin / vg_ba_seq_import.  On demand: no step
+ *                              launches it, and the step's launches, downloads and results are what they were.
+ *   vg_ba_seq_get_outputs      waits for the last _async (not for anything enqueued behind it) and copies one window: the scalars
+ *                              always, each array that is not NULL for min(n_*, max_points) rows.  Arrays must hold max_points rows.
+ * VG_ERR_BAD_ARG with a vg_last_error text and nothing moved: any of the three without a live sequence; _async or _get without a
+ * reservation; _get before any _async since the reservation; a window out of range; a wrong struct_size; max_points out of range. */
+#define VG_SEQ_OUT_TRUNCATED 1
+typedef struct vg_ba_seq_outputs {
+    int struct_size;             /* sizeof(vg_ba_seq_outputs), set by the caller                                              */
+    int status;                  /* VG_OK / the void step's status / VG_SEQ_OUT_TRUNCATED                                     */
+    int keyframe_valid;
+    int n_keyframe, n_cloud, n_margin;   /* true counts (may exceed max_points: status says so)                               */
+    double pose[7];              /* frame W - 2: px py pz qx qy qz qw                                                         */
+    double ex_pose[7];           /* tic, ric (x y z w)                                                                        */
+    float* kf_point_3d;          /* [max_points][3]   every array may be NULL                                                 */
+    float* kf_norm;              /* [max_points][2]   normalised x y in frame W - 2                                           */
+    float* kf_uv;                /* [max_points][2]   pixel u v in frame W - 2                                                */
+    int* kf_id;                  /* [max_points]                                                                              */
+    float* cloud_xyz;            /* [max_points][3]                                                                           */
+    float* margin_xyz;           /* [max_points][3]                                                                           */
+} vg_ba_seq_outputs;
+int vg_ba_seq_outputs_reserve(vg_handle* h, int max_points);
+int vg_ba_seq_outputs_async(vg_handle* h);
+int vg_ba_seq_get_outputs(vg_handle* h, int window, vg_ba_seq_outputs* out);
 
 /* Form of the prior factor the marginalization hands back (marginalization_factor.cpp:285-296 builds J0 = S^1/2 V^T,
  * r0 = S^-1/2 V^T b' from the eigen-decomposition A' = V S V^T of the kept system).  Everything downstream uses the factor

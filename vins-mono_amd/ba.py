@@ -96,6 +96,16 @@ class ReloResult(C.Structure):        # vg_ba_relo_result
                 ("drift_correct_r", C.c_double * 9), ("drift_correct_t", C.c_double * 3)]
 
 
+_pf = C.POINTER(C.c_float)
+VG_SEQ_OUT_TRUNCATED = 1
+
+
+class SeqOutputs(C.Structure):        # vg_ba_seq_outputs
+    _fields_ = [("struct_size", C.c_int), ("status", C.c_int), ("keyframe_valid", C.c_int), ("n_keyframe", C.c_int), ("n_cloud", C.c_int),
+                ("n_margin", C.c_int), ("pose", C.c_double * 7), ("ex_pose", C.c_double * 7), ("kf_point_3d", _pf), ("kf_norm", _pf),
+                ("kf_uv", _pf), ("kf_id", _pi), ("cloud_xyz", _pf), ("margin_xyz", _pf)]
+
+
 VG_ALIGN_OK, VG_ALIGN_FAILED_LINEAR, VG_ALIGN_FAILED_REFINE, VG_ALIGN_NUMERIC = 0, 1, 2, 3
 VG_ALIGN_MAX_FRAMES = 32
 
@@ -383,6 +393,10 @@ class Handle:
             L.vg_ba_seq_relo_reserve.argtypes = [C.c_void_p, C.c_int]
             L.vg_ba_seq_set_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloFrame)]
             L.vg_ba_seq_get_relo.argtypes = [C.c_void_p, C.c_int, C.POINTER(ReloResult)]
+        if hasattr(L, "vg_ba_seq_outputs_async"):         # (added within ABI 12)
+            L.vg_ba_seq_outputs_reserve.argtypes = [C.c_void_p, C.c_int]
+            L.vg_ba_seq_outputs_async.argtypes = [C.c_void_p]
+            L.vg_ba_seq_get_outputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(SeqOutputs)]
         if hasattr(L, "vg_init_align"):                   # (added within ABI 12)
             L.vg_init_align.argtypes = [C.c_void_p, C.c_int, C.POINTER(AlignIn), C.POINTER(AlignOut)]
         if hasattr(L, "vg_init_sfm"):                     # (added within ABI 12)
@@ -843,8 +857,36 @@ class Handle:
                     relative_t=np.array(o.relo_relative_t[:]), relative_q=np.array(o.relo_relative_q[:]), relative_yaw=float(o.relo_relative_yaw),
                     drift_r=np.array(o.drift_correct_r[:]).reshape(3, 3), drift_t=np.array(o.drift_correct_t[:]))
 
+    # ---- keyframe message and point clouds of a resident sequence (include/vinsgpu.h vg_ba_seq_outputs_*)
+    def seq_outputs_reserve(self, max_points):
+        """Any time a sequence is live: room for max_points (1 .. 1024) rows per list and window; again: replaces."""
+        self._chk(self.lib.vg_ba_seq_outputs_reserve(self.h, int(max_points)), "vg_ba_seq_outputs_reserve")
+        self._out_mp = int(max_points)
+
+    def seq_outputs_async(self):
+        """Enqueue ba_seq_publish_kernel and the one download of every window's header and lists (vg_ba_seq_outputs_async)."""
+        self._chk(self.lib.vg_ba_seq_outputs_async(self.h), "vg_ba_seq_outputs_async")
+
+    def seq_outputs(self, window, struct_size=None):
+        """What the last seq_outputs_async produced for one window: dict(status, keyframe_valid, n_keyframe, n_cloud, n_margin (true
+        counts), pose (7,), ex_pose (7,), kf_point_3d (n, 3), kf_norm (n, 2), kf_uv (n, 2) float32, kf_id (n,) int32, cloud_xyz (n, 3),
+        margin_xyz (n, 3) float32), the arrays cut to the stored counts min(n_*, max_points)."""
+        mp = max(1, getattr(self, "_out_mp", 0))
+        p3, nm, uv = np.zeros((mp, 3), np.float32), np.zeros((mp, 2), np.float32), np.zeros((mp, 2), np.float32)
+        ids, pc, mg = np.zeros(mp, np.int32), np.zeros((mp, 3), np.float32), np.zeros((mp, 3), np.float32)
+        fp = lambda a: a.ctypes.data_as(_pf)
+        o = SeqOutputs()
+        o.struct_size = C.sizeof(SeqOutputs) if struct_size is None else int(struct_size)
+        o.kf_point_3d, o.kf_norm, o.kf_uv, o.kf_id, o.cloud_xyz, o.margin_xyz = fp(p3), fp(nm), fp(uv), _ip(ids), fp(pc), fp(mg)
+        self._chk(self.lib.vg_ba_seq_get_outputs(self.h, int(window), C.byref(o)), "vg_ba_seq_get_outputs")
+        nk, nc, nmg = (min(int(v), mp) for v in (o.n_keyframe, o.n_cloud, o.n_margin))
+        return dict(status=int(o.status), keyframe_valid=int(o.keyframe_valid), n_keyframe=int(o.n_keyframe), n_cloud=int(o.n_cloud),
+                    n_margin=int(o.n_margin), pose=np.array(o.pose[:]), ex_pose=np.array(o.ex_pose[:]), kf_point_3d=p3[:nk].copy(),
+                    kf_norm=nm[:nk].copy(), kf_uv=uv[:nk].copy(), kf_id=ids[:nk].copy(), cloud_xyz=pc[:nc].copy(), margin_xyz=mg[:nmg].copy())
+
     def seq_end(self):
         self._chk(self.lib.vg_ba_seq_end(self.h), "vg_ba_seq_end")
+        self._out_mp = 0
 
     # ---- the front end feeds the sequence on the device, one call per frame (include/vinsgpu.h vg_vio_*)
     def vio_begin(self, lists=False):

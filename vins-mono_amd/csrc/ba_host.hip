@@ -1124,6 +1124,11 @@ static void seq_free(BaSeq& Q) {
     Q.vio = Q.vio_staged = false; Q.vio_flags = 0;
     for (hipEvent_t& ev : Q.ev_imu) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
     Q.imu_timing = Q.imu_timed = false;
+    (void)hipFree(Q.out_d); Q.out_d = nullptr;
+    Q.h_out.release();
+    if (Q.ev_out) (void)hipEventDestroy(Q.ev_out);
+    Q.ev_out = nullptr;
+    Q.out_mp = 0; Q.out_pending = false; Q.stepped = false;
     Q.active = false;
 }
 extern "C" void ba_seq_release(vg_handle* h) { seq_free(h->ba.seq); }
@@ -1403,6 +1408,7 @@ static int seq_launch_step(vg_handle* h, const SeqDev& D, const SeqBridge* bridg
     if (e != hipSuccess) { h->err = std::string("launch of the sequence slide kernels: ") + hipGetErrorString(e); return VG_ERR_HIP; }
     Q.imu_timed = timed;
     Q.cur ^= 1;
+    Q.stepped = true;
     B.mout_pending = false;                                      // (carried already; the slots' host mirror is not maintained in a sequence)
     return VG_OK;
 }
@@ -1751,6 +1757,87 @@ extern "C" int vg_ba_seq_get_relo(vg_handle* h, int window, vg_ba_relo_result* o
     }
     relo_R2q(rel, out->relo_relative_q);
     out->relo_relative_yaw = relo_normalize_angle(ypr_f[0] - ypr_relo[0]);
+    return VG_OK;
+}
+
+// ---- keyframe message and point clouds (include/vinsgpu.h vg_ba_seq_outputs_*; ba_seq_publish_kernel) --------------------------------
+extern "C" int ba_seq_out_stride(int max_points);
+extern "C" int ba_seq_out_hdr_words();
+extern "C" hipError_t ba_seq_launch_publish(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int cur, int stepped, int* out,
+                                            int max_points, hipStream_t stream);
+
+extern "C" int vg_ba_seq_outputs_reserve(vg_handle* h, int max_points) {
+    if (!h) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_ba_seq_outputs_reserve: ") + why; return VG_ERR_BAD_ARG; };
+    if (!Q.active || !h->ba.uploaded) return refuse("no running sequence (vg_ba_seq_begin)");
+    int ft_max = 0;
+    (void)ba_seq_limits(&ft_max, nullptr, nullptr, nullptr);
+    if (max_points < 1 || max_points > ft_max) return refuse(("max_points outside 1 .. " + std::to_string(ft_max)).c_str());
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                  // (an earlier download into the staging has landed)
+    const size_t words = (size_t)Q.nwin * ba_seq_out_stride(max_points);
+    int* d = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d, words * sizeof(int)));
+    if (Q.h_out.resize(words) != hipSuccess || (!Q.ev_out && hipEventCreateWithFlags(&Q.ev_out, hipEventDisableTiming) != hipSuccess)) {
+        (void)hipFree(d);
+        h->err = "vg_ba_seq_outputs_reserve: out of pinned memory or events";
+        return VG_ERR_HIP;
+    }
+    (void)hipFree(Q.out_d);
+    Q.out_d = d; Q.out_mp = max_points; Q.out_pending = false;
+    HIPCHK(h, hipMemsetAsync(Q.out_d, 0, words * sizeof(int), h->stream));
+    return VG_OK;
+}
+
+extern "C" int vg_ba_seq_outputs_async(vg_handle* h) {
+    VG_RANGE("vg_ba_seq_outputs_async");
+    if (!h) return VG_ERR_BAD_ARG;
+    BaBatch& B = h->ba;
+    BaSeq& Q = B.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_ba_seq_outputs_async: ") + why; return VG_ERR_BAD_ARG; };
+    if (!Q.active || !B.uploaded) return refuse("no running sequence (vg_ba_seq_begin)");
+    if (!Q.out_mp) return refuse("no reservation (vg_ba_seq_outputs_reserve)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const hipError_t e = ba_seq_launch_publish(B.L, B.dL, B.P, Q.D, Q.cur, Q.stepped ? 1 : 0, Q.out_d, Q.out_mp, h->stream);
+    if (e != hipSuccess) { h->err = std::string("launch of the sequence publish kernel: ") + hipGetErrorString(e); return VG_ERR_HIP; }
+    HIPCHK(h, hipMemcpyAsync(Q.h_out.data(), Q.out_d, Q.h_out.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipEventRecord(Q.ev_out, h->stream));
+    Q.out_pending = true;
+    return VG_OK;
+}
+
+extern "C" int vg_ba_seq_get_outputs(vg_handle* h, int window, vg_ba_seq_outputs* out) {
+    if (!h) return VG_ERR_BAD_ARG;
+    BaSeq& Q = h->ba.seq;
+    auto refuse = [&](const char* why) { h->err = std::string("vg_ba_seq_get_outputs: ") + why; return VG_ERR_BAD_ARG; };
+    if (!out) return refuse("out is NULL");
+    if (!Q.active) return refuse("no running sequence (vg_ba_seq_begin)");
+    if (!Q.out_mp) return refuse("no reservation (vg_ba_seq_outputs_reserve)");
+    if (!Q.out_pending) return refuse("no vg_ba_seq_outputs_async since the reservation");
+    if (window < 0 || window >= Q.nwin) return refuse("no such window");
+    if (out->struct_size != (int)sizeof(vg_ba_seq_outputs)) return refuse("vg_ba_seq_outputs::struct_size is not sizeof(vg_ba_seq_outputs)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipEventSynchronize(Q.ev_out));
+    const int MP = Q.out_mp;
+    const int* o = Q.h_out.data() + (size_t)window * ba_seq_out_stride(MP);
+    out->status = o[0]; out->keyframe_valid = o[1]; out->n_keyframe = o[2]; out->n_cloud = o[3]; out->n_margin = o[4];
+    memcpy(out->pose, o + 8, 7 * sizeof(double));
+    memcpy(out->ex_pose, o + 8 + 14, 7 * sizeof(double));
+    if (o[2] < 0 || o[3] < 0 || o[4] < 0) { h->err = "vg_ba_seq_get_outputs: inconsistent count from the device"; return VG_ERR_NUMERIC; }
+    const int nk = std::min(o[2], MP), nc = std::min(o[3], MP), nm = std::min(o[4], MP);
+    const int* kf = o + ba_seq_out_hdr_words();
+    const int* pc = kf + (size_t)8 * MP;
+    const int* mg = pc + (size_t)3 * MP;
+    for (int k = 0; k < nk; ++k) {                               // rows: w (3) | x y u v | id
+        const int* r = kf + (size_t)8 * k;
+        if (out->kf_point_3d) memcpy(out->kf_point_3d + 3 * (size_t)k, r, 12);
+        if (out->kf_norm) memcpy(out->kf_norm + 2 * (size_t)k, r + 3, 8);
+        if (out->kf_uv) memcpy(out->kf_uv + 2 * (size_t)k, r + 5, 8);
+        if (out->kf_id) out->kf_id[k] = r[7];
+    }
+    if (out->cloud_xyz && nc) memcpy(out->cloud_xyz, pc, (size_t)nc * 12);
+    if (out->margin_xyz && nm) memcpy(out->margin_xyz, mg, (size_t)nm * 12);
     return VG_OK;
 }
 

@@ -706,6 +706,121 @@ extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_bridge_kernel(SeqDev
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// vg_ba_seq_outputs_async: what the estimator node publishes between two frames (estimator_node.cpp:321-328), from the window as it
+// stands in HBM.  pubKeyframe (vins_estimator/src/utility/visualization.cpp:348-404): the pose of frame WINDOW_SIZE - 2 and, for every
+// solved track seen in that frame, its world point, the observation in that frame and the id; pubPointCloud (:240-296): the world
+// points of the solved landmarks and the margin cloud.  One workgroup per window.  Reads the CURRENT track table (the one the last slide
+// wrote, or vg_ba_seq_begin / vg_ba_seq_import filled) and the states of the input slab (after slideWindow() and removeFailures());
+// writes only the window's block of `out`: nothing resident changes.
+//   keyframe list   start < W - 2 && start + n_obs - 1 >= W - 2 && solve_flag == 1                              (:378)
+//   point cloud     n_obs >= 2 && start < W - 2 && !(start > W * 3.0 / 4.0) && solve_flag == 1                  (:251-254)
+//                   (the 3/4 test is vacuous for every K a sequence accepts: start <= W - 3 <= 0.75 W whenever W <= 12; it is evaluated
+//                    all the same, as the reference writes it)
+//   margin cloud    n_obs >= 2 && start < W - 2 && start == 0 && n_obs <= 2 && solve_flag == 1                  (:276-282)
+// each in track-list order (seq_compact).  World point, in FP64, rounded to float32 only by the store (the messages carry Point32):
+//   w = Rs[s] (ric (point0 depth) + tic) + Ps[s],  s = start_frame, point0 = first observation (x, y, z),
+// Rs / ric the matrices of the normalised quaternions, as ba_seq_tri_kernel takes them.
+// The window's block, in 4-byte words (vg_ba_seq_get_outputs unpacks it):
+//   [0] status  [1] keyframe_valid  [2] n_keyframe  [3] n_cloud  [4] n_margin (true counts)  [5 .. 7] 0
+//   [8 .. 36)   14 doubles: pose of frame W - 2 (px py pz qx qy qz qw), ex_pose (tic, ric as stored)
+//   [36 ..)     keyframe rows, 8 words each: w (3 float) | x y u v of the observation in frame W - 2 (4 float) | id (int)
+//   then        cloud rows, then margin rows, 3 floats each; every list has room for MP rows
+// More selected tracks than MP: the first MP of the list are stored, the count stays the true one, status = VG_SEQ_OUT_TRUNCATED.
+// A window whose last step was void reports that step's status and three zero counts.  stepped = 0 (no step since vg_ba_seq_begin):
+// the info words are not a step's, keyframe_valid = 0 and the status starts from VG_OK.
+#define SEQ_OUT_HDR 36
+extern "C" __global__ __launch_bounds__(SEQ_NT) void ba_seq_publish_kernel(const BaLayout* __restrict__ Lp, BaPtrs P, SeqDev S, int cur, int stepped,
+                                                                          int* __restrict__ out, int MP, int ostride) {
+    __shared__ int s_kf[SEQ_FT_MAX], s_pc[SEQ_FT_MAX], s_mg[SEQ_FT_MAX];
+    __shared__ double s_R[9 * BA_MAX_K], s_P[3 * BA_MAX_K], s_ex[12];       // Rs, Ps; ric (9) tic (3)
+    __shared__ int s_cnt[3];
+    const BaLayout& L = *Lp;
+    const int w = blockIdx.x, tid = threadIdx.x, K = S.K, WS = K - 1;
+    SeqTab T = seq_table(S, cur, w);
+    const double* di = P.din + (size_t)w * L.dstride;
+    const int* info = S.info + (size_t)w * VG_SEQ_INFO_INTS;
+    int* o = out + (size_t)w * ostride;
+    const int step_status = stepped ? info[VG_SEQ_STATUS] : VG_OK;
+    const int n = step_status == VG_OK ? T.hdr[0] : 0;
+    if (tid < K) {
+        const double* x = di + L.do_pose + 7 * tid;
+        double q[4] = {x[3], x[4], x[5], x[6]};
+        q_normalize(q);
+        q_to_R(q, s_R + 9 * tid);
+        s_P[3 * tid] = x[0]; s_P[3 * tid + 1] = x[1]; s_P[3 * tid + 2] = x[2];
+    } else if (tid == K) {                                                 // (the thread behind the K that take the poses)
+        const double* ex = di + L.do_ex;
+        double q[4] = {ex[3], ex[4], ex[5], ex[6]};
+        q_normalize(q);
+        q_to_R(q, s_ex);
+        s_ex[9] = ex[0]; s_ex[10] = ex[1]; s_ex[11] = ex[2];
+    }
+    for (int f = tid; f < n; f += SEQ_NT) {
+        const int st = T.start[f], no = T.nobs[f];
+        const int solved = T.sflag[f] == 1;
+        const int in_problem = no >= 2 && st < WS - 2;
+        s_kf[f] = (st < WS - 2 && st + no - 1 >= WS - 2 && solved) ? 1 : 0;
+        s_pc[f] = (in_problem && !((double)st > WS * 3.0 / 4.0) && solved) ? 1 : 0;
+        s_mg[f] = (in_problem && st == 0 && no <= 2 && solved) ? 1 : 0;
+    }
+    __syncthreads();
+    {
+        const int c0 = seq_compact(s_kf, s_kf, n, tid);                    // (in place: an entry is read and written by the same lane)
+        const int c1 = seq_compact(s_pc, s_pc, n, tid);
+        const int c2 = seq_compact(s_mg, s_mg, n, tid);
+        if (tid == 0) { s_cnt[0] = c0; s_cnt[1] = c1; s_cnt[2] = c2; }
+    }
+    __syncthreads();
+    // ---- the header
+    if (tid == 0) {
+        int status = step_status;
+        if (s_cnt[0] > MP || s_cnt[1] > MP || s_cnt[2] > MP) status = VG_SEQ_OUT_TRUNCATED;
+        o[0] = status;
+        o[1] = (stepped && info[VG_SEQ_FLAG] == VG_MARGIN_OLD) ? 1 : 0;   // marginalization_flag == 0 (:351)
+        o[2] = s_cnt[0]; o[3] = s_cnt[1]; o[4] = s_cnt[2]; o[5] = 0; o[6] = 0; o[7] = 0;
+    }
+    double* od = (double*)(o + 8);
+    if (tid < 7) od[tid] = di[L.do_pose + 7 * (WS - 2) + tid];
+    else if (tid < 14) od[tid] = di[L.do_ex + (tid - 7)];
+    // ---- the rows
+    float* kf = (float*)(o + SEQ_OUT_HDR);
+    float* pc = kf + (size_t)8 * MP;
+    float* mg = pc + (size_t)3 * MP;
+    for (int f = tid; f < n; f += SEQ_NT) {
+        const int dk = s_kf[f], dp = s_pc[f], dm = s_mg[f];
+        const bool k_on = dk >= 0 && dk < MP, p_on = dp >= 0 && dp < MP, m_on = dm >= 0 && dm < MP;
+        if (!(k_on || p_on || m_on)) continue;
+        const int st = T.start[f];
+        const double dep = T.depth[f];
+        const double* r0 = T.obs + (size_t)f * K * 8;                      // [x y u v vx vy cur_td z]
+        const double px = r0[0] * dep, py = r0[1] * dep, pz = r0[7] * dep;
+        const double cx = s_ex[0] * px + s_ex[1] * py + s_ex[2] * pz + s_ex[9];
+        const double cy = s_ex[3] * px + s_ex[4] * py + s_ex[5] * pz + s_ex[10];
+        const double cz = s_ex[6] * px + s_ex[7] * py + s_ex[8] * pz + s_ex[11];
+        const double* R = s_R + 9 * st;
+        const float wx = (float)(R[0] * cx + R[1] * cy + R[2] * cz + s_P[3 * st]);
+        const float wy = (float)(R[3] * cx + R[4] * cy + R[5] * cz + s_P[3 * st + 1]);
+        const float wz = (float)(R[6] * cx + R[7] * cy + R[8] * cz + s_P[3 * st + 2]);
+        if (k_on) {
+            const double* rj = r0 + (size_t)(WS - 2 - st) * 8;
+            float* d = kf + (size_t)8 * dk;
+            d[0] = wx; d[1] = wy; d[2] = wz;
+            d[3] = (float)rj[0]; d[4] = (float)rj[1]; d[5] = (float)rj[2]; d[6] = (float)rj[3];
+            ((int*)d)[7] = T.id[f];
+        }
+        if (p_on) { float* d = pc + (size_t)3 * dp; d[0] = wx; d[1] = wy; d[2] = wz; }
+        if (m_on) { float* d = mg + (size_t)3 * dm; d[0] = wx; d[1] = wy; d[2] = wz; }
+    }
+}
+extern "C" int ba_seq_out_stride(int max_points) { return (SEQ_OUT_HDR + 14 * max_points + 3) / 4 * 4; }     // words per window, a multiple of 16 bytes
+extern "C" int ba_seq_out_hdr_words() { return SEQ_OUT_HDR; }
+extern "C" hipError_t ba_seq_launch_publish(const BaLayout& L, const BaLayout* dL, const BaPtrs& P, const SeqDev& S, int cur, int stepped, int* out,
+                                            int max_points, hipStream_t stream) {
+    hipLaunchKernelGGL(ba_seq_publish_kernel, dim3(L.nwin), dim3(SEQ_NT), 0, stream, dL, P, S, cur, stepped, out, max_points, ba_seq_out_stride(max_points));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 extern "C" hipError_t ba_seq_launch_bridge(const BaLayout& L, const SeqDev& S, const int* tk_hdr, const int* msg_id, const double* msg_obs, int cap,
                                            const double* smp, int smp_stride, hipStream_t stream) {
     hipLaunchKernelGGL(ba_seq_bridge_kernel, dim3(L.nwin), dim3(SEQ_NT), 0, stream, S, tk_hdr, msg_id, msg_obs, cap, smp, smp_stride);

@@ -82,6 +82,13 @@ struct BaSeq {
     PinnedBuf<int> h_relo_i;
     PinnedBuf<double> h_relo_d;
     bool relo_staged = false;        // h_relo_i / h_relo_d hold this step's matches: they go up with the staging
+    // ---- keyframe message and point clouds (vg_ba_seq_outputs_*): ba_seq_publish_kernel writes out_d, one copy brings it to h_out
+    int out_mp = 0;                  // vg_ba_seq_outputs_reserve: rows per list and window (0: no reservation)
+    int* out_d = nullptr;            // [nwin][ba_seq_out_stride(out_mp)] 4-byte words
+    PinnedBuf<int> h_out;
+    hipEvent_t ev_out = nullptr;     // behind the download of the last vg_ba_seq_outputs_async
+    bool out_pending = false;        // an _async has been enqueued since the reservation
+    bool stepped = false;            // a step has run since vg_ba_seq_begin (info[] holds a step's record)
 };
 
 struct BaBatch {

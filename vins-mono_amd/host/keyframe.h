@@ -168,7 +168,7 @@ class KeyFrame {
     std::vector<BRIEF::bitset> brief_descriptors, window_brief_descriptors;
     vg_fe_camera camera = {};
     int slot;
-    std::vector<cv::Point3f> point_3d;  // per window point, like point_2d_uv
+    std::vector<cv::Point3f> point_3d;  // per window point, like point_2d_uv (from a resident sequence: vg_unpack_keyframe, host/vg_pack.h)
     std::vector<double> point_id;
     Eigen::Vector3d vio_T_w_i, T_w_i, origin_vio_T, tic;
     Eigen::Matrix3d vio_R_w_i, R_w_i, origin_vio_R, qic;          // (tic / qic: the reference's globals, per keyframe here)

@@ -733,6 +733,15 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
         fclose(rf);
         resp->useRelocalisation(max_match);
     }
+    // VINS_REPLAY_OUTPUTS=<max_points>: what the estimator node publishes after every frame (ResidentEstimators::usePublishedOutputs:
+    // pubKeyframe / pubPointCloud formed on the device) goes to <out>.outputs, per frame and estimator:
+    //   "F,frame,estimator,keyframe_valid,status,n_keyframe,n_cloud,n_margin,stamp of frame WINDOW_SIZE - 2"
+    //   "P,vio_T_w_i (3),vio_R_w_i (9, row-major)"       17 digits
+    //   "k,id,point_3d (3),uv (2),norm (2)"              per stored keyframe row; floats with 9 digits (they are float32)
+    //   "c,x,y,z" per point of the cloud, "m,x,y,z" per point of the margin cloud
+    const char* po_env = getenv("VINS_REPLAY_OUTPUTS");
+    const int pub_points = po_env ? atoi(po_env) : 0;
+    if (pub_points) resp->usePublishedOutputs(pub_points);
     std::vector<std::vector<double>> stamps0(N);
     for (int i = 0; i < N; ++i) {
         // the estimator as the reference's code would hold it between two frames, then handed over
@@ -795,6 +804,7 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
     }
     resp->begin();
     FILE* orelo = relo.empty() ? nullptr : fopen((std::string(out) + ".relo").c_str(), "w");
+    FILE* opub = pub_points ? fopen((std::string(out) + ".outputs").c_str(), "w") : nullptr;
     // VINS_REPLAY_KERNEL_TIMES=1 (with the IMU on the device): per frame "K,<frame>,<ms in ba_seq_imu_kernel>,<ms in ba_seq_merge_kernel>"
     // on stderr, from HIP events; asking for them waits for the merge, so such a run is not one to take host times from
     const bool kernel_times = device_imu && getenv("VINS_REPLAY_KERNEL_TIMES") != nullptr;
@@ -860,9 +870,24 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
             for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) fprintf(orelo, ",%.12g", e.drift_correct_r(a, b));
             fprintf(orelo, ",%.12g,%.12g,%.12g\n", e.drift_correct_t.x(), e.drift_correct_t.y(), e.drift_correct_t.z());
         }
+        for (int i = 0; i < N && opub; ++i) {
+            const ResidentEstimators::Keyframe& kf = resp->keyframe(i);
+            const ResidentEstimators::Cloud& pc = resp->pointCloud(i);
+            const ResidentEstimators::Cloud& mg = resp->marginCloud(i);
+            fprintf(opub, "F,%d,%d,%d,%d,%d,%d,%d,%.17g\n", w, i, kf.valid ? 1 : 0, kf.status, kf.count, pc.count, mg.count, kf.stamp);
+            fprintf(opub, "P,%.17g,%.17g,%.17g", kf.vio_T_w_i.x(), kf.vio_T_w_i.y(), kf.vio_T_w_i.z());
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) fprintf(opub, ",%.17g", kf.vio_R_w_i(a, b));
+            fprintf(opub, "\n");
+            for (size_t k = 0; k < kf.point_id.size(); ++k)
+                fprintf(opub, "k,%d,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g\n", (int)kf.point_id[k], kf.point_3d[3 * k], kf.point_3d[3 * k + 1], kf.point_3d[3 * k + 2],
+                        kf.point_2d_uv[2 * k], kf.point_2d_uv[2 * k + 1], kf.point_2d_norm[2 * k], kf.point_2d_norm[2 * k + 1]);
+            for (size_t k = 0; k + 2 < pc.xyz.size(); k += 3) fprintf(opub, "c,%.9g,%.9g,%.9g\n", pc.xyz[k], pc.xyz[k + 1], pc.xyz[k + 2]);
+            for (size_t k = 0; k + 2 < mg.xyz.size(); k += 3) fprintf(opub, "m,%.9g,%.9g,%.9g\n", mg.xyz[k], mg.xyz[k + 1], mg.xyz[k + 2]);
+        }
         if (w == handback_frame) {
             std::unique_ptr<ResidentEstimators> next(new ResidentEstimators(N, 512, 512));
             if (device_imu) next->useDeviceImu();
+            if (pub_points) next->usePublishedOutputs(pub_points);
             if (!relo.empty()) { int mm = 1; for (const ReloRec& q : relo) mm = std::max(mm, (int)q.match.size()); next->useRelocalisation(mm); }
             std::vector<std::unique_ptr<Estimator>> back;
             for (int i = 0; i < N; ++i) {
@@ -893,6 +918,7 @@ static int replay_seq(const char* in, const char* out, const char* frames = null
         }
     fclose(o);
     if (orelo) fclose(orelo);
+    if (opub) fclose(opub);
     fclose(rd.f);
     vg_destroy(h);
     return 0;

@@ -59,6 +59,48 @@ void ResidentEstimators::useRelocalisation(int max_match) {
     max_match_ = max_match;
 }
 
+void ResidentEstimators::usePublishedOutputs(int max_points) {
+    if (max_points < 1 || max_points > 1024) throw std::runtime_error("usePublishedOutputs(): max_points outside 1 .. 1024");
+    max_points_ = max_points;
+    pub_.assign(est_.size(), Published());
+    if (begun_) reservePublished();
+}
+
+void ResidentEstimators::reservePublished() {
+    if (vg_ba_seq_outputs_reserve(vg_, max_points_) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_outputs_reserve: ") + vg_last_error(vg_));
+    if (vg_ba_seq_outputs_async(vg_) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_outputs_async: ") + vg_last_error(vg_));
+    fetchPublished();
+}
+
+void ResidentEstimators::fetchPublished() {
+    struct F3 { float x, y, z; };
+    struct F2 { float x, y; };
+    const size_t mp = (size_t)max_points_;
+    std::vector<F3> p3(mp), pc(mp), mg(mp), q3;
+    std::vector<F2> nm(mp), uv(mp), quv, qnm;
+    std::vector<int> id(mp);
+    for (int i = 0; i < size(); ++i) {
+        vg_ba_seq_outputs o;
+        memset(&o, 0, sizeof(o));
+        o.struct_size = (int)sizeof(o);
+        o.kf_point_3d = &p3[0].x; o.kf_norm = &nm[0].x; o.kf_uv = &uv[0].x; o.kf_id = id.data(); o.cloud_xyz = &pc[0].x; o.margin_xyz = &mg[0].x;
+        if (vg_ba_seq_get_outputs(vg_, i, &o) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_get_outputs: ") + vg_last_error(vg_));
+        Published& p = pub_[i];
+        p.kf.valid = o.keyframe_valid != 0; p.kf.status = p.cloud.status = p.margin.status = o.status;
+        p.kf.count = o.n_keyframe; p.cloud.count = o.n_cloud; p.margin.count = o.n_margin;
+        p.kf.stamp = est_[i].Headers[WINDOW_SIZE - 2];
+        const int n = vg_pack::unpack_keyframe(o, max_points_, q3, quv, qnm, p.kf.point_id, p.kf.vio_T_w_i, p.kf.vio_R_w_i);
+        p.kf.point_3d.clear(); p.kf.point_2d_uv.clear(); p.kf.point_2d_norm.clear();
+        if (n) {
+            p.kf.point_3d.assign(&q3[0].x, &q3[0].x + 3 * (size_t)n);
+            p.kf.point_2d_uv.assign(&quv[0].x, &quv[0].x + 2 * (size_t)n);
+            p.kf.point_2d_norm.assign(&qnm[0].x, &qnm[0].x + 2 * (size_t)n);
+        }
+        p.cloud.xyz.assign(&pc[0].x, &pc[0].x + 3 * (size_t)std::min(o.n_cloud, max_points_));
+        p.margin.xyz.assign(&mg[0].x, &mg[0].x + 3 * (size_t)std::min(o.n_margin, max_points_));
+    }
+}
+
 bool ResidentEstimators::setReloFrame(int i, double frame_stamp, int frame_index, const std::vector<Vector3d>& match_points, const Vector3d& relo_t,
                                       const Matrix3d& relo_r) {
     if (!begun_ || !max_match_) throw std::runtime_error("setReloFrame(): useRelocalisation() before begin() reserves the loop-pose block");
@@ -254,6 +296,7 @@ void ResidentEstimators::begin() {
         if (vg_ba_seq_imu_begin(vg_, size(), &ic, seed.data()) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_imu_begin: ") + vg_last_error(vg_));
     }
     begun_ = true;
+    if (max_points_) reservePublished();
 }
 
 // Utility::deltaQ(theta).toRotationMatrix() (utility.h:16-28; Eigen's toRotationMatrix does not normalise)
@@ -311,7 +354,10 @@ void ResidentEstimators::solve() {
     } else {
         stepFromHost();
     }
+    // the keyframe message and the clouds of the window this step leaves: enqueued behind its slide, fetched once the mirror has followed
+    if (max_points_ && vg_ba_seq_outputs_async(vg_) != VG_OK) throw std::runtime_error(std::string("vg_ba_seq_outputs_async: ") + vg_last_error(vg_));
     finishStep();
+    if (max_points_) fetchPublished();
 }
 
 // processIMU's results from the host: the running intervals (and the merged ones) integrated in one batched call, the propagated guess

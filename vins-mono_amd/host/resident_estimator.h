@@ -88,6 +88,27 @@ class ResidentEstimators {
     // found, the NEXT solve() carries the loop pose (initially the pose of that frame) and one factor per matched landmark
     // (match_points[k] = x, y, feature id; ids ascending), selected on the device (vg_ba_seq_set_relo).  Returns whether it was found.
     bool setReloFrame(int i, double frame_stamp, int frame_index, const std::vector<Vector3d>& match_points, const Vector3d& relo_t, const Matrix3d& relo_r);
+    // Opt-in, before or after begin(): every solve() also forms, on the device, what the estimator node publishes after the frame
+    // (pubKeyframe / pubPointCloud, visualization.cpp:348-404 / :240-296; vg_ba_seq_outputs_*): room for max_points (1 .. 1024)
+    // rows per list and estimator.  The lists of the LAST solve() are in keyframe(i), pointCloud(i), marginCloud(i); right after
+    // begin() (or this call on a running batch) they are those of the windows as handed over.
+    struct Keyframe {                         // the arguments of host/keyframe.h's KeyFrame constructors, packed floats (cv::Point3f / Point2f)
+        bool valid = false;                   // marginalization_flag == 0 after the last solve(): the reference would publish it (:351)
+        int status = 0, count = 0;            // vg_ba_seq_outputs::status, n_keyframe (the true count; the vectors hold min(count, max_points))
+        double stamp = 0;                     // Headers[WINDOW_SIZE - 2] of the mirror (the sequence keeps no stamps)
+        Vector3d vio_T_w_i;
+        Matrix3d vio_R_w_i;
+        std::vector<float> point_3d, point_2d_uv, point_2d_norm;     // 3 / 2 / 2 floats per point
+        std::vector<double> point_id;
+    };
+    struct Cloud {
+        int status = 0, count = 0;
+        std::vector<float> xyz;               // 3 floats per point
+    };
+    void usePublishedOutputs(int max_points);
+    const Keyframe& keyframe(int i) const { return pub_.at(i).kf; }
+    const Cloud& pointCloud(int i) const { return pub_.at(i).cloud; }
+    const Cloud& marginCloud(int i) const { return pub_.at(i).margin; }
     void begin();                             // vg_ba_seq_begin once every estimator has been handed over
     // The way back, between two frames: window i of the running sequence into the members of a host Estimator (Ps / Rs / Vs / Bas /
     // Bgs, ric / tic / td, pre_integrations[1 .. WINDOW_SIZE - 1] -- the last one with its raw samples --, f_manager.feature,
@@ -113,6 +134,11 @@ class ResidentEstimators {
     bool device_imu_ = false;
     int max_samples_ = 512;
     int max_match_ = 0;
+    struct Published { Keyframe kf; Cloud cloud, margin; };
+    std::vector<Published> pub_;
+    int max_points_ = 0;                      // usePublishedOutputs (0: not asked for)
+    void reservePublished();                  // vg_ba_seq_outputs_reserve + the lists of the windows as they stand
+    void fetchPublished();                    // vg_ba_seq_get_outputs of every estimator into pub_
     void stepFromHost();                      // solve(): the host-fed step (pre-integration + propagated guess from here)
     void finishStep();                        // solve(): download, mirror, sample buffers
 };

@@ -8,6 +8,7 @@
 // transform of relo_Pose, configuration globals) stays in their own files.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -592,6 +593,35 @@ void pack_kf_pnp(const KF& kf, const std::vector<P3>& matched_3d, const std::vec
     }
 }
 
+// the estimator's keyframe message (vg_ba_seq_get_outputs of one window, its kf_* arrays filled, max_points rows each) as the arguments of
+// the KeyFrame constructors of host/keyframe.h: point_3d, point_2d_uv, point_2d_norm and point_id per window point (the id as the double the
+// reference's class keeps), vio_T_w_i, vio_R_w_i = the matrix of the normalised pose quaternion.  P3 / P2: three / two packed floats
+// (cv::Point3f / cv::Point2f).  The stamp and the image are the caller's.  Returns the number of points (min(n_keyframe, max_points)).
+template <class P3, class P2, class V3, class M3>
+int unpack_keyframe(const vg_ba_seq_outputs& o, int max_points, std::vector<P3>& point_3d, std::vector<P2>& point_2d_uv, std::vector<P2>& point_2d_norm,
+                    std::vector<double>& point_id, V3& vio_T_w_i, M3& vio_R_w_i) {
+    static_assert(sizeof(P3) == 3 * sizeof(float) && sizeof(P2) == 2 * sizeof(float), "packed float points");
+    const int n = std::max(0, std::min(o.n_keyframe, max_points));
+    if (n && (!o.kf_point_3d || !o.kf_uv || !o.kf_norm || !o.kf_id)) throw std::runtime_error("unpack_keyframe: the kf_* arrays of vg_ba_seq_outputs are not all there");
+    point_3d.resize(n); point_2d_uv.resize(n); point_2d_norm.resize(n); point_id.resize(n);
+    if (n) {
+        std::memcpy(&point_3d[0], o.kf_point_3d, sizeof(P3) * n);
+        std::memcpy(&point_2d_uv[0], o.kf_uv, sizeof(P2) * n);
+        std::memcpy(&point_2d_norm[0], o.kf_norm, sizeof(P2) * n);
+    }
+    for (int k = 0; k < n; ++k) point_id[k] = (double)o.kf_id[k];
+    const double* p = o.pose;
+    const double qn = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+    const double x = p[3] / qn, y = p[4] / qn, z = p[5] / qn, w = p[6] / qn;
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+    for (int r = 0; r < 3; ++r) {
+        vio_T_w_i(r) = p[r];
+        for (int c = 0; c < 3; ++c) vio_R_w_i(r, c) = R[3 * r + c];
+    }
+    return n;
+}
+
 // one request of vg_kf_loop_detect for a keyframe whose record is resident (kf.slot): flags VG_BOW_QUERY | VG_BOW_ADD is detectLoop,
 // VG_BOW_ADD alone addKeyFrameIntoVoc.  `out` is zeroed and gets its struct_size; the caller adds tap arrays if it wants them.
 template <class KF>
@@ -647,6 +677,12 @@ void vg_pack_bow(const KF& kf, int db, int frame_index, int flags, vg_bow_in& in
 template <class KF, class P3, class P2>
 void vg_pack_kf_pnp(const KF& kf, const std::vector<P3>& matched_3d, const std::vector<P2>& matched_2d_old_norm, const std::vector<int>& matched_id, vg_kf_pnp_in& in) {
     vg_pack::pack_kf_pnp(kf, matched_3d, matched_2d_old_norm, matched_id, in);
+}
+// (the unpacker of vg_ba_seq_get_outputs' keyframe message under the name the integration guide uses)
+template <class P3, class P2, class V3, class M3>
+int vg_unpack_keyframe(const vg_ba_seq_outputs& o, int max_points, std::vector<P3>& point_3d, std::vector<P2>& point_2d_uv, std::vector<P2>& point_2d_norm,
+                       std::vector<double>& point_id, V3& vio_T_w_i, M3& vio_R_w_i) {
+    return vg_pack::unpack_keyframe(o, max_points, point_3d, point_2d_uv, point_2d_norm, point_id, vio_T_w_i, vio_R_w_i);
 }
 // (the packer of vg_kf_add under the name the integration guide uses)
 template <class KF>
